@@ -189,7 +189,6 @@ if __name__ == "__main__":
     ap.add_argument("--classes", type=str, default=",".join(CLASSES))
     ap.add_argument("--option", action="append", default=[], help="engine option name=value (e.g. gru_mode=1)")
     a = ap.parse_args()
-    os.environ.setdefault("GPU_MAX_HW_QUEUES", "16")
     opts = {kv.split("=")[0]: int(kv.split("=")[1]) for kv in a.option}
     rep = run(a.numerics, a.isolation, a.seconds, a.threads, a.pages, classes=tuple(a.classes.split(",")), engine_options=opts)
     print(json.dumps(rep))
