@@ -114,10 +114,8 @@ OCRS_API ocrs_status ocrs_coalescer_selftest(int n_threads, int requests_per_thr
  *                     only: the relaxed / reduced modes have one persistent recurrence kernel for every request size)
  *   "gru_local"       persistent GRU kernels: 1 = a cluster of workgroups that finds itself on one XCD hands its state
  *                     over through that XCD's L2 (default), 0 = always through write-through stores
- *   "det_fuse"        1 = fused DoubleConv blocks of the detection U-Net where they win (default), 2 = for every block
- *                     shape that has a fused kernel, 0 = per-operator kernels only
- *   "det_mfma"        1 = the LDS-tiled DoubleConv blocks run their pointwise convolutions and ConvTranspose on the matrix
- *                     cores (default), 0 = thread-per-pixel VALU kernels
+ *   "det_fuse"        1 = fused DoubleConv blocks of the detection U-Net for every block shape that has a fused kernel
+ *                     (default; 2 = the same, kept for older callers), 0 = per-operator kernels only
  *   "det_stream"      1 (default) = the DoubleConv blocks of the U-Net's full-resolution level run as row-streaming wave
  *                     kernels (a wave walks down a 64-column strip, a lane keeps its pixel's channels in registers,
  *                     horizontal taps through DPP lane shifts), rows per wave chosen from the request's size; 8 / 14 / 32 =

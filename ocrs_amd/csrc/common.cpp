@@ -434,8 +434,7 @@ const OptDef kOptDefs[OPT_COUNT] = {
     {"gru_mode", "OCRS_GRU_MODE", GRU_PERSISTENT},      // 0 persistent recurrence kernel, 1 one launch per time step
     {"gru_gates", "OCRS_GRU_GATES", 1},                 // persistent GRU: gate-per-wave kernel when every row tile gets its own cluster
     {"gru_local", "OCRS_GRU_LOCAL", 1},                 // persistent GRU: 1 same-XCD clusters hand off through L2, 0 always write-through
-    {"det_fuse", "OCRS_DET_FUSE", 1},                   // fused DoubleConv blocks: 1 where they win, 2 every shape, 0 none
-    {"det_mfma", "OCRS_DET_MFMA", 1},                   // fused detection blocks: pointwise convs + ConvTranspose on MFMA (1); VALU kernels (0)
+    {"det_fuse", "OCRS_DET_FUSE", 1},                   // fused DoubleConv blocks for every shape that has one (1; 2 = the same), 0 none
     {"det_stream", "OCRS_DET_STREAM", 1},               // DoubleConv blocks of the full-resolution levels: row-streaming wave kernels (1; 8 / 14 / 32 rows per wave) or LDS-tiled (0)
     {"det_rows", "OCRS_DET_ROWS", 1},                   // DoubleConv blocks of the 16-64-channel levels: row-streaming workgroup kernels (1; 8 / 14 / 20 / 32 rows) or LDS-tiled (0)
     {"ccl_quad", "OCRS_CCL_QUAD", 1},                   // component labelling / root compaction: four pixels per thread on word-aligned masks (1) or one (0)
@@ -455,7 +454,7 @@ const OptDef kOptDefs[OPT_COUNT] = {
 // allowed set beyond 0 / 1
 struct OptRange { long lo, hi; long also[4]; };
 const OptRange kOptRanges[OPT_COUNT] = {
-    {0, 1, {}}, {0, 1, {}}, {0, 1, {}}, {0, 2, {}}, {0, 2, {}}, {0, 1, {8, 14, 32}}, {0, 1, {8, 14, 20, 32}}, {0, 1, {}}, {0, 1, {}}, {0, 1, {}}, {0, 1, {}},
+    {0, 1, {}}, {0, 1, {}}, {0, 1, {}}, {0, 2, {}}, {0, 1, {8, 14, 32}}, {0, 1, {8, 14, 20, 32}}, {0, 1, {}}, {0, 1, {}}, {0, 1, {}}, {0, 1, {}},
     {0, 2, {}}, {0, 64, {}}, {1, 4096, {}}, {0, 10000000, {}}, {0, 4096, {}}, {0, INT64_MAX, {}},
 };
 bool in_range(int i, long v) {
@@ -464,10 +463,11 @@ bool in_range(int i, long v) {
     for (long a : r.also) if (a && v == a) return true;
     return false;
 }
-// options of rounds 2-4 that round 5 removed with their kernels: still accepted by ocrs_set_option as no-ops, so that a caller
-// (or a launch script) written against the older header keeps working; their OCRS_* environment variables are ignored
+// options removed with their kernels (rounds 2-4's by round 5; later the VALU DoubleConv blocks' selector): still accepted
+// by ocrs_set_option as no-ops, so that a caller (or a launch script) written against an older header keeps working; their
+// OCRS_* environment variables are ignored
 const char* const kRetired[] = {"det_heavy", "det_tail", "gru_waves", "gru_background", "gru_scatter", "gru_gates_pack", "conv_occupancy",
-                                "gx_heavy", "gemm_nfast", "conv_a_lds", "gru_heavy", "heavy_priority"};
+                                "gx_heavy", "gemm_nfast", "conv_a_lds", "gru_heavy", "heavy_priority", "det_mfma"};
 std::atomic<long> g_opts[OPT_COUNT];
 std::once_flag g_opts_once;
 void init_options() {   // the only getenv of the option system: once per process

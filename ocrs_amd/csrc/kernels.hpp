@@ -112,13 +112,11 @@ struct DoubleConvArgs {
 struct StreamWeights {
     const float *wt, *bt, *wd1, *bd1, *wp1, *bp1, *wd2, *bd2, *wp2, *bp2, *wf, *bf;
 };
-// true if a fused kernel exists for the shape (cs skip channels, cx ConvT input channels or 0, ...) at this
-// fuse level (option "det_fuse": 1 = the shapes where fusion wins, 2 = every shape that has a kernel);
-// launches it when `launch` is set.  *on_mfma: the block's pointwise convs / ConvTranspose run on the matrix cores
-// (option "det_mfma").
+// true if a fused kernel exists for the shape (cs skip channels, cx ConvT input channels or 0, ...); launches it when
+// `launch` is set.  *on_mfma: the block's pointwise convs / ConvTranspose run on the matrix cores.
 // *path: which kernel family takes the shape with the current options and this request (a.n, a.h, a.w): 0 = LDS-tiled
 // block, 1 = row-streaming wave kernel, 2 = row-streaming workgroup kernel.
-bool double_conv_fused(const DoubleConvArgs& a, int cs, int cx, int cmid, int cout, bool pool, bool final_conv, int fuse_level,
+bool double_conv_fused(const DoubleConvArgs& a, int cs, int cx, int cmid, int cout, bool pool, bool final_conv,
                        bool launch, hipStream_t s, bool* on_mfma = nullptr, int* path = nullptr);
 // ---- kernels_det_stream.hip (r4): the same blocks as row-streaming register kernels for the full-resolution levels;
 // true if the shape has one (launches it when `launch` is set).  Same bits as the tiled blocks and the per-op kernels.

@@ -13,7 +13,7 @@
 //     operations are bias, then the nine taps in (ky, kx) order: the numeric spec's chain, bit for bit.
 //   * pointwise 1x1, ConvTranspose 2x2/s2, final 1x1: per-pixel chains over the lane's registers with wave-uniform
 //     weights as SGPR operands, pairs of output channels as v_pk_fma_f32 (measured on gfx950: plain v_fma_f32 69 TFLOP/s,
-//     v_pk_fma_f32 119 — tools/micro/valu_probe.hip).  The ConvTranspose's weights depend on the column's parity, which
+//     v_pk_fma_f32 119 — DESIGN.md §6.2.2).  The ConvTranspose's weights depend on the column's parity, which
 //     alternates across lanes: both parities are computed and the lane selects (the price of keeping one column per
 //     lane: 128 of the decoder block's 672 FMAs per pixel).
 //   * THE WEIGHT TAPE.  A row step uses every weight of the block exactly once (~700 floats for the level-0 decoder

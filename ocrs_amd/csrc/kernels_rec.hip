@@ -269,20 +269,11 @@ void to_seq_packed_ragged(const float* x, const RaggedView& in, int c, const int
 //     full-resolution activation is never written nor re-read, and the pool launches disappear.
 //     max(relu(a), relu(b)) over the window in (py, px) order is exactly MaxPool(ReLU(conv)).
 // BK = 16 keeps LDS at 33 KB/block and the kernel at 128 VGPRs, so four blocks (4 waves/SIMD)
-// share a CU and cover each other's barrier / LDS-fill phases (tools/conv_variants.sh: 113 TFLOP/s
-// vs 109 with three, 102 at BK = 32 with two; s_setprio around the MFMA cluster measured -1 %).
+// share a CU and cover each other's barrier / LDS-fill phases (113 TFLOP/s vs 109 with three, 102 at
+// BK = 32 with two; s_setprio around the MFMA cluster measured -1 %: docs/history/DESIGN_rounds_1-5.md).
 // ---------------------------------------------------------------------------
-#ifndef OCRS_CONV_BK
-#define OCRS_CONV_BK 16
-#endif
-constexpr int RG_BM = 128, RG_BK = OCRS_CONV_BK, RG_LDA = RG_BM + 1;
-
-#ifndef OCRS_CONV_WAVES
-#define OCRS_CONV_WAVES 4
-#endif
-#ifndef OCRS_ABL
-#define OCRS_ABL 0  // ablation builds (tools/conv_ablation.sh, tools/r6_session.sh instab; results are WRONG on purpose; 8 no epilogue, 16 half of K): 1 no barriers,
-#endif              // 2 no global loads, 4 no LDS writes
+constexpr int RG_BM = 128, RG_BK = 16, RG_LDA = RG_BM + 1;
+constexpr int CONV_WAVES = 4;   // blocks per CU of the exact kernels (128 VGPRs)
 // FLAT: the patches of a group tile the strip of ALL its images side by side (flat column c = img * Wp + x, Wp = W
 // rounded up to PW) instead of each image on its own, so only the last patch of a GROUP is ragged, not the last
 // patch of every image (group widths are multiples of 50: W / 4 = 87, 112, 137 ... wasted 7 % of the MFMA rows).
@@ -290,11 +281,7 @@ constexpr int RG_BM = 128, RG_BK = OCRS_CONV_BK, RG_LDA = RG_BM + 1;
 // the contraction on the bf16 matrix cores with both operands cut into SPLIT bf16 terms — split_mfma.hpp has the arithmetic,
 // the LDS layout and the pipeline.  Bw is then the weights' split image (split_weights).
 template <int BN, int TW, int PH, int PW, bool FLAT, int SPLIT = 0>   // SPLIT: 0 exact; 3 / 2 = bf16 planes per operand (relaxed / reduced numerics)
-#if defined(OCRS_PROBE_ACC_AGPR) || defined(OCRS_PROBE_ALL_AGPR)   // probe builds: room for the AGPR operands
-__global__ void __launch_bounds__(256, SPLIT != 0 ? 2 : OCRS_CONV_WAVES)
-#else
-__global__ void __launch_bounds__(256, SPLIT == 3 ? 2 : SPLIT == 2 ? 3 : OCRS_CONV_WAVES)   // (split: 72 / 48 KB of LDS per block)
-#endif
+__global__ void __launch_bounds__(256, SPLIT == 3 ? 2 : SPLIT == 2 ? 3 : CONV_WAVES)   // (split: 72 / 48 KB of LDS per block)
 conv3x3_ragged_kernel(const float* __restrict__ X, RaggedView rv, int cin, const float* __restrict__ Bw,
                       const float* __restrict__ bias, int cout, int relu, float* __restrict__ Y,
                       const int64_t* __restrict__ out_poff) {
@@ -347,7 +334,7 @@ conv3x3_ragged_kernel(const float* __restrict__ X, RaggedView rv, int cin, const
     // Per-thread A addressing, hoisted out of the K loop: the centre-pixel offset of each of the thread's
     // rows and a 9-bit mask of the taps that fall inside the image.  In the loop a load is then
     // base + (uniform tap delta), unconditional from a clamped address, and zeroed by a select — no
-    // divergent branches and no 64-bit multiplies (the load path cost 10 % of the kernel: tools/conv_ablation.sh).
+    // divergent branches and no 64-bit multiplies (the load path cost 10 % of the kernel: docs/history/DESIGN_rounds_1-5.md).
     int aoff[AV];        // ((y * W + x) * cin + akq * 4) of the centre pixel, clamped inside the image
     unsigned amask[AV];  // bit (3 * ky + kx) set <=> tap (ky, kx) of this row is inside the image
 #pragma unroll
@@ -474,7 +461,7 @@ conv3x3_ragged_kernel(const float* __restrict__ X, RaggedView rv, int cin, const
             }
         }
     };
-    const int nchunks = (OCRS_ABL & 16) ? K / RG_BK / 2 : K / RG_BK;  // even: cin % (2*RG_BK) == 0   (ablation 16: half of K)
+    const int nchunks = K / RG_BK;  // even: cin % (2*RG_BK) == 0
     if constexpr (SPLIT != 0) {
         static_assert(AV == 2, "split::pipeline counts four activation loads per chunk pair");
         split::pipeline<NP>(nchunks,   // nchunks % 4 == 0 (cin % 64 == 0: the host checks)
@@ -487,35 +474,24 @@ conv3x3_ragged_kernel(const float* __restrict__ X, RaggedView rv, int cin, const
     load_b(0, 0);
     commit(0, pa0);
     __syncthreads();
-#define OCRS_SYNC() do { if (!(OCRS_ABL & 1)) __syncthreads(); } while (0)
     for (int c = 0; c < nchunks; c += 2) {
         // even chunk c in buffer 0; chunk c+1's A half is already in registers
-        if (!(OCRS_ABL & 2)) load_b((c + 1) * RG_BK, 1);
+        load_b((c + 1) * RG_BK, 1);
         compute(0);
-        if (!(OCRS_ABL & 4)) commit(1, pa1);
-        OCRS_SYNC();
+        commit(1, pa1);
+        __syncthreads();
         // odd chunk c+1 in buffer 1; fetch the next pair
         const bool more = c + 2 < nchunks;
-        if (more && !(OCRS_ABL & 2)) {
+        if (more) {
             load_a_pair((c + 2) * RG_BK);
             load_b((c + 2) * RG_BK, 0);
         }
         compute(1);
-        if (more && !(OCRS_ABL & 4)) commit(0, pa0);
-        OCRS_SYNC();
+        if (more) commit(0, pa0);
+        __syncthreads();
     }
-#undef OCRS_SYNC
     }
 
-    if (OCRS_ABL & 8) {   // ablation: no epilogue (one never-taken store keeps the accumulators alive)
-        float sum = 0.0f;
-#pragma unroll
-        for (int t = 0; t < NTW; t++)
-#pragma unroll
-            for (int r = 0; r < 16; r++) sum += acc[0][t][r] + acc[1][t][r];
-        if (sum == 1.2345e-30f) Y[0] = sum;
-        return;
-    }
     // ---- epilogue: ReLU, optional in-register MaxPool, store.
     // GEMM row m = wm*64 + i*32 + q, q = (r&3) + 8*(r>>2) + 4*half, is patch pixel (m / TW, m % TW):
     //   TW = 32: ty = 2*wm + i,              tx = q            vertical partner: the other i, same r
@@ -531,10 +507,7 @@ conv3x3_ragged_kernel(const float* __restrict__ X, RaggedView rv, int cin, const
     // split::pipeline ends behind a drained barrier, the operand buffers are idle there too).  The pooled layers store half / a quarter as
     // much and get SLOWER through the tile (9.87-9.89 -> 10.23-10.28 ms, whether each half or both halves' outputs are staged
     // at once): they keep the direct form below.
-#ifndef OCRS_DIRECT_EPILOGUES
-#define OCRS_DIRECT_EPILOGUES 0   // ablation builds: see kernels_nn.hip
-#endif
-    if (!OCRS_DIRECT_EPILOGUES && PH == 1 && PW == 1 && n0 + BN <= cout && (cout & 3) == 0 && (((uintptr_t)Y) & 15) == 0) {
+    if (PH == 1 && PW == 1 && n0 + BN <= cout && (cout & 3) == 0 && (((uintptr_t)Y) & 15) == 0) {
         constexpr int WN = BN / 2, LPR = WN / 4, RPI = 64 / LPR, NIT = 32 / RPI;
         static_assert(SPLIT != 0 || 4 * 32 * WN <= 2 * RG_BK * RG_LDA + 2 * RG_BK * BN, "staging must fit the operand tiles");   // split: 48 / 72 KB
         float* stage = lds + wave * (32 * WN);
@@ -631,19 +604,14 @@ conv3x3_ragged_kernel(const float* __restrict__ X, RaggedView rv, int cin, const
 // between two images (flat column = image * Wg + x, Wg = W + 1 rounded up to even), so that a position is either a
 // pixel of ONE image or padding for both of its neighbours.
 // ---------------------------------------------------------------------------
-#ifndef OCRS_F12_ABL
-#define OCRS_F12_ABL 0   // ablation builds (tools/conv12_ablation.sh; wrong results on purpose): 1 no conv1 stage, 2 no weight loads, 4 an eighth of the MFMAs
-#endif
 constexpr int F12_MID = 32, F12_COUT = 64, F12_TW = 16, F12_TH = 8, F12_HW = F12_TW + 2, F12_HH = F12_TH + 2;
 constexpr int F12_NPOS = F12_HH * F12_HW;          // 180 halo positions
 constexpr int F12_LD = F12_MID + 1;                // tile row stride (floats): consecutive positions -> consecutive banks
-#ifndef OCRS_F12_BK
-#define OCRS_F12_BK 16   // 32 (half the barriers, four blocks per CU instead of five) measured the same
-#endif
-constexpr int F12_BK = OCRS_F12_BK;                // K chunk of conv2's weight stream (one barrier per chunk)
+constexpr int F12_BK = 16;                         // K chunk of conv2's weight stream (one barrier per chunk); 32 (half the
+                                                   // barriers, four blocks per CU instead of five) measured the same
 constexpr size_t F12_LDS = (size_t)(F12_NPOS * F12_LD + 2 * F12_BK * F12_COUT) * sizeof(float);
 
-__global__ void __launch_bounds__(256, OCRS_CONV_WAVES)
+__global__ void __launch_bounds__(256, CONV_WAVES)
 conv12_fused_kernel(const float* __restrict__ X0, RaggedView in0, RaggedView mid, const float* __restrict__ w1,
                     const float* __restrict__ b1, const float* __restrict__ Bw, const float* __restrict__ bias,
                     float* __restrict__ Y, const int64_t* __restrict__ out_poff) {
@@ -694,7 +662,7 @@ conv12_fused_kernel(const float* __restrict__ X0, RaggedView in0, RaggedView mid
 #pragma unroll
         for (int c = 0; c < 2; c++) bq[c] = f32x2{b1[4 * q + 2 * c], b1[4 * q + 2 * c + 1]};
         const float* __restrict__ xg = X0 + in0.poff[g];
-        for (int p = tid >> 3; p < ((OCRS_F12_ABL & 1) ? 0 : F12_NPOS); p += 32) {
+        for (int p = tid >> 3; p < F12_NPOS; p += 32) {
             const int hy = p / F12_HW, hx = p - hy * F12_HW;
             const int y = y0 - 1 + hy;
             int x = x0 - 1 + hx, ir = 0;
@@ -772,12 +740,12 @@ conv12_fused_kernel(const float* __restrict__ X0, RaggedView in0, RaggedView mid
     static_assert(F12_MID % F12_BK == 0 && F12_BK % 16 == 0, "chunk size");
 #pragma unroll
     for (int c = 0; c < NCH; c++) {
-        if (c + 1 < NCH && !(OCRS_F12_ABL & 2)) load_b((c + 1) * F12_BK, (c + 1) & 1);
+        if (c + 1 < NCH) load_b((c + 1) * F12_BK, (c + 1) & 1);
         const int tap = (c * F12_BK) / F12_MID, ch0 = (c * F12_BK) % F12_MID;
         const int toff = ((tap / 3) * F12_HW + tap % 3) * LD + ch0;
         const float* b = Bs + (c & 1) * F12_BK * BN + wn * 32 + l31;
 #pragma unroll
-        for (int kp = 0; kp < ((OCRS_F12_ABL & 4) ? 1 : F12_BK / 2); kp++) {
+        for (int kp = 0; kp < F12_BK / 2; kp++) {
             const float a0 = T[abase[0] + toff + 2 * kp], a1 = T[abase[1] + toff + 2 * kp];
             const float bt = b[(2 * kp + half) * BN];
             acc[0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, bt, acc[0], 0, 0, 0);
@@ -827,11 +795,7 @@ constexpr int F12S_BTAP = F12_COUT * 64;                      // bytes per plane
 constexpr size_t f12s_lds(int np) { return (size_t)np * (F12S_TILE + 3 * F12S_BTAP); }   // 74.4 KB (NP 3) / 49.6 KB (NP 2)
 
 template <int NP>
-#if defined(OCRS_PROBE_ACC_AGPR) || defined(OCRS_PROBE_ALL_AGPR)
-__global__ void __launch_bounds__(256, 2)
-#else
 __global__ void __launch_bounds__(256, NP == 3 ? 2 : 3)
-#endif
 conv12_fused_split_kernel(const float* __restrict__ X0, RaggedView in0, RaggedView mid, const float* __restrict__ w1,
                           const float* __restrict__ b1, const uint16_t* __restrict__ Bimg, const float* __restrict__ bias,
                           float* __restrict__ Y, const int64_t* __restrict__ out_poff) {

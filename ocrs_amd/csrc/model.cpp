@@ -275,7 +275,7 @@ std::unique_ptr<HipModel> HipModel::load(const void* data, size_t len, int devic
                 else if (uses(ops[k].out) == 0) continue;
             }
             k::DoubleConvArgs none{};
-            if (!k::double_conv_fused(none, b.cs, b.cx, b.cmid, b.cout, b.pool >= 0, b.fin >= 0, 2, false, nullptr)) continue;
+            if (!k::double_conv_fused(none, b.cs, b.cx, b.cmid, b.cout, b.pool >= 0, b.fin >= 0, false, nullptr)) continue;
             {   // a row-streaming kernel for the shape: its weights laid out as the tape a row step reads (kernels_det_stream.hip)
                 auto host = [&](int op, int j) -> const float* { return op >= 0 ? slab.data() + fops[op].w[j].off : nullptr; };
                 k::StreamWeights hw{host(b.convt, 0), host(b.convt, 1), host(b.dw1, 0), host(b.dw1, 1), host(b.pw1, 0), host(b.pw1, 1),
@@ -466,11 +466,11 @@ float* HipModel::run_device(Workspace& ws, const float* d_in, int n, int h, int 
                 da.tape = b.tape; da.tape_len = b.tape_len; da.rtape = b.rtape; da.rtape_len = b.rtape_len;
                 // Is there a fused kernel for THIS request (its page count and sizes, not just the block's channel counts)?  A
                 // query with the real arguments: the row-streaming kernels decline some requests (more than 8 pages, an odd pad
-                // offset) and two block shapes have no other fused kernel when option det_mfma is 0 — those fall through to the
+                // offset) and the next kernel family takes them; a block that no fused kernel takes falls through to the
                 // per-operator kernels below.
                 bool on_mfma = false;
                 int path = 0;   // which kernel family will take it (nothing is launched by the query)
-                if (ok) ok = k::double_conv_fused(da, b.cs, b.cx, b.cmid, b.cout, b.pool >= 0, b.fin >= 0, det_fuse, false, nullptr, &on_mfma, &path);
+                if (ok) ok = k::double_conv_fused(da, b.cs, b.cx, b.cmid, b.cout, b.pool >= 0, b.fin >= 0, false, nullptr, &on_mfma, &path);
                 const double px = (double)sk.n * sk.h * sk.w;
                 double out_floats = 0;
                 if (ok) {
@@ -500,7 +500,7 @@ float* HipModel::run_device(Workspace& ws, const float* d_in, int n, int h, int 
                                             2.0 * px * (b.convt >= 0 ? (double)b.cx * b.cs : 0.0);
                     bool launched = false;
                     timed(path == 1 ? KC_DET_STREAM_WAVE : path == 2 ? KC_DET_STREAM_ROWS : KC_DET_BLOCK, fl, 4.0 * (px * b.cs + px1 * b.cx + out_floats), [&] {
-                        launched = k::double_conv_fused(da, b.cs, b.cx, b.cmid, b.cout, b.pool >= 0, b.fin >= 0, det_fuse, true, st);
+                        launched = k::double_conv_fused(da, b.cs, b.cx, b.cmid, b.cout, b.pool >= 0, b.fin >= 0, true, st);
                     }, on_mfma ? fl_dense : 0.0);
                     if (!launched) fail(OCRS_ERR_RUN_FAILED, "model run failed: internal (no fused kernel took the DoubleConv block its query accepted)");
                     for (int q = b.first + 1; q <= b.last; q++) covered[q] = 1;

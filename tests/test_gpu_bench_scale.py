@@ -292,8 +292,8 @@ def test_gru_modes_give_identical_bits(engine):
 @pytest.mark.parametrize("in_hw,depths", [((800, 600), (8, 16, 32, 32, 64, 128, 256)), ((160, 128), (8, 16, 32, 32)),
                                            ((232, 184), (8, 16, 32, 32, 64))])
 def test_fused_double_conv_blocks_equal_unfused_and_oracle(in_hw, depths):
-    """Detection CNN: the fused LDS-tiled DoubleConv launches (option det_fuse = 1, default) against the unfused
-    kernels (det_fuse = 0), bit for bit, on 3 pages through the Model::run seam — tile edges that are not multiples of
+    """Detection CNN: the fused DoubleConv launches (option det_fuse = 1, default, and 2, its older spelling) against the
+    unfused kernels (det_fuse = 0), bit for bit, on 3 pages through the Model::run seam — tile edges that are not multiples of
     the tile (600 = 18 x 32 + 24; 184 = 5 x 32 + 24), odd sizes under the pools (75 -> 37: the decoder pads `up`), and
     the small model against the oracle's exact chain as well."""
     from oracle.nn import OracleGraph
@@ -306,16 +306,12 @@ def test_fused_double_conv_blocks_equal_unfused_and_oracle(in_hw, depths):
         _lib.set_option("det_fuse", 0)
         ref = model.run(x)
         outs = {}
-        for mfma in (2, 1, 0):               # r3: pointwise convs of the fused blocks on MFMA: + C = 32 levels / default / none
-            _lib.set_option("det_mfma", mfma)
-            _lib.set_option("det_fuse", 2)   # every block shape that has a fused kernel
-            outs[(mfma, 2)] = model.run(x)
-            _lib.set_option("det_fuse", 1)   # the default: only the shapes where fusion wins
-            outs[(mfma, 1)] = model.run(x)
+        for fuse in (2, 1):
+            _lib.set_option("det_fuse", fuse)
+            outs[fuse] = model.run(x)
     finally:
         _lib.set_option("det_fuse", 1)
-        _lib.set_option("det_mfma", 1)
-    got = outs[(1, 1)]   # the defaults
+    got = outs[1]   # the defaults
     assert got.shape == ref.shape == (3, 1) + in_hw
     for key, o in outs.items():
         assert np.array_equal(o, ref), key
@@ -324,11 +320,11 @@ def test_fused_double_conv_blocks_equal_unfused_and_oracle(in_hw, depths):
 
 
 @pytest.mark.parametrize("n", [9, 16])
-def test_blocks_without_a_fused_kernel_for_the_request_fall_back_to_the_per_operator_kernels(n):
-    """det_mfma = 0 with det_fuse = 1: the (32, 32, 32, 32) and (32, 64, 32, 32) decoder blocks then have ONE fused kernel, the
-    row-streaming one, and it declines requests of more than 8 pages.  The executor's query must be made with the request's
-    arguments so that those blocks run on the per-operator kernels (round 4 queried with empty arguments, marked the
-    operators as done and launched nothing: garbage, silently).  Same bits as det_fuse = 0 and as the defaults."""
+def test_requests_the_row_kernels_decline_get_the_same_bits_from_the_kernel_that_takes_them(n):
+    """The row-streaming workgroup kernels of the 16-64-channel blocks decline requests of more than 8 pages.  The executor's
+    query must be made with the request's arguments so that another kernel takes those blocks (round 4 queried with empty
+    arguments, marked the operators as done and launched nothing: garbage, silently).  The defaults, det_fuse = 0 and the
+    row kernels forced on for every request size (det_rows = 32) give the same bits."""
     dbuf = M.detection_model_bytes((232, 184), (8, 16, 32, 32, 64))
     model = Model.load_bytes(dbuf)
     rng = np.random.default_rng(n)
@@ -338,12 +334,9 @@ def test_blocks_without_a_fused_kernel_for_the_request_fall_back_to_the_per_oper
         _lib.set_option("det_fuse", 0)
         unfused = model.run(x)
         _lib.set_option("det_fuse", 1)
-        _lib.set_option("det_mfma", 0)
-        got = model.run(x)
-        _lib.set_option("det_rows", 32)          # and with the row kernels forced on for every request size
+        _lib.set_option("det_rows", 32)          # the row kernels forced on for every request size
         forced = model.run(x)
     finally:
         _lib.set_option("det_fuse", 1)
-        _lib.set_option("det_mfma", 1)
         _lib.set_option("det_rows", 1)
-    assert np.array_equal(unfused, ref) and np.array_equal(got, ref) and np.array_equal(forced, ref)
+    assert np.array_equal(unfused, ref) and np.array_equal(forced, ref)

@@ -8,8 +8,7 @@
 //   hazard_repro [--aggressor split3|split2|exact|none] [--seconds S] [--lines N] [--split-cus A]
 //                [--victim-streams V]
 // --split-cus A: aggressor on a stream confined to compute units [0, A), victims on the complementary units
-// (hipExtStreamCreateWithCUMask).  --lines N: victim occupancy (64 * N workgroups per launch).  A build with
-// -DOCRS_CROP_SETPRIO=n raises the victim's wave priority (s_setprio) — see build_hazard_repro.sh.
+// (hipExtStreamCreateWithCUMask).  --lines N: victim occupancy (64 * N workgroups per launch).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
