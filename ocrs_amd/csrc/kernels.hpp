@@ -136,8 +136,8 @@ void avgpool(const float* x, int n, int h, int w, int c, int kh, int kw, float* 
 void padcat(const float* skip, int n, int sh, int sw, int cs, const float* x, int h, int w, int cx, float* y,
             hipStream_t s);
 void sigmoid(const float* x, float* y, int64_t count, hipStream_t s);
-// pointwise conv with Cout == 1 (+ optional sigmoid): y[p] = act(b + sum_c x[p,c] w[c])
-void conv1x1_cout1(const float* x, int64_t pixels, int cin, const float* wt, const float* bias, int do_sigmoid,
+// pointwise conv with Cout == 1 (+ optional ReLU, then optional sigmoid): y[p] = act(b + sum_c x[p,c] w[c])
+void conv1x1_cout1(const float* x, int64_t pixels, int cin, const float* wt, const float* bias, int relu, int do_sigmoid,
                    float* y, hipStream_t s);
 // [N,1,W,C] -> [W,N,C]
 void to_seq(const float* x, int n, int w, int c, float* y, hipStream_t s);

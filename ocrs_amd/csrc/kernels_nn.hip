@@ -121,7 +121,17 @@ __global__ void __launch_bounds__(256) gemm_mfma_kernel(GemmDesc d) {
 
         for (int kk = 0; kk < kc; kk += 4) {
             float4 av = make_float4(0.f, 0.f, 0.f, 0.f);
-            if (a_ok) av = *reinterpret_cast<const float4*>(arow + kk);
+            if (a_ok) {
+                if (kk + 4 <= kc) {
+                    av = *reinterpret_cast<const float4*>(arow + kk);
+                } else {
+                    // K tail (K % 4 != 0; never im2col): load only columns < K.  Past K the B rows are zero, but a
+                    // NaN / Inf read from the next row (or past the tensor) would still poison this row's output.
+                    av.x = arow[kk];
+                    if (kk + 1 < kc) av.y = arow[kk + 1];
+                    if (kk + 2 < kc) av.z = arow[kk + 2];
+                }
+            }
             const float a0 = half ? av.y : av.x;
             const float a1 = half ? av.w : av.z;
             const float* b0p = &lds_b[(kk + half) * BN + l31];
@@ -1053,7 +1063,7 @@ void sigmoid(const float* x, float* y, int64_t count, hipStream_t s) {
 // output layer.  y[p] = act(b + chain_c fmaf(x[p,c], w[c])).
 __global__ void __launch_bounds__(256)
 conv1x1_cout1_kernel(const float* __restrict__ x, int64_t pixels, int cin, const float* __restrict__ wt,
-                     const float* __restrict__ bias, int do_sigmoid, float* __restrict__ y) {
+                     const float* __restrict__ bias, int relu, int do_sigmoid, float* __restrict__ y) {
     for (int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; p < pixels; p += (int64_t)gridDim.x * blockDim.x) {
         float acc = bias[0];
         const float* xp = x + p * cin;
@@ -1068,15 +1078,16 @@ conv1x1_cout1_kernel(const float* __restrict__ x, int64_t pixels, int cin, const
         } else {
             for (int c = 0; c < cin; c++) acc = fmaf(xp[c], wt[c], acc);
         }
+        if (relu) acc = acc > 0.0f ? acc : 0.0f;
         y[p] = do_sigmoid ? spec_sigmoidf(acc) : acc;
     }
 }
 
-void conv1x1_cout1(const float* x, int64_t pixels, int cin, const float* wt, const float* bias, int do_sigmoid,
+void conv1x1_cout1(const float* x, int64_t pixels, int cin, const float* wt, const float* bias, int relu, int do_sigmoid,
                    float* y, hipStream_t s) {
     int grid = (int)((pixels + 255) / 256 < 16384 ? (pixels + 255) / 256 : 16384);
     if (grid < 1) grid = 1;
-    hipLaunchKernelGGL(conv1x1_cout1_kernel, dim3(grid), dim3(256), 0, s, x, pixels, cin, wt, bias, do_sigmoid, y);
+    hipLaunchKernelGGL(conv1x1_cout1_kernel, dim3(grid), dim3(256), 0, s, x, pixels, cin, wt, bias, relu, do_sigmoid, y);
 }
 
 // [N,1,W,C] -> [W,N,C]

@@ -145,6 +145,38 @@ std::unique_ptr<HipModel> HipModel::load(const void* data, size_t len, int devic
         }
         m->ops.push_back(op);
     }
+    // Channel counts, inferred statically: every input slot is the model input (slot 0, one channel) or the output of
+    // an earlier op, and every op with a `cin` reads a slot of exactly that many channels.  The kernels index their
+    // input with lda = cin; a mismatch or an unwritten slot would read out of bounds (or through a null pointer).
+    {
+        std::vector<int64_t> chans(hd.n_slots, -1);   // -1: not written yet
+        chans[0] = 1;
+        for (uint32_t i = 0; i < hd.n_ops; i++) {
+            const FileOp& f = fops[i];
+            auto in = [&](int32_t sl) {
+                if (chans[sl] < 0)
+                    fail(OCRS_ERR_IO, "op %u (%s): input slot %d is not written by an earlier op", i, kOpNames[f.type], sl);
+                return chans[sl];
+            };
+            const int64_t c0 = in(f.in0);
+            auto need = [&](int64_t want, const char* what) {
+                if (c0 != want)
+                    fail(OCRS_ERR_IO, "op %u (%s): %s is %lld but input slot %d carries %lld channels", i, kOpNames[f.type], what,
+                         (long long)want, f.in0, (long long)c0);
+            };
+            int64_t co = c0;
+            switch (f.type) {
+                case OP_CONV: case OP_CONVT2: case OP_LINEAR: need(f.cin, "cin"); co = f.cout; break;
+                case OP_DWCONV3: need(f.cin, "channels"); break;
+                case OP_GRU: need(f.cin, "input size"); co = 2LL * f.hidden; break;
+                case OP_PADCAT: co = c0 + in(f.in1); break;
+                default: break;
+            }
+            if (co > (1 << 24)) fail(OCRS_ERR_IO, "op %u (%s): %lld output channels", i, kOpNames[f.type], (long long)co);
+            chans[f.out] = co;
+        }
+        if (chans[hd.out_slot] < 0) fail(OCRS_ERR_IO, "the output slot %u is not written by any op", hd.out_slot);
+    }
     // everything above is validation on the host (a malformed file fails before any device work); from here on
     // the thread is bound to the device that will hold the weights
     DeviceScope bind(device);
@@ -269,7 +301,7 @@ std::unique_ptr<HipModel> HipModel::load(const void* data, size_t len, int devic
             const int k = j + 4;
             if (k < n && ops[k].type == OP_MAXPOOL && ops[k].kh == 2 && ops[k].kw == 2 && ops[k].in0 == p2.out && b.convt < 0) {
                 b.pool = k; b.last = k;
-            } else if (k < n && pw11(ops[k]) && ops[k].cout == 1 && ops[k].in0 == p2.out && uses(p2.out) == 1 && b.convt >= 0) {
+            } else if (k < n && pw11(ops[k]) && ops[k].cout == 1 && !ops[k].relu && ops[k].in0 == p2.out && uses(p2.out) == 1 && b.convt >= 0) {
                 b.fin = k; b.last = k;
                 if (k + 1 < n && ops[k + 1].type == OP_SIGMOID && ops[k + 1].fused_into_prev) { b.sig = k + 1; b.last = k + 1; }
                 else if (uses(ops[k].out) == 0) continue;
@@ -553,7 +585,7 @@ float* HipModel::run_device(Workspace& ws, const float* d_in, int n, int h, int 
                 const double cbytes = 4.0 * (double)px * (op.cin + op.cout) + wbytes(op, 0);
                 if (op.kh == 1 && op.kw == 1 && op.cout == 1) {
                     timed(KC_CONV1X1_SIGMOID, cflops, cbytes,
-                          [&] { k::conv1x1_cout1(x, px, op.cin, op.w[0], op.w[1], next_sigmoid ? 1 : 0, y, st); });
+                          [&] { k::conv1x1_cout1(x, px, op.cin, op.w[0], op.w[1], op.relu, next_sigmoid ? 1 : 0, y, st); });
                 } else if (op.kh == 1 && op.kw == 1 && (op.cin % 4) == 0) {
                     k::GemmDesc d{};
                     d.A = x; d.lda = op.cin; d.B = op.w[0]; d.ldb = op.cout; d.bias = op.w[1];

@@ -89,6 +89,8 @@ class OracleGraph:
                 y = clib.gru_bidir(a, ws)
             elif t == OP_LINEAR:
                 y = clib.linear(a, W[0].reshape(op["cin"], op["cout"]), W[1])
+                if op["relu"]:   # the executor's GEMM epilogue: v > 0 ? v : 0
+                    y = np.where(y > 0, y, np.float32(0))
             elif t == OP_LOGSOFTMAX:
                 y = clib.log_softmax(a)
             else:
@@ -168,6 +170,8 @@ class OracleGraph:
                     y, _ = torch._VF.gru(a, h0, flat, True, 1, 0.0, False, True, False)
                 elif t == OP_LINEAR:
                     y = a @ cw[0].reshape(op["cin"], op["cout"]) + cw[1]
+                    if op["relu"]:
+                        y = F.relu(y)
                 elif t == OP_LOGSOFTMAX:
                     y = F.log_softmax(a, dim=-1)
                 slots[op["out"]] = y

@@ -1,0 +1,270 @@
+"""Float64 definitions of the graph ops and elementwise error bounds for their fp32 evaluation.
+
+An independent yardstick for the C oracle (oracle/csrc/ocrs_oracle.c) and, through it, for the HIP kernels that
+match the oracle bit for bit.  Each function is written from the ONNX / PyTorch operator definition in numpy
+float64, not from the oracle's loops, and returns (y64, bound): the exact value and a per-element bound that any
+fp32 evaluation in the numeric spec of DESIGN.md §4 must stay within, |y - y64| <= bound.
+
+Bounds (u = 2^-24, gamma(n) = n u / (1 - n u)):
+  * contractions (conv, depthwise, ConvT, Linear, GRU projections): a chain acc = b; acc = fmaf(a_k, w_k, acc) of K
+    terms rounds K times, so |y - y64| <= gamma(K + 1) (|b| + sum_k |w_k x_k|), plus K * 2^-150 for products that
+    fall below the normal range (Higham, Accuracy and Stability of Numerical Algorithms, §3.1 and §2.1);
+  * average pool: the same bound with the 1 / (kh kw) scale (sum of K terms, the rounded reciprocal, the product);
+  * max pool, pad-and-concat, the to-sequence reshape: exact;
+  * exp, log, sigmoid, tanh: the spec polynomials' bounds below, measured over dense grids of their domains
+    (tests/test_numeric_spec.py asserts them) with at most 1.5x headroom;
+  * LogSoftmax and the GRU cell: propagated from the above (see those functions).
+"""
+import numpy as np
+
+U = 2.0 ** -24
+TINY = 2.0 ** -150     # half the smallest subnormal: the underflow error of one fmaf
+MIN_NORMAL = 2.0 ** -126
+
+# Error bounds of the spec transcendentals.  Measured maxima on 4 M-point grids:
+# exp 0.91 ulp on [-87, 88]; log 2.75 ulp on [1, 1024]; sigmoid 2.46 ulp on [-88, 88] where the value is normal;
+# tanh 1.34e-7 absolute on [-30, 30].
+EXP_ULP = 1.0
+LOG_ULP = 3.0
+SIGMOID_ULP = 3.0
+TANH_ABS = 1.5e-7
+
+
+def gamma(n):
+    n = np.asarray(n, np.float64)
+    return n * U / (1.0 - n * U)
+
+
+def ulp(v):
+    """fp32 unit in the last place of float64 values (the subnormal spacing below 2^-126)."""
+    a = np.abs(np.asarray(v, np.float64))
+    e = np.floor(np.log2(np.where(a > 0, a, 1.0)))
+    return 2.0 ** (np.maximum(e, -126) - 23)
+
+
+def _f64(a):
+    return np.asarray(a, np.float64)
+
+
+def _relu(y, relu):
+    return np.maximum(y, 0.0) if relu else y
+
+
+# ---------------------------------------------------------------- contractions
+def conv(x, w, b, relu=0):
+    """ONNX Conv, stride 1, 'same' zero padding (kh // 2, kw // 2) for odd kh, kw.  x NHWC, w [KH][KW][Cin][Cout]."""
+    x, w, b = _f64(x), _f64(w), _f64(b)
+    kh, kw, cin, cout = w.shape
+    n, h, wd, c = x.shape
+    assert c == cin and kh % 2 == 1 and kw % 2 == 1
+    xp = np.zeros((n, h + kh - 1, wd + kw - 1, cin))
+    xp[:, kh // 2:kh // 2 + h, kw // 2:kw // 2 + wd] = x
+    y = np.broadcast_to(b, (n, h, wd, cout)).copy()
+    mag = np.broadcast_to(np.abs(b), (n, h, wd, cout)).copy()
+    for ky in range(kh):
+        for kx in range(kw):
+            win = xp[:, ky:ky + h, kx:kx + wd]
+            y += win @ w[ky, kx]
+            mag += np.abs(win) @ np.abs(w[ky, kx])
+    k = kh * kw * cin
+    return _relu(y, relu), gamma(k + 1) * mag + k * TINY
+
+
+def dwconv3x3(x, w, b, relu=0):
+    """Depthwise (group = channel) 3x3 convolution, pad 1.  w [3][3][C]."""
+    x, w, b = _f64(x), _f64(w), _f64(b)
+    n, h, wd, c = x.shape
+    xp = np.zeros((n, h + 2, wd + 2, c))
+    xp[:, 1:h + 1, 1:wd + 1] = x
+    y = np.broadcast_to(b, x.shape).copy()
+    mag = np.broadcast_to(np.abs(b), x.shape).copy()
+    for ky in range(3):
+        for kx in range(3):
+            win = xp[:, ky:ky + h, kx:kx + wd]
+            y += win * w[ky, kx]
+            mag += np.abs(win * w[ky, kx])
+    return _relu(y, relu), gamma(10) * mag + 9 * TINY
+
+
+def convt2x2(x, w, b):
+    """ConvTranspose 2x2, stride 2 (no overlap: output (2i + dy, 2j + dx) = b + sum_ci x[i, j, ci] w[dy, dx, ci])."""
+    x, w, b = _f64(x), _f64(w), _f64(b)
+    n, h, wd, cin = x.shape
+    cout = w.shape[3]
+    y = np.empty((n, 2 * h, 2 * wd, cout))
+    mag = np.empty_like(y)
+    for dy in range(2):
+        for dx in range(2):
+            y[:, dy::2, dx::2] = x @ w[dy, dx] + b
+            mag[:, dy::2, dx::2] = np.abs(x) @ np.abs(w[dy, dx]) + np.abs(b)
+    return y, gamma(cin + 1) * mag + cin * TINY
+
+
+def linear(x, w, b, relu=0):
+    """y = x W + b over the last axis.  w [K][O]."""
+    x, w, b = _f64(x), _f64(w), _f64(b)
+    k = w.shape[0]
+    return _relu(x @ w + b, relu), gamma(k + 1) * (np.abs(x) @ np.abs(w) + np.abs(b)) + k * TINY
+
+
+# ---------------------------------------------------------------- pools, layout
+def _windows(x, kh, kw):
+    n, h, wd, c = x.shape
+    oh, ow = h // kh, wd // kw
+    return x[:, :oh * kh, :ow * kw].reshape(n, oh, kh, ow, kw, c)
+
+
+def maxpool(x, kh, kw):
+    """MaxPool, kernel = stride, floor (rows / columns the window does not reach are dropped).  Exact."""
+    y = _windows(_f64(x), kh, kw).max(axis=(2, 4))
+    return y, np.zeros_like(y)
+
+
+def avgpool(x, kh, kw):
+    """AveragePool, kernel = stride, floor.  Bound: gamma(K + 1) * mean |x| (sum, rounded 1/K, product)."""
+    win = _windows(_f64(x), kh, kw)
+    k = kh * kw
+    return win.mean(axis=(2, 4)), gamma(k + 1) * np.abs(win).mean(axis=(2, 4)) + TINY
+
+
+def padcat(skip, up):
+    """Zero-pad `up` to the spatial size of `skip` (before = d // 2, after = d - d // 2 per axis, as PyTorch's
+    F.pad(x, [dx // 2, dx - dx // 2, dy // 2, dy - dy // 2]) in the U-Net's Up block) and concatenate [skip, up]
+    along channels.  Exact."""
+    skip, up = _f64(skip), _f64(up)
+    n, sh, sw, _ = skip.shape
+    _, h, w, cx = up.shape
+    dy, dx = sh - h, sw - w
+    pad = np.zeros((n, sh, sw, cx))
+    pad[:, dy // 2:dy // 2 + h, dx // 2:dx // 2 + w] = up
+    y = np.concatenate([skip, pad], axis=3)
+    return y, np.zeros_like(y)
+
+
+def to_seq(x):
+    """[N, 1, W, C] (NHWC, height 1) -> [T = W, N, C].  Exact."""
+    x = _f64(x)
+    assert x.shape[1] == 1
+    y = np.ascontiguousarray(x[:, 0].transpose(1, 0, 2))
+    return y, np.zeros_like(y)
+
+
+# ---------------------------------------------------------------- elementwise transcendentals
+def _sigmoid64(x):
+    with np.errstate(over="ignore"):
+        return 1.0 / (1.0 + np.exp(-x))
+
+
+def sigmoid(x):
+    """1 / (1 + e^-x).  Bound: SIGMOID_ULP ulp where the value is normal, one smallest-normal below (the spec clamps
+    its exponent to [-87, 88], so sigmoid(x < -88) is ~6e-39, not the true subnormal or zero)."""
+    y = _sigmoid64(_f64(x))
+    return y, np.where(y >= MIN_NORMAL, SIGMOID_ULP * ulp(y), MIN_NORMAL)
+
+
+def tanh(x):
+    x = _f64(x)
+    return np.tanh(x), np.full(x.shape, TANH_ABS)
+
+
+# ---------------------------------------------------------------- LogSoftmax
+def log_softmax(x):
+    """LogSoftmax over the last axis, y_j = x_j - (m + log sum_c exp(x_c - m)).
+
+    Bound, per row, for the spec's evaluation order (m = max; s = sum_c exp(x_c - m) sequentially from 0;
+    lse = m + log(s); y_j = x_j - lse):
+      * the rounded difference x_c - m is off by at most u |x_c - m|, a relative error of that size (and a little
+        more) in its exponential; the exp polynomial adds EXP_ULP ulp (<= 2^-23 EXP_ULP relative); arguments below
+        -87 are clamped, so their term is up to 2^-125 instead of ~0;
+      * the sum of C terms rounds C - 1 times: gamma(C - 1) relative;
+      * so s = s64 (1 + e_s) + C 2^-125 with e_s bounded below, and log(s) = log(s64) + e_s' with s >= 1;
+      * the log polynomial adds LOG_ULP ulp of log(s); m + log(s) and x_j - lse round once each."""
+    x = _f64(x)
+    m = x.max(axis=-1, keepdims=True)
+    d = x - m
+    s64 = np.exp(d).sum(axis=-1, keepdims=True)
+    L = np.log(s64)
+    y = d - L
+    c = x.shape[-1]
+    e_arg = 1.01 * U * np.abs(d).max(axis=-1, keepdims=True)
+    e_s = gamma(c - 1) + e_arg + EXP_ULP * 2.0 ** -23 + c * 2.0 ** -125
+    e_s = 1.01 * e_s   # log(1 + e) <= e, and the products of these small terms
+    lse = m + L
+    bound = e_s + LOG_ULP * ulp(L) + U * np.abs(lse) + U * np.abs(y) + U * U * np.abs(x)
+    return y, np.broadcast_to(bound, y.shape).copy()
+
+
+# ---------------------------------------------------------------- GRU
+def gru_dir(x, wi, bi, wh, bh, h_prev_fp32, reverse=False):
+    """One direction of an ONNX / PyTorch GRU (gate order r, z, n; linear_before_reset = 1; h0 = 0), bounded one step
+    at a time: h_t is compared with the float64 cell applied to the fp32 h_{t-1} that the evaluation under test
+    produced itself (`h_prev_fp32` [T][N][H], its own output of this direction), so the bound does not grow with T.
+
+        r = sigmoid(x Wi_r + bi_r + h Wh_r + bh_r)
+        z = sigmoid(x Wi_z + bi_z + h Wh_z + bh_z)
+        n = tanh(x Wi_n + bi_n + r (h Wh_n + bh_n))
+        h' = (1 - z) n + z h
+
+    Bound: the two projections by the contraction bound; the gate pre-activations add one rounding; sigmoid is
+    1/4-Lipschitz and tanh 1-Lipschitz, plus their own bounds; the spec's h' = fmaf(z, h - n, n) rounds twice."""
+    x, wi, bi, wh, bh = _f64(x), _f64(wi), _f64(bi), _f64(wh), _f64(bh)
+    hs = _f64(h_prev_fp32)
+    T, N, I = x.shape
+    H = wh.shape[0]
+    y = np.empty((T, N, H))
+    bound = np.empty((T, N, H))
+    order = range(T - 1, -1, -1) if reverse else range(T)
+    h = np.zeros((N, H))
+    for t in order:
+        gx = x[t] @ wi + bi
+        ex = gamma(I + 1) * (np.abs(x[t]) @ np.abs(wi) + np.abs(bi)) + I * TINY
+        gh = h @ wh + bh
+        eh = gamma(H + 1) * (np.abs(h) @ np.abs(wh) + np.abs(bh)) + H * TINY
+        ar, az = gx[:, :H] + gh[:, :H], gx[:, H:2 * H] + gh[:, H:2 * H]
+        r, z = _sigmoid64(ar), _sigmoid64(az)
+        er = 0.25 * (ex[:, :H] + eh[:, :H] + U * np.abs(ar)) + SIGMOID_ULP * ulp(np.maximum(r, MIN_NORMAL))
+        ez = 0.25 * (ex[:, H:2 * H] + eh[:, H:2 * H] + U * np.abs(az)) + SIGMOID_ULP * ulp(np.maximum(z, MIN_NORMAL))
+        an = gx[:, 2 * H:] + r * gh[:, 2 * H:]
+        n = np.tanh(an)
+        en = ex[:, 2 * H:] + er * np.abs(gh[:, 2 * H:]) + (r + er) * eh[:, 2 * H:] + U * np.abs(an) + TANH_ABS
+        hn = (1 - z) * n + z * h
+        e = ez * np.abs(h - n) + (z + ez) * (en + U * np.abs(h - n)) + en + U * np.abs(hn)
+        y[t] = hn
+        bound[t] = 1.01 * e   # second-order products of the terms above
+        h = hs[t]             # the next step starts from the evaluation's own fp32 state
+    return y, bound
+
+
+def gru_bidir(x, ws, y_fp32):
+    """Bidirectional GRU -> [T][N][2H] (forward, then backward); ws = (wi, bi, wh, bh) x 2 as in the model file;
+    y_fp32 is the fp32 output under test, whose halves supply each direction's previous state."""
+    H = _f64(ws[2]).shape[0]
+    yf, bf = gru_dir(x, *ws[0:4], y_fp32[..., :H], reverse=False)
+    yb, bb = gru_dir(x, *ws[4:8], y_fp32[..., H:], reverse=True)
+    return np.concatenate([yf, yb], axis=-1), np.concatenate([bf, bb], axis=-1)
+
+
+# ---------------------------------------------------------------- CTC greedy
+def ctc_greedy(logp):
+    """Greedy CTC decoding: per step the arg max (the first of equal maxima), merge repeats, drop the blank (0).
+    Returns [(label, step)] for the first step of each emitted label."""
+    out, last = [], 0
+    for t, row in enumerate(np.asarray(logp)):
+        best = int(np.argmax(row))      # numpy returns the first maximum
+        if best != last and best != 0:
+            out.append((best, t))
+        last = best
+    return out
+
+
+def check(y, ref, what=""):
+    """Assert |y - y64| <= bound elementwise (both finite where the reference is)."""
+    y64, bound = ref
+    y = np.asarray(y, np.float64)
+    assert y.shape == y64.shape, (what, y.shape, y64.shape)
+    err = np.abs(y - y64)
+    bad = ~(err <= bound)
+    if bad.any():
+        i = np.unravel_index(np.argmax(np.where(bad, err / np.maximum(bound, 1e-300), 0)), y.shape)
+        raise AssertionError("%s: %d of %d elements outside the float64 bound; worst at %s: got %r, float64 %r, "
+                             "bound %.3g" % (what, bad.sum(), y.size, i, y[i], y64[i], bound[i]))

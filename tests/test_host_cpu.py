@@ -253,6 +253,37 @@ def test_malformed_model_files_are_rejected_at_load(lib):
     bad = bytearray(good); struct.pack_into("<I", bad, 8 + 4 + 4 + 32 + 8, 10 ** 6)  # header: output slot outside the table
     expect_io(bad)
 
+    # Graphs whose every weight tensor fits its op but whose channel counts or slot order do not: the kernels would index
+    # their input with lda = cin over a smaller buffer (or a slot nothing wrote).  Each must fail with IO, naming the op.
+    from ocrs_amd import modelfile as mf
+    rng = np.random.default_rng(0)
+
+    def conv(i, o, cin, cout, k=1):
+        return mf.Op(mf.OP_CONV, i, o, kh=k, kw=k, cin=cin, cout=cout,
+                     weights=(rng.standard_normal((k, k, cin, cout)), np.zeros(cout)))
+
+    def gru(i, o, cin, hid):
+        ws = []
+        for _ in range(2):
+            ws += [np.zeros((cin, 3 * hid)), np.zeros(3 * hid), np.zeros((hid, 3 * hid)), np.zeros(3 * hid)]
+        return mf.Op(mf.OP_GRU, i, o, cin=cin, hidden=hid, weights=ws)
+
+    def expect_io_naming(ops, n_slots, out_slot, what):
+        buf = mf.Graph(mf.KIND_DETECTION, [-1, 1, -1, -1], ops, n_slots, out_slot).to_bytes()
+        with pytest.raises(OcrsError) as e:
+            Model.load_bytes(buf)
+        assert e.value.status_name == "IO" and what in str(e.value), e.value
+
+    expect_io_naming([conv(0, 1, 1, 32), conv(1, 2, 64, 32, 3)], 3, 2, "op 1 (conv)")           # cin 64 after cout 32
+    expect_io_naming([conv(0, 1, 1, 8), conv(2, 3, 8, 8)], 4, 3, "op 1 (conv)")                  # reads slot 2 before any write
+    expect_io_naming([mf.Op(mf.OP_LINEAR, 0, 1, cin=16, cout=4, weights=(np.zeros((16, 4)), np.zeros(4)))], 2, 1,
+                     "op 0 (linear)")                                                              # cin 16 on the 1-channel input
+    expect_io_naming([conv(0, 1, 1, 8), mf.Op(mf.OP_DWCONV3, 1, 2, kh=3, kw=3, cin=16, cout=16,
+                                              weights=(np.zeros((3, 3, 16)), np.zeros(16)))], 3, 2, "op 1 (dwconv3)")
+    expect_io_naming([conv(0, 1, 1, 8), mf.Op(mf.OP_TOSEQ, 1, 2), gru(2, 3, 12, 4)], 4, 3, "op 2 (gru)")
+    expect_io_naming([conv(0, 1, 1, 8), gru(1, 2, 8, 4), conv(2, 3, 16, 4)], 4, 3, "op 2 (conv)")  # GRU emits 2 x hidden
+    expect_io_naming([conv(0, 1, 1, 8)], 3, 2, "output slot 2")                                   # output slot never written
+
 
 # ---------------------------------------------------------------- recognition.rs:512-514 (decode_beam)
 def _random_logp(rng, T, C, peak):
