@@ -466,7 +466,7 @@ static double rec_pixel_budget() {
 void ocrs_engine::recognize_now(const ocrs_page* const* pages, size_t n_pages,
                                 const std::vector<std::vector<std::vector<RotatedRect>>>& lines_per_page,
                                 std::vector<std::vector<CtcStep>>* steps_out, std::vector<RecLine>* rec_lines_out,
-                                std::vector<uint32_t>* ctc_len_out) const {
+                                std::vector<uint32_t>* ctc_len_out, std::vector<std::vector<float>>* logp_out) const {
     if (!recognition) fail(OCRS_ERR_MODEL_NOT_LOADED, "Recognition model not loaded");
     const uint32_t rec_h = rec_input_height();
     std::vector<RecLine> lines;
@@ -477,12 +477,13 @@ void ocrs_engine::recognize_now(const ocrs_page* const* pages, size_t n_pages,
     double total = 0.0;
     for (const RecLine& l : lines) total += (double)rec_h * l.group_width;
     if (total <= budget) {
-        recognize_lines(pages, n_pages, lines, steps_out, ctc_len_out);
+        recognize_lines(pages, n_pages, lines, steps_out, ctc_len_out, logp_out);
         *rec_lines_out = std::move(lines);
         return;
     }
     steps_out->assign(L, {});
     ctc_len_out->assign(L, 0);
+    if (logp_out) logp_out->assign(L, {});
     for (size_t b = 0; b < L;) {
         size_t e = b;
         double px = 0.0;
@@ -490,10 +491,12 @@ void ocrs_engine::recognize_now(const ocrs_page* const* pages, size_t n_pages,
         std::vector<RecLine> part(lines.begin() + b, lines.begin() + e);
         std::vector<std::vector<CtcStep>> st;
         std::vector<uint32_t> cl;
-        recognize_lines(pages, n_pages, part, &st, &cl);
+        std::vector<std::vector<float>> lp;
+        recognize_lines(pages, n_pages, part, &st, &cl, logp_out ? &lp : nullptr);
         for (size_t i = b; i < e; i++) {
             (*steps_out)[i] = std::move(st[i - b]);
             (*ctc_len_out)[i] = cl[i - b];
+            if (logp_out) (*logp_out)[i] = std::move(lp[i - b]);
         }
         b = e;
     }
@@ -504,11 +507,10 @@ void ocrs_engine::recognize_logits(const ocrs_page* page, const std::vector<std:
                                    std::vector<std::vector<float>>* logp, int* classes) const {
     if (!recognition) fail(OCRS_ERR_MODEL_NOT_LOADED, "Recognition model not loaded");
     if (recognition->is_callback()) fail(OCRS_ERR_INVALID_ARGUMENT, "recognize_logits needs a model of the fixed-graph executor");
-    std::vector<RecLine> lines;
-    for (const auto& words : lines_in) lines.push_back(make_rec_line(words, 0, lines.size()));
     std::vector<std::vector<CtcStep>> steps;
+    std::vector<RecLine> lines;
     std::vector<uint32_t> ctc_len;
-    recognize_lines(&page, 1, lines, &steps, &ctc_len, logp);
+    recognize_now(&page, 1, {lines_in}, &steps, &lines, &ctc_len, logp);
     *classes = (int)alphabet.size() + 1;
 }
 

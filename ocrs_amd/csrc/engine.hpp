@@ -106,7 +106,7 @@ struct ocrs_engine {
     void recognize_now(const ocrs_page* const* pages, size_t n_pages,
                        const std::vector<std::vector<std::vector<ocrs::geom::RotatedRect>>>& lines_per_page,
                        std::vector<std::vector<ocrs::CtcStep>>* steps, std::vector<ocrs::RecLine>* rec_lines,
-                       std::vector<uint32_t>* ctc_input_len) const;
+                       std::vector<uint32_t>* ctc_input_len, std::vector<std::vector<float>>* logp = nullptr) const;
     void init_coalescers();
     mutable std::unique_ptr<ocrs::Coalescer<ocrs::DetRequest>> det_queue;
     mutable std::unique_ptr<ocrs::Coalescer<ocrs::RecRequest>> rec_queue;
@@ -115,7 +115,8 @@ struct ocrs_engine {
     void recognize_lines(const ocrs_page* const* pages, size_t n_pages, const std::vector<ocrs::RecLine>& lines,
                          std::vector<std::vector<ocrs::CtcStep>>* steps, std::vector<uint32_t>* ctc_input_len,
                          std::vector<std::vector<float>>* logp = nullptr) const;
-    // the recognition model's output for the lines of one page, one request, no coalescing (parity / tolerance checks)
+    // the recognition model's output for the lines of one page, no coalescing (parity / tolerance checks); split into
+    // sub-requests within the activation budget as `recognize` is
     void recognize_logits(const ocrs_page* page, const std::vector<std::vector<ocrs::geom::RotatedRect>>& lines,
                           std::vector<std::vector<float>>* logp, int* classes) const;
 

@@ -268,3 +268,57 @@ def check(y, ref, what=""):
         i = np.unravel_index(np.argmax(np.where(bad, err / np.maximum(bound, 1e-300), 0)), y.shape)
         raise AssertionError("%s: %d of %d elements outside the float64 bound; worst at %s: got %r, float64 %r, "
                              "bound %.3g" % (what, bad.sum(), y.size, i, y[i], y64[i], bound[i]))
+
+
+# ---------------------------------------------------------------- whole graphs
+def _op_ref(op, slots):
+    """The float64 reference of one op of an OracleGraph, applied to the oracle's own fp32 input slot(s)."""
+    t, x, W = op["type"], slots[op["in0"]], op["w"]
+    kh, kw, cin, cout, hid = op["kh"], op["kw"], op["cin"], op["cout"], op["hidden"]
+    if t == 0:
+        return conv(x, W[0].reshape(kh, kw, cin, cout), W[1], op["relu"])
+    if t == 1:
+        return dwconv3x3(x, W[0].reshape(3, 3, cin), W[1], op["relu"])
+    if t == 2:
+        return maxpool(x, kh, kw)
+    if t == 3:
+        return avgpool(x, kh, kw)
+    if t == 4:
+        return convt2x2(x, W[0].reshape(2, 2, cin, cout), W[1])
+    if t == 5:
+        return padcat(x, slots[op["in1"]])
+    if t == 6:
+        return sigmoid(x)
+    if t == 7:
+        return to_seq(x)
+    if t == 8:
+        ws = []
+        for d in range(2):
+            wi, bi, wh, bh = W[4 * d:4 * d + 4]
+            ws += [wi.reshape(cin, 3 * hid), bi, wh.reshape(hid, 3 * hid), bh]
+        return gru_bidir(x, ws, slots[op["out"]])
+    if t == 9:
+        return linear(x, W[0].reshape(cin, cout), W[1], op["relu"])
+    if t == 10:
+        return log_softmax(x)
+    raise AssertionError("op type %d has no float64 definition" % t)
+
+
+def check_graph(buf, x, what=""):
+    """Run a whole model file through the oracle (OracleGraph.run_exact, every slot kept) and check each op's fp32
+    output slot, in graph order, against the float64 op applied to the oracle's fp32 input slot(s).  Each op is
+    bounded on its own inputs, so the bound does not grow with depth; an op without a float64 definition fails.
+    Returns the per-op list of (op name, worst |y - y64| / bound)."""
+    from oracle.nn import OracleGraph
+    g = OracleGraph(buf)
+    _, slots = g.run_exact(x, return_slots=True)
+    names = ["conv", "dwconv3", "maxpool", "avgpool", "convt2", "padcat", "sigmoid", "toseq", "gru", "linear",
+             "logsoftmax"]
+    worst = []
+    for i, op in enumerate(g.ops):
+        ref = _op_ref(op, slots)
+        name = names[op["type"]]
+        check(slots[op["out"]], ref, "%s: op %d (%s)" % (what, i, name))
+        err = np.abs(np.asarray(slots[op["out"]], np.float64) - ref[0])
+        worst.append((name, float(np.max(np.where(ref[1] > 0, err / np.maximum(ref[1], 1e-300), 0), initial=0))))
+    return worst

@@ -370,6 +370,9 @@ def test_recognition_other_input_heights_and_ragged_widths(in_h, chans):
             assert [c.rect for c in a.chars()] == [c.rect.tlbr() for c in b.chars]
             n_chars += len(b.chars)
     assert n_chars > 20
+    # the log-probs themselves, not only their greedy decode
+    M.assert_logits_equal(gpu.recognize_logits(inp, [rects_of(l) for l in lines]),
+                          M.oracle_line_logits(rbuf, ora, oin, lines), "in_h %d" % in_h)
 
 
 def test_full_pipeline_tokens_boxes_and_text_identical():
@@ -586,6 +589,8 @@ def test_recognition_long_short_split_path():
             assert [c.rect for c in a.chars()] == [c.rect.tlbr() for c in b.chars]
             n_chars += len(b.chars)
     assert n_chars > 100
+    M.assert_logits_equal(gpu.recognize_logits(inp, [rects_of(l) for l in lines]),
+                          M.oracle_line_logits(rbuf, ora, oin, lines), "long/short")
 
 
 def test_bench_call_sequence_batch_apis_match_single_page_path_and_oracle():

@@ -358,6 +358,7 @@ def test_recurrence_paths_by_hidden_size_and_mode(hidden):
     lines = _some_lines()
     exp = ora.recognize_text(oin, lines)
     assert sum(1 for t in exp if t is not None) >= 5
+    exp_lp = M.oracle_line_logits(rbuf, ora, oin, lines)
 
     def run(mode):
         gpu.set_option("gru_mode", mode)
@@ -370,6 +371,7 @@ def test_recurrence_paths_by_hidden_size_and_mode(hidden):
             assert (a is None) == (b is None)
             if a is not None:
                 assert str(a) == str(b) and [c.rect for c in a.chars()] == [c.rect.tlbr() for c in b.chars]
+        M.assert_logits_equal(gpu.recognize_logits(inp, [rects_of(l) for l in lines]), exp_lp, "gru_mode %d" % mode)
         return ks["gemm_gru_hidden_mfma"]["launches"], ks["gru_gates"]["launches"]
 
     try:
@@ -402,6 +404,7 @@ def test_narrow_lines_sharing_conv_patches():
                                       (np.float32(0.0), np.float32(1.0)), np.float32(ww), np.float32(20.0))])
     exp = ora.recognize_text(oin, lines)
     assert sum(1 for t in exp if t is not None and len(t.chars)) >= 10
+    exp_lp = M.oracle_line_logits(rbuf, ora, oin, lines)
     try:
         # conv12_fuse: conv1 + pool + conv2 + pool as one kernel (its patches leave an empty column between images)
         for flat, fuse12 in ((1, 1), (0, 1), (1, 0), (0, 0)):
@@ -412,6 +415,8 @@ def test_narrow_lines_sharing_conv_patches():
                 assert (a is None) == (b is None)
                 if a is not None:
                     assert str(a) == str(b) and [c.rect for c in a.chars()] == [c.rect.tlbr() for c in b.chars]
+            M.assert_logits_equal(gpu.recognize_logits(inp, [rects_of(l) for l in lines]), exp_lp,
+                                  "conv_flat %d conv12_fuse %d" % (flat, fuse12))
     finally:
         gpu.set_option("conv_flat", 1)
         gpu.set_option("conv12_fuse", 1)

@@ -10,8 +10,11 @@ import numpy as np
 import pytest
 
 import f64_ref as R
+import models_util as M
 from ocrs_amd import modelfile as mf
+from ocrs_amd import synth
 from oracle import clib
+from oracle import pipeline as OP
 from oracle.nn import OracleGraph
 
 RNG_SEED = 20261015
@@ -261,3 +264,49 @@ def test_oracle_linear_against_float64():
             lin = mf.Op(mf.OP_LINEAR, 1, 2, relu=relu, cin=cin, cout=cout, weights=(w, b))
             s = _run([_lift(rng, cin, KINDS[j]), lin], 3, 2, _image(rng, 2, 3, 5, KINDS[j]))
             R.check(s[2], R.linear(s[1], w, b, relu), "linear %d->%d relu %d" % (cin, cout, relu))
+
+
+# ---------------------------------------------------------------- whole models, op by op
+def _rec_input(in_h, width, seed):
+    """Two synthetic line crops of height in_h in a row of `width` padded with BLACK_VALUE (-0.5), the second crop
+    repeated to the right so that long rows carry text beyond 256 px."""
+    crops = synth.synthetic_line_crops(seed, n=2)[:, ::64 // in_h, ::64 // in_h]
+    x = np.full((2, 1, in_h, width), -0.5, np.float32)
+    cw = crops.shape[2]
+    for i in range(2):
+        for x0 in range(0, width if i else min(width, cw), cw):
+            w = min(cw, width - x0)
+            x[i, 0, :, x0:x0 + w] = crops[i, :, :w]
+    return x
+
+
+@pytest.mark.parametrize("width", [50, 300, 2400])
+def test_production_recognition_model_within_float64_bounds(width):
+    """The production CRNN (H 64, K = 1152 convs, hidden 256, 97 classes) at T = 12, 75 and 600: every op of the
+    oracle's run within its float64 bound, on its own fp32 inputs."""
+    R.check_graph(M.recognition_model_bytes(), _rec_input(64, width, 3), "recognition W %d" % width)
+
+
+@pytest.mark.parametrize("hidden,in_h,chans", [(32, 64, (32, 64, 64, 64, 64, 64)), (64, 64, (32, 64, 64, 64, 64, 64)),
+                                               (128, 64, (32, 64, 64, 64, 64, 64)),
+                                               (64, 32, (32, 64, 64, 64, 64, 64))])
+def test_small_recognition_models_within_float64_bounds(hidden, in_h, chans):
+    buf = M.small_recognition_bytes(hidden, in_h, chans=chans)
+    R.check_graph(buf, _rec_input(in_h, 450, 4), "recognition hidden %d H %d" % (hidden, in_h))
+
+
+@pytest.mark.parametrize("in_hw,depths", [((800, 600), (8, 16, 32, 32, 64, 128, 256)), ((96, 64), (8, 16, 32, 32))])
+def test_detection_model_within_float64_bounds(in_hw, depths):
+    """The U-Net (depthwise DoubleConvs, pools, ConvT, pad-and-concat with odd sizes, sigmoid) on a synthetic page."""
+    buf = M.detection_model_bytes(in_hw, depths)
+    px = synth.synthetic_page(6, in_hw[0], in_hw[1], lines=max(2, in_hw[0] // 40))
+    page = OP.prepare_image(OP.ImageSource.from_tensor(px, "hwc"))
+    R.check_graph(buf, page[None], "detection %dx%d" % in_hw)
+
+
+def test_graph_walk_fails_on_an_op_without_a_definition():
+    """An op type the float64 reference does not define fails the walk instead of being skipped."""
+    class _Op(dict):
+        pass
+    with pytest.raises(AssertionError, match="no float64 definition"):
+        R._op_ref(_Op(type=11, in0=0, out=1, w=[], kh=0, kw=0, cin=0, cout=0, hidden=0, relu=0), {0: np.zeros(1)})
