@@ -8,7 +8,7 @@ One "step" = one pass of the full pipeline over one batch of synthetic pages han
 u8 HWC buffers, where an image decoder would write them — the reference's prepare_input takes host pixels, lib.rs:183-187):
 upload + prepare_input -> detect_words (CNN @ 800x600, threshold, components -> rects) -> find_text_lines (host) ->
 recognize_text (line crops, CRNN, greedy CTC) -> TextLines on the host.  The uploads are inside the timed region.
-`--resident` times the round 1-4 form instead (pages already in HBM); the default run reports it as an extra.
+`--resident` times the round 1-4 form instead (pages already in HBM); `--full` reports it as an extra.
 
 N > 1, two shapes (pages are independent units: no collective on the compute path in either; weak scaling —
 `--pages` pages per step per GPU):
@@ -28,15 +28,24 @@ processed in requests of `--pages` pages.
 `--dump-outputs DIR` writes what the last timed step returned to its caller as DIR/<name>.npy (float32 / float64, at most
 64 MB): the inputs are seeded, so two builds run with the same arguments can be compared output for output.
 
+A plain run does what the headline needs: it sets up, warms up, times the K steps, writes `--dump-outputs` and prints the
+result line with what the timed region itself measured (stage and live per-kernel times, `roofline` / `rooflines`, request
+latency).  `--full` adds everything that takes runs of its own: the untimed calibration step behind the rooflines' `alone`
+figures and `pipeline`, the same K steps from an empty pipeline (`value_incl_fill_drain`), the extra legs (`extras`,
+`roofline_detection`, the other page hand-overs, relaxed / reduced numerics) and `cpu_baseline`.
+
 Prints ONE JSON line (rank 0).  Real weights are not obtainable offline, so
 the models are the SURVEY.md §2.4 architectures with seeded synthetic weights.
 """
 import argparse
+import atexit
 import ctypes as C
 import json
 import os
+import shutil
 import socket
 import sys
+import tempfile
 import time
 
 ROOT = os.path.dirname(os.path.abspath(__file__))
@@ -68,18 +77,21 @@ def parse(argv=None):
                     help="pages already resident in HBM when the timed region starts (rounds 1-4); default: every page is "
                          "uploaded from page-locked host memory inside the timed region")
     ap.add_argument("--numerics", choices=("exact", "relaxed", "reduced"), default="exact",
-                    help="ocrs_engine_params.numerics of the timed engine (the headline is exact; the default run reports "
-                         "the other two as extras)")
+                    help="ocrs_engine_params.numerics of the timed engine (the headline is exact; --full reports the other "
+                         "two as extras)")
     ap.add_argument("--coalesce", type=int, default=0,
                     help="ocrs_engine_params.coalesce: merged batches of one-page calls in flight per stage (0 = default 2, -1 = off)")
     ap.add_argument("--no-steady-state", action="store_true",
                     help="time the K steps from an EMPTY pipeline to an empty pipeline (the rounds 1-5 form) instead of in steady state")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also run what takes runs of its own: the kernel-timing calibration step, the "
+                         "fill/drain re-run of the K steps, the extra legs and the CPU baseline (default: the headline only)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--cpu-pages", type=int, default=2, help="pages in the bounded CPU-baseline sample")
     ap.add_argument("--no-kernel-timing", action="store_true")
     ap.add_argument("--inflight", type=int, default=5,
                     help="full steps kept in flight on separate host threads / HIP streams (default 5 = the knee of the "
-                         "throughput / latency / memory curve, tools/inflight_sweep.sh: 6 and 7 add 0.3 % and 1 % pages/s for "
+                         "throughput / latency / memory curve, tools/inflight_sweep.sh: 6 and 7 add 0.3 %% and 1 %% pages/s for "
                          "+50 / +110 ms of request latency and +6 GB each; 1 = the "
                          "2-stage pipeline or, with --no-pipeline, strictly sequential steps)")
     ap.add_argument("--no-pipeline", action="store_true",
@@ -87,7 +99,7 @@ def parse(argv=None):
                          "pipeline across steps: detect+layout of step i+1 overlap recognition of step i)")
     ap.add_argument("--profile-hint", action="store_true", help="print per-stage and per-kernel tables to stderr")
     ap.add_argument("--no-extras", action="store_true",
-                    help="skip the detection-only (configs[1]), recognition-only (configs[2]) and host-pixels legs")
+                    help="with --full: skip the detection-only (configs[1]), recognition-only (configs[2]) and host-pixels legs")
     ap.add_argument("--spawn-ranks", action="store_true",
                     help="N > 1 launched without a launcher: re-execute under torch.distributed.run with N ranks (one "
                          "process per GPU) instead of driving the N GPUs from this process through the engine group")
@@ -268,6 +280,11 @@ def main():
     maybe_spawn(args, argv)
     if args.dist_selftest:
         return selftest_main(args)
+    # ocrs_amd.models caches the synthetic model files under $OCRS_AMD_CACHE: point it at a directory of this run's own, so
+    # that every run makes them itself and none reads what an earlier run (or another user) left behind
+    cache_dir = tempfile.mkdtemp(prefix="ocrs_bench_models_")
+    os.environ["OCRS_AMD_CACHE"] = cache_dir
+    atexit.register(shutil.rmtree, cache_dir, True)
     per_rank_cores = cap_host_threads(int(os.environ.get("LOCAL_WORLD_SIZE", os.environ.get("WORLD_SIZE", "1"))))
     import numpy as np
     import torch
@@ -474,16 +491,17 @@ def main():
         settle_steps += max(args.inflight, 1)
     # Per-launch HIP events (on the launching stream) in the timed region for the three MFMA classes only — the conv
     # stack, the GRU input projections and the GRU recurrence: a dozen launches per step, so the live roofline figures
-    # do not slow the run.  One untimed calibration step times EVERY class (whole-pipeline FLOP count, shares).
-    # --profile-hint keeps all classes on.
+    # do not slow the run.  With --full, one untimed calibration step times EVERY class (whole-pipeline FLOP count, shares,
+    # the `alone` figures).  --profile-hint keeps all classes on.
     cal = {}
     timed_classes = ["gemm_conv3x3_mfma", "gemm_gru_input_mfma", "gemm_gru_hidden_mfma"]
     if not args.no_kernel_timing:
-        engine.enable_timing(2)
-        engine.set_kernel_timing_classes(None)
-        engine.stage_times(reset=True)
-        step(0)
-        cal = {k: v for k, v in engine.kernel_stats(reset=True).items() if v["launches"] > 0}
+        if args.full:
+            engine.enable_timing(2)
+            engine.set_kernel_timing_classes(None)
+            engine.stage_times(reset=True)
+            step(0)
+            cal = {k: v for k, v in engine.kernel_stats(reset=True).items() if v["launches"] > 0}
         engine.set_kernel_timing_classes(None if args.profile_hint else timed_classes)
     engine.enable_timing(0 if args.no_kernel_timing else 2)
     engine.stage_times(reset=True)
@@ -548,7 +566,7 @@ def main():
     engine.enable_timing(0)
     # the same K steps from an empty pipeline to an empty pipeline (fill and drain inside the clock): the form of rounds 1-5
     elapsed_fd = None
-    if steady:
+    if steady and args.full:
         sync_all()
         t0 = time.perf_counter()
         run_steps(args.steps, latency=[])
@@ -626,7 +644,7 @@ def main():
                         "stream of requests (%d in flight) between two barrier + device-synchronize points; the window runs from the completion "
                         "of the last priming step to the completion of the last timed step, so exactly %d steps complete inside it and each "
                         "does all of its work, uploads included; its duration = steps x the least-squares slope through its completion times "
-                        "(completions come in bursts: value_first_to_last_completion is the two-point figure); value_incl_fill_drain = the same %d steps from an empty pipeline to an empty "
+                        "(completions come in bursts: value_first_to_last_completion is the two-point figure); value_incl_fill_drain (--full) = the same %d steps from an empty pipeline to an empty "
                         "pipeline (the rounds 1-5 form)" % (prime, args.steps, trail, max(args.inflight, 1), args.steps, args.steps))
                        if steady else "whole region between two barrier + device-synchronize points (pipeline fill and drain inside the clock)"),
             "pages_per_step_per_gpu": B,
@@ -734,8 +752,8 @@ def main():
             for k, v in stages.items():
                 print("stage %-18s %8.3f ms/step" % (k, v[0] / steps_under_timers), file=sys.stderr)
 
-    # ---- extra legs named by BASELINE.json (rank 0, N=1 only; not part of `value`)
-    if world == 1 and not group_mode and not args.no_extras:
+    # ---- extra legs named by BASELINE.json (--full, rank 0, N=1 only; not part of `value`)
+    if args.full and world == 1 and not group_mode and not args.no_extras:
         result["extras"] = extra_legs(engine, dptrs, host_pages, H, W, synth, np, DimOrder, sync_all, args)
         if "roofline_detection" in result["extras"]:
             result["roofline_detection"] = result["extras"].pop("roofline_detection")
@@ -784,8 +802,8 @@ def main():
                 "engines (box flips = word rects that differ, token flips = lines whose greedy CTC (label, position) sequence differs, "
                 "max |d log-prob| over the recognition model's outputs); the headline is exact" % (k2, BG, args.inflight))
 
-    # ---- CPU baseline: the oracle on the host cores, bounded sample (rank 0, N=1 only)
-    if world == 1 and not group_mode and not args.no_cpu_baseline and not args.stream_pages:
+    # ---- CPU baseline: the oracle on the host cores, bounded sample (--full, rank 0, N=1 only)
+    if args.full and world == 1 and not group_mode and not args.no_cpu_baseline and not args.stream_pages:
         words, (rects, loffs, poffs), (chars, coffs) = last
         gpu_text = []
         for i in range(min(args.cpu_pages, B)):

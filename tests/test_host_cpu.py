@@ -213,6 +213,17 @@ def test_committed_bench_line_keeps_the_driver_contract():
     assert abs(d["value"] - d["config"]["pages_per_step_per_gpu"] * 1000.0 / d["ms_per_step"]) / d["value"] < 1e-3
 
 
+def test_bench_help_lists_full():
+    """`bench.py --help` prints (every help string formats) and offers --full, the switch behind every leg beyond the
+    headline; a plain run leaves it off."""
+    import subprocess
+    import sys
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--help"], capture_output=True, text=True, timeout=120,
+                       cwd=ROOT)
+    assert r.returncode == 0, r.stderr[-2000:]
+    assert "--full" in r.stdout and "--no-cpu-baseline" in r.stdout
+
+
 def test_no_gpu_means_a_loud_error_not_a_cpu_fallback(lib):
     """The product has no CPU path: without a HIP device, loading a model (the first thing that needs HBM) must
     raise, not quietly compute somewhere else."""

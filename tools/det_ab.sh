@@ -3,7 +3,7 @@
 #   tools/det_ab.sh <ENV_NAME> <mode> <value> [<value> ...]      e.g.  tools/det_ab.sh OCRS_DET_ROWS loop 1 0 1 0
 # modes:  loop  = detection-only loop (tools/det_bench.py: 8 pages per request, one request at a time)
 #         prof  = the same under rocprofv3 --kernel-trace --stats (per-kernel times into gpurun_out/det_ab/<value>.txt)
-#         bench = the default bench (16-page requests, 5 in flight) with extras
+#         bench = bench.py --full (16-page requests, 5 in flight) with extras
 # ENV_NAME: OCRS_DET_STREAM (0 | 1 | 8 | 14 | 32), OCRS_DET_ROWS (0 | 1 | 8 | 14 | 20 | 32), OCRS_CCL_QUAD (0 | 1), ...
 export TMPDIR=/tmp
 NAME=$1; MODE=$2; shift 2
@@ -15,7 +15,7 @@ for v in "$@"; do
     (cd /tmp && env $NAME=$v timeout 300 rocprofv3 --kernel-trace --stats -d $OLDPWD/$O/p$v -o det -- python $OLDPWD/tools/det_bench.py 20 > $OLDPWD/$O/p$v.log 2>&1)
     python tools/rocprof_summary.py $O/p$v/det_results.db $O/$v.txt > /dev/null; echo "== $NAME=$v"; head -16 $O/$v.txt | cut -c1-150;;
   bench)
-    env $NAME=$v timeout 300 python bench.py --no-cpu-baseline > $O/bench_$v.json 2> $O/err.txt
+    env $NAME=$v timeout 300 python bench.py --full --no-cpu-baseline > $O/bench_$v.json 2> $O/err.txt
     python - $O/bench_$v.json "$NAME=$v" <<'PY'
 import json,sys
 d=json.loads([l for l in open(sys.argv[1]).read().splitlines() if l.startswith("{")][-1])

@@ -56,7 +56,7 @@ serial16)
 det)
   say "== detection stack: fused LDS-tiled DoubleConv blocks (1) vs unfused kernels (0); extras legs only"
   for f in 1 0; do
-    OCRS_DET_FUSE=$f timeout 400 python bench.py --steps 6 --warmup 3 --settle-s 0 --no-cpu-baseline > $OUT/bench_det$f.json 2> $OUT/bench_det$f.err; jsum $OUT/bench_det$f.json "det_fuse=$f"
+    OCRS_DET_FUSE=$f timeout 400 python bench.py --full --steps 6 --warmup 3 --settle-s 0 --no-cpu-baseline > $OUT/bench_det$f.json 2> $OUT/bench_det$f.err; jsum $OUT/bench_det$f.json "det_fuse=$f"
   done;;
 detprof)
   say "== rocprofv3 kernel trace of the detection-only loop (tools/det_bench.py), fused vs unfused"
@@ -67,7 +67,7 @@ detprof)
   done
   find $OUT/detprof -size +30M -delete;;
 full)
-  say "== default bench with every leg (extras, cpu baseline)"; timeout 900 python bench.py > $OUT/bench_full.json 2> $OUT/bench_full.err; say "rc=$?"; jsum $OUT/bench_full.json "default";;
+  say "== bench.py --full: every leg (extras, cpu baseline)"; timeout 900 python bench.py --full > $OUT/bench_full.json 2> $OUT/bench_full.err; say "rc=$?"; jsum $OUT/bench_full.json "default";;
 multi)
   say "== 2 ranks on this one GPU (gloo, ranks share the device): exercises the self-spawn + gather path"
   OCRS_DIST_BACKEND=gloo timeout 600 python bench.py --gpus 2 --spawn-ranks --steps 8 --warmup 4 --pages 8 --settle-s 0 --no-cpu-baseline --no-extras > $OUT/bench_2rank.json 2> $OUT/bench_2rank.err; say "rc=$?"; jsum $OUT/bench_2rank.json "2 ranks/1 GPU"; tail -3 $OUT/bench_2rank.err | cut -c1-300 | tee -a $S
