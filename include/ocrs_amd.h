@@ -83,6 +83,10 @@ OCRS_API ocrs_status ocrs_get_device(int* device);
  * Outputs are malloc'ed (ocrs_buffer_free). */
 OCRS_API ocrs_status ocrs_ctc_beam_search(const float* logp, int t, int c, uint32_t width, int impl, uint32_t** labels,
                                           uint32_t** positions, size_t* n);
+/* The same with confidence: *score = the best beam's float64 lse(pb, pnb) (0 if t = 0), *step_logp[i] = logp[pos_i][label_i]
+ * (n entries, malloc'ed). */
+OCRS_API ocrs_status ocrs_ctc_beam_search_scored(const float* logp, int t, int c, uint32_t width, int impl, uint32_t** labels,
+                                                 uint32_t** positions, size_t* n, double* score, float** step_logp);
 
 /* Test hook (host only, no GPU work): how the persistent GRU kernel would deal the 16-line row tiles of a request
  * to its waves.  lengths_desc = sequence lengths of the lines, descending (tile k = lines 16k .. 16k+15).
@@ -358,6 +362,23 @@ OCRS_API ocrs_status ocrs_engine_recognize_text_batch(const ocrs_engine* e, cons
                                              const size_t* page_line_offsets, const float* line_rects,
                                              const size_t* line_offsets, size_t n_lines,
                                              ocrs_text_char** chars, size_t** char_offsets);
+
+/* Recognition confidence (DESIGN.md "Recognition confidence"): the two calls above, plus
+ *   char_logp:  one float per returned ocrs_text_char, same indexing: the log-prob of the CTC step the char came from
+ *               (the masked log-prob the decoder saw; in greedy decoding the row's maximum);
+ *   line_score: n_lines doubles: greedy, the log-probability of the greedy alignment path (sum over all T steps of
+ *               the line, padding included, of the masked row maximum, in ascending t); beam search, the best
+ *               beam's total.  A line without text (empty char range) has a score too; a line of no steps has 0.
+ * Both malloc'ed (ocrs_buffer_free).  Scores say how sure the model was, not whether it is right: calibrate on real
+ * models before thresholding. */
+OCRS_API ocrs_status ocrs_engine_recognize_text_scored(const ocrs_engine* e, const ocrs_page* page, const float* line_rects,
+                                                       const size_t* line_offsets, size_t n_lines, ocrs_text_char** chars,
+                                                       size_t** char_offsets, float** char_logp, double** line_score);
+OCRS_API ocrs_status ocrs_engine_recognize_text_batch_scored(const ocrs_engine* e, const ocrs_page* const* pages,
+                                                             size_t n_pages, const size_t* page_line_offsets,
+                                                             const float* line_rects, const size_t* line_offsets,
+                                                             size_t n_lines, ocrs_text_char** chars, size_t** char_offsets,
+                                                             float** char_logp, double** line_score);
 
 /* Raw CTC output for the same lines (labels and time steps of
  * CtcHypothesis::steps(), recognition.rs:257-289), for token-level parity. */

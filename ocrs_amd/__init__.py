@@ -7,6 +7,7 @@ Python mirror (ctypes) of the reference's public surface (ocrs/src/lib.rs:29-31,
 libocrs_amd.so (HIP, gfx950); this module only marshals arrays.
 """
 import ctypes as C
+import math
 
 import numpy as np
 
@@ -224,11 +225,17 @@ class OcrInput:
 
 
 class TextChar:  # text_items.rs:48-54
-    __slots__ = ("char", "rect")
+    __slots__ = ("char", "rect", "logp")
 
-    def __init__(self, char, rect):
+    def __init__(self, char, rect, logp=None):
         self.char = char
         self.rect = rect  # (top, left, bottom, right)
+        self.logp = logp  # log-prob of the CTC step the char came from (float32), None when unscored
+
+    @property
+    def confidence(self):
+        """exp(logp), or None when unscored."""
+        return None if self.logp is None else math.exp(float(self.logp))
 
 
 class _TextItem:
@@ -237,6 +244,13 @@ class _TextItem:
 
     def chars(self):
         return self._chars
+
+    @property
+    def confidence(self):
+        """exp of the mean of the chars' logp, in float64 (a line's mean includes its spaces); None when unscored."""
+        if not self._chars or any(c.logp is None for c in self._chars):
+            return None
+        return math.exp(math.fsum(float(c.logp) for c in self._chars) / len(self._chars))
 
     def bounding_rect(self):
         a = np.array([c.rect for c in self._chars])
@@ -266,9 +280,10 @@ class TextWord(_TextItem):  # text_items.rs:92-107
 
 
 class TextLine(_TextItem):  # text_items.rs:61-82
-    def __init__(self, chars):
+    def __init__(self, chars, score=None):
         assert chars, "Text lines must not be empty"
         super().__init__(chars)
+        self.score = score  # float64 line score (include/ocrs_amd.h), None when unscored
 
     def words(self):
         out, cur = [], []
@@ -458,9 +473,11 @@ class OcrEngine:
             lib().ocrs_buffer_free(p)
         return rects, loffs, poffs
 
-    def recognize_text_batch_raw(self, inputs, rects, line_offsets, page_line_offsets):
+    def recognize_text_batch_raw(self, inputs, rects, line_offsets, page_line_offsets, scores=False):
         """Packed form of recognize_text_batch: returns (chars, char_offsets) where chars is a
-        structured array (ch, top, left, bottom, right) and line i owns chars[char_offsets[i]:char_offsets[i+1]]."""
+        structured array (ch, top, left, bottom, right) and line i owns chars[char_offsets[i]:char_offsets[i+1]].
+        scores=True: returns (chars, char_offsets, char_logp float32 [len(chars)], line_score float64 [lines]), every
+        line scored, those without text included."""
         n = len(inputs)
         pages = (C.c_void_p * n)(*[i._h for i in inputs])
         rects = np.ascontiguousarray(rects, np.float32)
@@ -469,10 +486,14 @@ class OcrEngine:
         nl = len(lo) - 1
         chars = C.POINTER(_lib.TextCharC)()
         coffs = C.POINTER(C.c_size_t)()
-        check(lib().ocrs_engine_recognize_text_batch(
-            self._h, pages, C.c_size_t(n), po.ctypes.data_as(C.POINTER(C.c_size_t)),
-            rects.ctypes.data_as(C.POINTER(C.c_float)), lo.ctypes.data_as(C.POINTER(C.c_size_t)), C.c_size_t(nl),
-            C.byref(chars), C.byref(coffs)))
+        args = [self._h, pages, C.c_size_t(n), po.ctypes.data_as(C.POINTER(C.c_size_t)),
+                rects.ctypes.data_as(C.POINTER(C.c_float)), lo.ctypes.data_as(C.POINTER(C.c_size_t)), C.c_size_t(nl),
+                C.byref(chars), C.byref(coffs)]
+        if scores:
+            clp, lsc = C.POINTER(C.c_float)(), C.POINTER(C.c_double)()
+            check(lib().ocrs_engine_recognize_text_batch_scored(*args, C.byref(clp), C.byref(lsc)))
+        else:
+            check(lib().ocrs_engine_recognize_text_batch(*args))
         co = np.ctypeslib.as_array(coffs, shape=(nl + 1,)).astype(np.uintp)
         total = int(co[nl])
         dt = np.dtype([("ch", np.uint32), ("top", np.int32), ("left", np.int32), ("bottom", np.int32), ("right", np.int32)])
@@ -483,27 +504,36 @@ class OcrEngine:
             arr = np.zeros(0, dt)
         lib().ocrs_buffer_free(chars)
         lib().ocrs_buffer_free(coffs)
-        return arr, co
+        if not scores:
+            return arr, co
+        char_logp = np.ctypeslib.as_array(clp, shape=(max(total, 1),))[:total].copy()
+        line_score = np.ctypeslib.as_array(lsc, shape=(max(nl, 1),))[:nl].copy()
+        lib().ocrs_buffer_free(clp)
+        lib().ocrs_buffer_free(lsc)
+        return arr, co, char_logp, line_score
 
     # ---- lib.rs:237-256
-    def recognize_text(self, inp, lines):
-        """OcrEngine::recognize_text (lib.rs:237-256) through the single-page entry point a Rust binding uses."""
+    def recognize_text(self, inp, lines, scores=False):
+        """OcrEngine::recognize_text (lib.rs:237-256) through the single-page entry point a Rust binding uses.
+        scores=True: through ocrs_engine_recognize_text_scored; every TextChar gets its logp, every TextLine its score."""
         rects, offs = _pack_lines(lines)
         chars = C.POINTER(_lib.TextCharC)()
         coffs = C.POINTER(C.c_size_t)()
-        check(lib().ocrs_engine_recognize_text(
-            self._h, inp._h, rects.ctypes.data_as(C.POINTER(C.c_float)), offs.ctypes.data_as(C.POINTER(C.c_size_t)),
-            C.c_size_t(len(lines)), C.byref(chars), C.byref(coffs)))
-        out = []
-        for li in range(len(lines)):
-            a, b = coffs[li], coffs[li + 1]
-            out.append(TextLine([TextChar(chr(chars[k].ch), (chars[k].top, chars[k].left, chars[k].bottom, chars[k].right))
-                                 for k in range(a, b)]) if b > a else None)
-        lib().ocrs_buffer_free(chars)
-        lib().ocrs_buffer_free(coffs)
+        args = [self._h, inp._h, rects.ctypes.data_as(C.POINTER(C.c_float)), offs.ctypes.data_as(C.POINTER(C.c_size_t)),
+                C.c_size_t(len(lines)), C.byref(chars), C.byref(coffs)]
+        clp = lsc = None
+        if scores:
+            clp, lsc = C.POINTER(C.c_float)(), C.POINTER(C.c_double)()
+            check(lib().ocrs_engine_recognize_text_scored(*args, C.byref(clp), C.byref(lsc)))
+        else:
+            check(lib().ocrs_engine_recognize_text(*args))
+        out = [_line_from_c(chars, coffs, clp, lsc, li) for li in range(len(lines))]
+        for p in (chars, coffs, clp, lsc):
+            if p is not None:
+                lib().ocrs_buffer_free(p)
         return out
 
-    def recognize_text_batch(self, inputs, lines_per_page):
+    def recognize_text_batch(self, inputs, lines_per_page, scores=False):
         n = len(inputs)
         pages = (C.c_void_p * n)(*[i._h for i in inputs])
         all_lines = [l for lines in lines_per_page for l in lines]
@@ -514,25 +544,26 @@ class OcrEngine:
         plo_a = np.array(plo, dtype=np.uintp)
         chars = C.POINTER(_lib.TextCharC)()
         coffs = C.POINTER(C.c_size_t)()
-        check(lib().ocrs_engine_recognize_text_batch(
-            self._h, pages, C.c_size_t(n), plo_a.ctypes.data_as(C.POINTER(C.c_size_t)),
-            rects.ctypes.data_as(C.POINTER(C.c_float)), offs.ctypes.data_as(C.POINTER(C.c_size_t)),
-            C.c_size_t(len(all_lines)), C.byref(chars), C.byref(coffs)))
+        args = [self._h, pages, C.c_size_t(n), plo_a.ctypes.data_as(C.POINTER(C.c_size_t)),
+                rects.ctypes.data_as(C.POINTER(C.c_float)), offs.ctypes.data_as(C.POINTER(C.c_size_t)),
+                C.c_size_t(len(all_lines)), C.byref(chars), C.byref(coffs)]
+        clp = lsc = None
+        if scores:
+            clp, lsc = C.POINTER(C.c_float)(), C.POINTER(C.c_double)()
+            check(lib().ocrs_engine_recognize_text_batch_scored(*args, C.byref(clp), C.byref(lsc)))
+        else:
+            check(lib().ocrs_engine_recognize_text_batch(*args))
         result = []
         li = 0
         for lines in lines_per_page:
             page_out = []
             for _ in lines:
-                a, b = coffs[li], coffs[li + 1]
-                if b > a:
-                    page_out.append(TextLine([TextChar(chr(chars[k].ch), (chars[k].top, chars[k].left, chars[k].bottom,
-                                                                           chars[k].right)) for k in range(a, b)]))
-                else:
-                    page_out.append(None)
+                page_out.append(_line_from_c(chars, coffs, clp, lsc, li))
                 li += 1
             result.append(page_out)
-        lib().ocrs_buffer_free(chars)
-        lib().ocrs_buffer_free(coffs)
+        for p in (chars, coffs, clp, lsc):
+            if p is not None:
+                lib().ocrs_buffer_free(p)
         return result
 
     def recognize_tokens(self, inp, lines):
@@ -632,6 +663,16 @@ class OcrEngine:
             self._h = None
         except Exception:
             pass
+
+
+def _line_from_c(chars, coffs, clp, lsc, li):
+    """Line li of a recognize_text output as a TextLine (None: no text); clp / lsc: the scored call's arrays or None."""
+    a, b = coffs[li], coffs[li + 1]
+    if b <= a:
+        return None
+    return TextLine([TextChar(chr(chars[k].ch), (chars[k].top, chars[k].left, chars[k].bottom, chars[k].right),
+                              None if clp is None else np.float32(clp[k])) for k in range(a, b)],
+                    None if lsc is None else float(lsc[li]))
 
 
 def _chars_from_c(chars, coffs, nl):

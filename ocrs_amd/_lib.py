@@ -72,6 +72,7 @@ DECLARED_SYMBOLS = [
     "ocrs_group_recognize_text_batch", "ocrs_group_gather", "ocrs_group_final_gather", "ocrs_group_worker_threads", "ocrs_group_last_gather", "ocrs_device_malloc_on", "ocrs_engine_coalesce_stats", "ocrs_coalescer_selftest", "ocrs_engine_kernel_mfma_flops", "ocrs_engine_prepare_input_jpeg", "ocrs_jpeg_decode_rgb", "ocrs_jpeg_info", "ocrs_jpeg_coefficients",
     "ocrs_group_member_stats", "ocrs_numa_parse_cpulist", "ocrs_numa_bind_selftest", "ocrs_engine_recognize_logits", "ocrs_engine_set_option", "ocrs_engine_get_option", "ocrs_option_name", "ocrs_device_pool_stats", "ocrs_device_pool_configure", "ocrs_device_pool_trim",
     "ocrs_device_set_isolation", "ocrs_device_isolation", "ocrs_group_set_replay", "ocrs_abi_version",
+    "ocrs_engine_recognize_text_scored", "ocrs_engine_recognize_text_batch_scored", "ocrs_ctc_beam_search_scored",
 ]
 
 ABI_VERSION = 6   # include/ocrs_amd.h OCRS_ABI_VERSION
@@ -185,6 +186,22 @@ def ctc_beam_search(logp, width, impl=0):
     lib().ocrs_buffer_free(lab)
     lib().ocrs_buffer_free(pos)
     return out
+
+
+def ctc_beam_search_scored(logp, width, impl=0):
+    """ocrs_ctc_beam_search_scored on a [T, C] float32 matrix -> ([(label, pos)], score, step log-probs float32)."""
+    import numpy as np
+    a = np.ascontiguousarray(logp, np.float32)
+    t, c = a.shape
+    lab, pos, n = C.POINTER(C.c_uint32)(), C.POINTER(C.c_uint32)(), C.c_size_t(0)
+    score, slp = C.c_double(0.0), C.POINTER(C.c_float)()
+    check(lib().ocrs_ctc_beam_search_scored(a.ctypes.data_as(C.POINTER(C.c_float)), t, c, C.c_uint32(width), int(impl),
+                                            C.byref(lab), C.byref(pos), C.byref(n), C.byref(score), C.byref(slp)))
+    out = [(int(lab[i]), int(pos[i])) for i in range(n.value)]
+    lp = np.array([slp[i] for i in range(n.value)], np.float32)
+    for p in (lab, pos, slp):
+        lib().ocrs_buffer_free(p)
+    return out, score.value, lp
 
 
 def require_gpu():

@@ -42,6 +42,9 @@ def main(argv=None):
     ap.add_argument("--allowed-chars")
     ap.add_argument("--beam", action="store_true", help="beam search decoding (width 100, main.rs:403-404)")
     ap.add_argument("-j", "--json", action="store_true")
+    ap.add_argument("--confidence", action="store_true",
+                    help="with -j: a \"confidence\" per line and word, exp of the mean log-prob of its chars (no reference "
+                         "counterpart; uncalibrated: DESIGN.md \"Recognition confidence\")")
     ap.add_argument("-o", "--output")
     ap.add_argument("--debug", action="store_true")
     ap.add_argument("--text-map", action="store_true", help="write text-map.png (detect_text_pixels)")
@@ -52,6 +55,8 @@ def main(argv=None):
     ap.add_argument("--text-line-images", action="store_true",
                     help="write lines/line-N.png: the pre-processed recognition input of every text line")
     args = ap.parse_args(argv)
+    if args.confidence and not args.json:
+        ap.error("--confidence is only valid with -j/--json")
 
     from . import DecodeMethod, DimOrder, ImageSource, Model, OcrEngine, models, output
     from ._lib import OcrsError
@@ -91,9 +96,9 @@ def main(argv=None):
         os.makedirs("lines", exist_ok=True)
         for i, line in enumerate(lines):
             write_image("lines/line-%d.png" % i, engine.prepare_recognition_input(inp, line) + np.float32(0.5))
-    texts = engine.recognize_text(inp, lines)
+    texts = engine.recognize_text(inp, lines, scores=args.confidence)
     if args.json:
-        content = output.format_json_output(args.image, tuple(shape_hw), texts)
+        content = output.format_json_output(args.image, tuple(shape_hw), texts, confidence=args.confidence)
     else:
         content = output.format_text_output(texts)
     if args.output:

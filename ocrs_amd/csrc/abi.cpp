@@ -67,47 +67,86 @@ ocrs_status ocrs_coalescer_selftest(int n_threads, int requests_per_thread, int 
     });
 }
 
+namespace {
+
+// ocrs_ctc_beam_search[_scored]: score / step_logp null for the unscored hook
+void beam_search_hook(const float* logp, int t, int c, uint32_t width, int impl, std::vector<uint32_t>* l,
+                      std::vector<uint32_t>* p, double* score, std::vector<float>* step_logp) {
+    if (impl == 2 && t > 0) {   // the HIP kernel, on this matrix as a one-line packed batch
+        DeviceScope bind(-1);
+        if (!k::ctc_beam_supported(c, (int)width)) fail(OCRS_ERR_CAPACITY, "beam search on the GPU supports up to 128 classes and width 128");
+        Workspace ws;
+        std::vector<int32_t> meta(1 + t + 1);
+        meta[0] = t;
+        for (int i = 0; i <= t; i++) meta[1 + i] = i;   // off[t] = t: one line, row t = time t
+        int32_t* d_meta = ws.alloc_n<int32_t>(meta.size());
+        float* d_logp = ws.alloc_n<float>((size_t)t * c);
+        ws.upload(d_meta, meta.data(), meta.size() * sizeof(int32_t));
+        ws.upload(d_logp, logp, (size_t)t * c * sizeof(float));
+        const size_t arena = k::ctc_beam_arena_entries(t, (int)width);
+        int2* d_nodes = ws.alloc_n<int2>(arena);
+        int2* d_posn = ws.alloc_n<int2>(arena);
+        uint32_t* d_ol = ws.alloc_n<uint32_t>(t);
+        uint32_t* d_op = ws.alloc_n<uint32_t>(t);
+        int32_t* d_cnt = ws.alloc_n<int32_t>(1);
+        double* d_score = score ? ws.alloc_n<double>(1) : nullptr;
+        float* d_slp = score ? ws.alloc_n<float>(t) : nullptr;
+        k::ctc_beam_packed(d_logp, d_meta, d_meta + 1, 1, t, c, (int)width, nullptr, d_nodes, d_posn, d_ol, d_op, d_cnt, ws.s(),
+                           d_score, d_slp);
+        std::vector<uint32_t> hl(t), hp(t);
+        std::vector<float> hs(score ? t : 0);
+        int32_t cnt = 0;
+        ws.download(hl.data(), d_ol, (size_t)t * 4);
+        ws.download(hp.data(), d_op, (size_t)t * 4);
+        ws.download(&cnt, d_cnt, 4);
+        if (score) {
+            ws.download(score, d_score, sizeof(double));
+            ws.download(hs.data(), d_slp, (size_t)t * sizeof(float));
+        }
+        ws.sync();
+        OCRS_HIP(hipGetLastError());
+        l->assign(hl.begin(), hl.begin() + cnt);
+        p->assign(hp.begin(), hp.begin() + cnt);
+        if (score) step_logp->assign(hs.begin(), hs.begin() + cnt);
+    } else {
+        double bs = 0.0;   // t = 0: the empty beam, lse(0, -inf) = 0
+        const std::vector<CtcStep> st = t == 0 ? std::vector<CtcStep>()
+                                              : (impl == 1 ? ctc_beam_search_reference(logp, t, c, c, width, &bs)
+                                                           : ctc_beam_search(logp, t, c, c, width, &bs));
+        l->resize(st.size()); p->resize(st.size());
+        for (size_t i = 0; i < st.size(); i++) { (*l)[i] = st[i].label; (*p)[i] = st[i].pos; }
+        if (score) score_line(logp, t, c, c, nullptr, st, &bs, step_logp, score);
+    }
+}
+
+}  // namespace
+
 ocrs_status ocrs_ctc_beam_search(const float* logp, int t, int c, uint32_t width, int impl, uint32_t** labels,
                                  uint32_t** positions, size_t* n) {
     return guarded([&] {
         if (!logp || !labels || !positions || !n || t < 0 || c < 1) fail(OCRS_ERR_INVALID_ARGUMENT, "bad argument");
         std::vector<uint32_t> l, p;
-        if (impl == 2 && t > 0) {   // the HIP kernel, on this matrix as a one-line packed batch
-            DeviceScope bind(-1);
-            if (!k::ctc_beam_supported(c, (int)width)) fail(OCRS_ERR_CAPACITY, "beam search on the GPU supports up to 128 classes and width 128");
-            Workspace ws;
-            std::vector<int32_t> meta(1 + t + 1);
-            meta[0] = t;
-            for (int i = 0; i <= t; i++) meta[1 + i] = i;   // off[t] = t: one line, row t = time t
-            int32_t* d_meta = ws.alloc_n<int32_t>(meta.size());
-            float* d_logp = ws.alloc_n<float>((size_t)t * c);
-            ws.upload(d_meta, meta.data(), meta.size() * sizeof(int32_t));
-            ws.upload(d_logp, logp, (size_t)t * c * sizeof(float));
-            const size_t arena = k::ctc_beam_arena_entries(t, (int)width);
-            int2* d_nodes = ws.alloc_n<int2>(arena);
-            int2* d_posn = ws.alloc_n<int2>(arena);
-            uint32_t* d_ol = ws.alloc_n<uint32_t>(t);
-            uint32_t* d_op = ws.alloc_n<uint32_t>(t);
-            int32_t* d_cnt = ws.alloc_n<int32_t>(1);
-            k::ctc_beam_packed(d_logp, d_meta, d_meta + 1, 1, t, c, (int)width, nullptr, d_nodes, d_posn, d_ol, d_op, d_cnt, ws.s());
-            std::vector<uint32_t> hl(t), hp(t);
-            int32_t cnt = 0;
-            ws.download(hl.data(), d_ol, (size_t)t * 4);
-            ws.download(hp.data(), d_op, (size_t)t * 4);
-            ws.download(&cnt, d_cnt, 4);
-            ws.sync();
-            OCRS_HIP(hipGetLastError());
-            l.assign(hl.begin(), hl.begin() + cnt);
-            p.assign(hp.begin(), hp.begin() + cnt);
-        } else {
-            const std::vector<CtcStep> st = t == 0 ? std::vector<CtcStep>()
-                                                  : (impl == 1 ? ctc_beam_search_reference(logp, t, c, c, width) : ctc_beam_search(logp, t, c, c, width));
-            l.resize(st.size()); p.resize(st.size());
-            for (size_t i = 0; i < st.size(); i++) { l[i] = st[i].label; p[i] = st[i].pos; }
-        }
+        beam_search_hook(logp, t, c, width, impl, &l, &p, nullptr, nullptr);
         *labels = dup_buffer(l);
         *positions = dup_buffer(p);
         *n = l.size();
+    });
+}
+
+ocrs_status ocrs_ctc_beam_search_scored(const float* logp, int t, int c, uint32_t width, int impl, uint32_t** labels,
+                                        uint32_t** positions, size_t* n, double* score, float** step_logp) {
+    return guarded([&] {
+        if (!logp || !labels || !positions || !n || !score || !step_logp || t < 0 || c < 1)
+            fail(OCRS_ERR_INVALID_ARGUMENT, "bad argument");
+        std::vector<uint32_t> l, p;
+        std::vector<float> s;
+        double sc = 0.0;
+        beam_search_hook(logp, t, c, width, impl, &l, &p, &sc, &s);
+        *labels = dup_buffer(l);
+        *positions = dup_buffer(p);
+        *step_logp = dup_buffer(s);
+        *n = l.size();
+        *score = sc;
     });
 }
 
@@ -607,10 +646,12 @@ ocrs_status ocrs_engine_find_text_lines_batch(const ocrs_engine* e, size_t n_pag
     });
 }
 
-ocrs_status ocrs_engine_recognize_text_batch(const ocrs_engine* e, const ocrs_page* const* pages, size_t n_pages,
-                                             const size_t* page_line_offsets, const float* line_rects,
-                                             const size_t* line_offsets, size_t n_lines, ocrs_text_char** chars,
-                                             size_t** char_offsets) {
+namespace {
+
+// ocrs_engine_recognize_text[_batch][_scored]: char_logp / line_score null for the unscored calls
+ocrs_status recognize_text_batch(const ocrs_engine* e, const ocrs_page* const* pages, size_t n_pages, const size_t* page_line_offsets,
+                                 const float* line_rects, const size_t* line_offsets, size_t n_lines, ocrs_text_char** chars,
+                                 size_t** char_offsets, float** char_logp, double** line_score) {
     return guarded_engine(e, [&] {
         if (!e || !pages || !page_line_offsets || !line_offsets || !chars || !char_offsets)
             fail(OCRS_ERR_INVALID_ARGUMENT, "null argument");
@@ -622,17 +663,36 @@ ocrs_status ocrs_engine_recognize_text_batch(const ocrs_engine* e, const ocrs_pa
         std::vector<std::vector<CtcStep>> steps;
         std::vector<RecLine> rl;
         std::vector<uint32_t> ctc_len;
-        e->recognize(pages, n_pages, lpp, &steps, &rl, &ctc_len);
+        const bool scored = char_logp != nullptr;
+        RecScores sc;
+        e->recognize(pages, n_pages, lpp, &steps, &rl, &ctc_len, scored ? &sc : nullptr);
         std::vector<ocrs_text_char> flat;
         std::vector<size_t> offs{0};
+        std::vector<float> flat_lp, lp;
         for (size_t i = 0; i < rl.size(); i++) {
-            for (const TextChar& c : e->text_line_from_result(rl[i], ctc_len[i], steps[i]))
+            for (const TextChar& c : e->text_line_from_result(rl[i], ctc_len[i], steps[i], scored ? &sc.step_logp[i] : nullptr,
+                                                              scored ? &lp : nullptr))
                 flat.push_back(ocrs_text_char{c.ch, c.rect.top, c.rect.left, c.rect.bottom, c.rect.right});
+            if (scored) flat_lp.insert(flat_lp.end(), lp.begin(), lp.end());
             offs.push_back(flat.size());
         }
         *chars = dup_buffer(flat);
         *char_offsets = dup_buffer(offs);
+        if (scored) {
+            *char_logp = dup_buffer(flat_lp);
+            *line_score = dup_buffer(sc.line_score);
+        }
     });
+}
+
+}  // namespace
+
+ocrs_status ocrs_engine_recognize_text_batch(const ocrs_engine* e, const ocrs_page* const* pages, size_t n_pages,
+                                             const size_t* page_line_offsets, const float* line_rects,
+                                             const size_t* line_offsets, size_t n_lines, ocrs_text_char** chars,
+                                             size_t** char_offsets) {
+    return recognize_text_batch(e, pages, n_pages, page_line_offsets, line_rects, line_offsets, n_lines, chars, char_offsets,
+                                nullptr, nullptr);
 }
 
 ocrs_status ocrs_engine_recognize_text(const ocrs_engine* e, const ocrs_page* page, const float* line_rects,
@@ -640,6 +700,23 @@ ocrs_status ocrs_engine_recognize_text(const ocrs_engine* e, const ocrs_page* pa
                                        size_t** char_offsets) {
     size_t plo[2] = {0, n_lines};
     return ocrs_engine_recognize_text_batch(e, &page, 1, plo, line_rects, line_offsets, n_lines, chars, char_offsets);
+}
+
+ocrs_status ocrs_engine_recognize_text_batch_scored(const ocrs_engine* e, const ocrs_page* const* pages, size_t n_pages,
+                                                    const size_t* page_line_offsets, const float* line_rects,
+                                                    const size_t* line_offsets, size_t n_lines, ocrs_text_char** chars,
+                                                    size_t** char_offsets, float** char_logp, double** line_score) {
+    if (!char_logp || !line_score) return guarded([] { fail(OCRS_ERR_INVALID_ARGUMENT, "null argument"); });
+    return recognize_text_batch(e, pages, n_pages, page_line_offsets, line_rects, line_offsets, n_lines, chars, char_offsets,
+                                char_logp, line_score);
+}
+
+ocrs_status ocrs_engine_recognize_text_scored(const ocrs_engine* e, const ocrs_page* page, const float* line_rects,
+                                              const size_t* line_offsets, size_t n_lines, ocrs_text_char** chars,
+                                              size_t** char_offsets, float** char_logp, double** line_score) {
+    size_t plo[2] = {0, n_lines};
+    return ocrs_engine_recognize_text_batch_scored(e, &page, 1, plo, line_rects, line_offsets, n_lines, chars, char_offsets,
+                                                   char_logp, line_score);
 }
 
 ocrs_status ocrs_engine_recognize_tokens(const ocrs_engine* e, const ocrs_page* page, const float* line_rects,

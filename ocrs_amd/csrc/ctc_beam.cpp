@@ -41,7 +41,7 @@ struct PosNode { int parent; uint32_t pos; };
 struct Beam { int labels; int positions; double pb, pnb; };
 }  // namespace
 
-std::vector<CtcStep> ctc_beam_search_reference(const float* logp, int T, int C, int row_stride, uint32_t width) {
+std::vector<CtcStep> ctc_beam_search_reference(const float* logp, int T, int C, int row_stride, uint32_t width, double* score) {
     std::vector<LabelNode> trie(1);
     trie[0].parent = -1;
     trie[0].label = 0;
@@ -107,6 +107,7 @@ std::vector<CtcStep> ctc_beam_search_reference(const float* logp, int T, int C, 
         const double sc = lse(beams[i].pb, beams[i].pnb);
         if (sc > best_score) { best = i; best_score = sc; }
     }
+    if (score) *score = best_score;
     std::vector<CtcStep> out;
     int ln = beams[best].labels, pn = beams[best].positions;
     while (ln > 0) {
@@ -118,7 +119,7 @@ std::vector<CtcStep> ctc_beam_search_reference(const float* logp, int T, int C, 
     return out;
 }
 
-std::vector<CtcStep> ctc_beam_search(const float* logp, int T, int C, int row_stride, uint32_t width) {
+std::vector<CtcStep> ctc_beam_search(const float* logp, int T, int C, int row_stride, uint32_t width, double* score) {
     struct Node { int parent; int label; };
     struct FBeam { int node, pos; double pb, pnb; };
     struct Cand { double score; int key; };
@@ -206,6 +207,7 @@ std::vector<CtcStep> ctc_beam_search(const float* logp, int T, int C, int row_st
         const double sc = lse(beams[i].pb, beams[i].pnb);
         if (sc > best_score) { best = i; best_score = sc; }
     }
+    if (score) *score = best_score;
     std::vector<CtcStep> out;
     int ln = beams[best].node, pn = beams[best].pos;
     while (ln > 0) {
@@ -215,6 +217,28 @@ std::vector<CtcStep> ctc_beam_search(const float* logp, int T, int C, int row_st
     }
     std::reverse(out.begin(), out.end());
     return out;
+}
+
+void score_line(const float* logp, int T, int C, size_t row_stride, const uint8_t* excluded, const std::vector<CtcStep>& steps,
+                const double* beam_score, std::vector<float>* step_logp, double* line_score) {
+    const float ninf = -std::numeric_limits<float>::infinity();
+    auto at = [&](int t, int c) { return (excluded && excluded[c]) ? ninf : logp[(size_t)t * row_stride + c]; };
+    step_logp->resize(steps.size());
+    for (size_t i = 0; i < steps.size(); i++) (*step_logp)[i] = at((int)steps[i].pos, (int)steps[i].label);
+    if (beam_score) {
+        *line_score = *beam_score;
+        return;
+    }
+    double s = 0.0;
+    for (int t = 0; t < T; t++) {   // the row maximum exactly as log_softmax_argmax_kernel keeps it (first of equals)
+        float bv = at(t, 0);
+        for (int c = 1; c < C; c++) {
+            const float v = at(t, c);
+            if (v > bv) bv = v;
+        }
+        s += (double)bv;
+    }
+    *line_score = s;
 }
 
 }  // namespace ocrs

@@ -309,25 +309,33 @@ void ocrs_engine::init_coalescers() {
                 [&] {
                     if (batch.size() == 1) {
                         RecRequest& r = *batch[0];
-                        recognize_now(r.pages, r.n_pages, *r.lines_per_page, r.steps, r.rec_lines, r.ctc_len);
+                        recognize_now(r.pages, r.n_pages, *r.lines_per_page, r.steps, r.rec_lines, r.ctc_len, nullptr, r.scores);
                         return;
                     }
                     std::vector<const ocrs_page*> pages;
                     std::vector<std::vector<std::vector<RotatedRect>>> lpp;
+                    bool any_scores = false;   // scored if any member asked; the steps are the same either way
                     for (RecRequest* r : batch) {
                         pages.insert(pages.end(), r->pages, r->pages + r->n_pages);
                         lpp.insert(lpp.end(), r->lines_per_page->begin(), r->lines_per_page->end());
+                        any_scores = any_scores || r->scores;
                     }
                     std::vector<std::vector<CtcStep>> steps;
                     std::vector<RecLine> rl;
                     std::vector<uint32_t> cl;
-                    recognize_now(pages.data(), pages.size(), lpp, &steps, &rl, &cl);
+                    RecScores sc;
+                    recognize_now(pages.data(), pages.size(), lpp, &steps, &rl, &cl, nullptr, any_scores ? &sc : nullptr);
                     size_t line0 = 0, page0 = 0;
                     for (RecRequest* r : batch) {
                         size_t nl = 0;
                         for (const auto& pg : *r->lines_per_page) nl += pg.size();
                         r->steps->assign(std::make_move_iterator(steps.begin() + line0), std::make_move_iterator(steps.begin() + line0 + nl));
                         r->ctc_len->assign(cl.begin() + line0, cl.begin() + line0 + nl);
+                        if (r->scores) {
+                            r->scores->step_logp.assign(std::make_move_iterator(sc.step_logp.begin() + line0),
+                                                        std::make_move_iterator(sc.step_logp.begin() + line0 + nl));
+                            r->scores->line_score.assign(sc.line_score.begin() + line0, sc.line_score.begin() + line0 + nl);
+                        }
                         r->rec_lines->assign(std::make_move_iterator(rl.begin() + line0), std::make_move_iterator(rl.begin() + line0 + nl));
                         for (RecLine& l : *r->rec_lines) {   // back to the caller's numbering
                             l.page -= page0;
@@ -337,7 +345,9 @@ void ocrs_engine::init_coalescers() {
                         page0 += r->n_pages;
                     }
                 },
-                [&](RecRequest& r) { recognize_now(r.pages, r.n_pages, *r.lines_per_page, r.steps, r.rec_lines, r.ctc_len); });
+                [&](RecRequest& r) {
+                    recognize_now(r.pages, r.n_pages, *r.lines_per_page, r.steps, r.rec_lines, r.ctc_len, nullptr, r.scores);
+                });
         },
         [](const RecRequest&, const RecRequest&) { return true; });   // lines of any pages share a ragged batch
 }
@@ -360,16 +370,16 @@ void ocrs_engine::detect(const ocrs_page* const* pages, size_t n, std::vector<st
 void ocrs_engine::recognize(const ocrs_page* const* pages, size_t n_pages,
                             const std::vector<std::vector<std::vector<RotatedRect>>>& lines_per_page,
                             std::vector<std::vector<CtcStep>>* steps_out, std::vector<RecLine>* rec_lines_out,
-                            std::vector<uint32_t>* ctc_len_out) const {
+                            std::vector<uint32_t>* ctc_len_out, RecScores* scores) const {
     const int max_active = option(OPT_COALESCE);
     const size_t max_pages = (size_t)std::max(1, option(OPT_COALESCE_PAGES));
     if (max_active <= 0 || !rec_queue || n_pages == 0 || 2 * n_pages >= max_pages || !recognition || recognition->is_callback()) {
-        recognize_now(pages, n_pages, lines_per_page, steps_out, rec_lines_out, ctc_len_out);
+        recognize_now(pages, n_pages, lines_per_page, steps_out, rec_lines_out, ctc_len_out, nullptr, scores);
         return;
     }
     RecRequest r;
     r.pages = pages; r.n_pages = n_pages; r.lines_per_page = &lines_per_page;
-    r.steps = steps_out; r.rec_lines = rec_lines_out; r.ctc_len = ctc_len_out; r.weight = n_pages;
+    r.steps = steps_out; r.rec_lines = rec_lines_out; r.ctc_len = ctc_len_out; r.scores = scores; r.weight = n_pages;
     rec_queue->submit(r, max_active, max_pages, option_long(OPT_COALESCE_WINDOW_US));
 }
 
@@ -466,7 +476,8 @@ static double rec_pixel_budget() {
 void ocrs_engine::recognize_now(const ocrs_page* const* pages, size_t n_pages,
                                 const std::vector<std::vector<std::vector<RotatedRect>>>& lines_per_page,
                                 std::vector<std::vector<CtcStep>>* steps_out, std::vector<RecLine>* rec_lines_out,
-                                std::vector<uint32_t>* ctc_len_out, std::vector<std::vector<float>>* logp_out) const {
+                                std::vector<uint32_t>* ctc_len_out, std::vector<std::vector<float>>* logp_out,
+                                RecScores* scores) const {
     if (!recognition) fail(OCRS_ERR_MODEL_NOT_LOADED, "Recognition model not loaded");
     const uint32_t rec_h = rec_input_height();
     std::vector<RecLine> lines;
@@ -477,13 +488,17 @@ void ocrs_engine::recognize_now(const ocrs_page* const* pages, size_t n_pages,
     double total = 0.0;
     for (const RecLine& l : lines) total += (double)rec_h * l.group_width;
     if (total <= budget) {
-        recognize_lines(pages, n_pages, lines, steps_out, ctc_len_out, logp_out);
+        recognize_lines(pages, n_pages, lines, steps_out, ctc_len_out, logp_out, scores);
         *rec_lines_out = std::move(lines);
         return;
     }
     steps_out->assign(L, {});
     ctc_len_out->assign(L, 0);
     if (logp_out) logp_out->assign(L, {});
+    if (scores) {
+        scores->step_logp.assign(L, {});
+        scores->line_score.assign(L, 0.0);
+    }
     for (size_t b = 0; b < L;) {
         size_t e = b;
         double px = 0.0;
@@ -492,11 +507,16 @@ void ocrs_engine::recognize_now(const ocrs_page* const* pages, size_t n_pages,
         std::vector<std::vector<CtcStep>> st;
         std::vector<uint32_t> cl;
         std::vector<std::vector<float>> lp;
-        recognize_lines(pages, n_pages, part, &st, &cl, logp_out ? &lp : nullptr);
+        RecScores sc;
+        recognize_lines(pages, n_pages, part, &st, &cl, logp_out ? &lp : nullptr, scores ? &sc : nullptr);
         for (size_t i = b; i < e; i++) {
             (*steps_out)[i] = std::move(st[i - b]);
             (*ctc_len_out)[i] = cl[i - b];
             if (logp_out) (*logp_out)[i] = std::move(lp[i - b]);
+            if (scores) {
+                scores->step_logp[i] = std::move(sc.step_logp[i - b]);
+                scores->line_score[i] = sc.line_score[i - b];
+            }
         }
         b = e;
     }
@@ -516,9 +536,13 @@ void ocrs_engine::recognize_logits(const ocrs_page* page, const std::vector<std:
 
 void ocrs_engine::recognize_lines(const ocrs_page* const* pages, size_t n_pages, const std::vector<RecLine>& lines,
                                   std::vector<std::vector<CtcStep>>* steps_out, std::vector<uint32_t>* ctc_len_out,
-                                  std::vector<std::vector<float>>* logp_out) const {
+                                  std::vector<std::vector<float>>* logp_out, RecScores* scores) const {
     const bool beam = decode_method == OCRS_DECODE_BEAM_SEARCH;
     if (logp_out) logp_out->assign(lines.size(), {});
+    if (scores) {   // lines without rows keep these: no steps, score 0
+        scores->step_logp.assign(lines.size(), {});
+        scores->line_score.assign(lines.size(), 0.0);
+    }
     const uint32_t rec_h = rec_input_height();
     const size_t alphabet_len = alphabet.size();
 
@@ -641,8 +665,12 @@ void ocrs_engine::recognize_lines(const ocrs_page* const* pages, size_t n_pages,
                             seq[(size_t)t * C + c] = v;
                         }
                     const size_t li = ch.members[j];
-                    (*steps_out)[li] = ctc_beam_search(seq.data(), Tn, C, C, beam_width);
+                    double bs = 0.0;
+                    (*steps_out)[li] = ctc_beam_search(seq.data(), Tn, C, C, beam_width, scores ? &bs : nullptr);
                     (*ctc_len_out)[li] = (uint32_t)Tn;
+                    if (scores)
+                        score_line(seq.data(), Tn, C, C, nullptr, (*steps_out)[li], &bs, &scores->step_logp[li],
+                                   &scores->line_score[li]);
                 }
                 continue;
             }
@@ -669,6 +697,9 @@ void ocrs_engine::recognize_lines(const ocrs_page* const* pages, size_t n_pages,
                 sv.resize(hc[j]);
                 for (int q = 0; q < hc[j]; q++) sv[q] = CtcStep{hl[j * Tn + q], hpz[j * Tn + q]};
                 (*ctc_len_out)[li] = (uint32_t)Tn;
+                if (scores)   // the model output is on the host already: line j's row t is hout[(t * nb + j) * C]
+                    score_line(&hout[j * C], Tn, C, nb * (size_t)C, has_excluded ? excluded.data() : nullptr, sv, nullptr,
+                               &scores->step_logp[li], &scores->line_score[li]);
             }
         }
     } else {
@@ -702,6 +733,8 @@ void ocrs_engine::recognize_lines(const ocrs_page* const* pages, size_t n_pages,
             std::vector<Slot> slots;
             std::vector<uint32_t> hl, hp;
             std::vector<int32_t> hc;
+            std::vector<float> hlp;        // scored, on the GPU: [M][Tmax] step log-probs
+            std::vector<double> hscore;    // scored, on the GPU: [M] line scores
             int Tmax = 0;
             uint32_t gru_status[8] = {0};  // time-out words of the persistent GRU kernels (0 = fine)
             bool gpu_beam = false;         // beam search already done on the GPU: hl/hp/hc hold its steps
@@ -760,7 +793,9 @@ void ocrs_engine::recognize_lines(const ocrs_page* const* pages, size_t n_pages,
                                                        d_meta + pos_at[c - c0]});
             int32_t* d_labels = w.alloc_n<int32_t>((size_t)plan.R);
             float* d_logp = nullptr;
-            hm->run_recognition_packed(w, pg, plan, (int)rec_h, T, d_excl, d_labels, (beam || logp_out) ? &d_logp : nullptr);
+            float* d_maxlp = (scores && !beam) ? w.alloc_n<float>((size_t)plan.R) : nullptr;
+            hm->run_recognition_packed(w, pg, plan, (int)rec_h, T, d_excl, d_labels, (beam || logp_out) ? &d_logp : nullptr,
+                                       d_maxlp);
             if (logp_out) {
                 sub.logp.resize((size_t)plan.R * C);
                 sub.off = hoff;
@@ -777,10 +812,12 @@ void ocrs_engine::recognize_lines(const ocrs_page* const* pages, size_t n_pages,
                 uint32_t* d_ol = w.alloc_n<uint32_t>((size_t)M * Tmax);
                 uint32_t* d_op = w.alloc_n<uint32_t>((size_t)M * Tmax);
                 int32_t* d_cnt = w.alloc_n<int32_t>(M);
+                double* d_score = scores ? w.alloc_n<double>(M) : nullptr;
+                float* d_slp = scores ? w.alloc_n<float>((size_t)M * Tmax) : nullptr;
                 {
                     StageScope sc(T, ST_CTC, sst);
                     k::ctc_beam_packed(d_logp, plan.d_Tm, plan.d_off, M, Tmax, C, (int)beam_width, d_excl, d_nodes, d_posn, d_ol,
-                                       d_op, d_cnt, sst);
+                                       d_op, d_cnt, sst, d_score, d_slp);
                 }
                 sub.hl.resize((size_t)M * Tmax);
                 sub.hp.resize((size_t)M * Tmax);
@@ -788,6 +825,12 @@ void ocrs_engine::recognize_lines(const ocrs_page* const* pages, size_t n_pages,
                 w.download(sub.hl.data(), d_ol, sub.hl.size() * 4, sst);
                 w.download(sub.hp.data(), d_op, sub.hp.size() * 4, sst);
                 w.download(sub.hc.data(), d_cnt, (size_t)M * 4, sst);
+                if (scores) {
+                    sub.hlp.resize((size_t)M * Tmax);
+                    sub.hscore.resize(M);
+                    w.download(sub.hlp.data(), d_slp, sub.hlp.size() * sizeof(float), sst);
+                    w.download(sub.hscore.data(), d_score, (size_t)M * sizeof(double), sst);
+                }
                 return;
             }
             if (beam) {
@@ -805,7 +848,19 @@ void ocrs_engine::recognize_lines(const ocrs_page* const* pages, size_t n_pages,
             uint32_t* d_ol = w.alloc_n<uint32_t>((size_t)M * Tmax);
             uint32_t* d_op = w.alloc_n<uint32_t>((size_t)M * Tmax);
             int32_t* d_cnt = w.alloc_n<int32_t>(M);
-            {
+            if (scores) {   // the same collapse, with each step's log-prob and the greedy path's score, in one pass
+                float* d_slp = w.alloc_n<float>((size_t)M * Tmax);
+                double* d_score = w.alloc_n<double>(M);
+                {
+                    StageScope sc(T, ST_CTC, sst);
+                    k::ctc_collapse_scored_packed(d_labels, d_maxlp, plan.d_Tm, plan.d_off, M, Tmax, d_ol, d_op, d_slp, d_cnt,
+                                                  d_score, sst);
+                }
+                sub.hlp.resize((size_t)M * Tmax);
+                sub.hscore.resize(M);
+                w.download(sub.hlp.data(), d_slp, sub.hlp.size() * sizeof(float), sst);
+                w.download(sub.hscore.data(), d_score, (size_t)M * sizeof(double), sst);
+            } else {
                 StageScope sc(T, ST_CTC, sst);
                 k::ctc_collapse_packed(d_labels, plan.d_Tm, plan.d_off, M, Tmax, d_ol, d_op, d_cnt, sst);
             }
@@ -842,8 +897,12 @@ void ocrs_engine::recognize_lines(const ocrs_page* const* pages, size_t n_pages,
                                     seq[(size_t)t * C + c] = (has_excluded && excluded[c]) ? -std::numeric_limits<float>::infinity() : src[c];
                             }
                             const size_t li = sub.slots[m].line;
-                            (*steps_out)[li] = ctc_beam_search(seq.data(), Tm, C, C, beam_width);
+                            double bs = 0.0;
+                            (*steps_out)[li] = ctc_beam_search(seq.data(), Tm, C, C, beam_width, scores ? &bs : nullptr);
                             (*ctc_len_out)[li] = (uint32_t)Tm;
+                            if (scores)
+                                score_line(seq.data(), Tm, C, C, nullptr, (*steps_out)[li], &bs, &scores->step_logp[li],
+                                           &scores->line_score[li]);
                         }
                     });
                 for (auto& t : th) t.join();
@@ -856,6 +915,11 @@ void ocrs_engine::recognize_lines(const ocrs_page* const* pages, size_t n_pages,
                 for (int q = 0; q < sub.hc[m]; q++)
                     sv[q] = CtcStep{sub.hl[m * sub.Tmax + q], sub.hp[m * sub.Tmax + q]};
                 (*ctc_len_out)[li] = (uint32_t)sub.slots[m].T;
+                if (scores) {
+                    const float* lp = &sub.hlp[m * sub.Tmax];
+                    scores->step_logp[li].assign(lp, lp + sub.hc[m]);
+                    scores->line_score[li] = sub.hscore[m];
+                }
             }
         };
         Sub sub_long, sub_short;
@@ -882,8 +946,10 @@ void ocrs_engine::recognize_lines(const ocrs_page* const* pages, size_t n_pages,
 
 // recognition.rs:241-311 for one line
 std::vector<TextChar> ocrs_engine::text_line_from_result(const RecLine& line, uint32_t ctc_input_len,
-                                                         const std::vector<CtcStep>& steps) const {
+                                                         const std::vector<CtcStep>& steps, const std::vector<float>* step_logp,
+                                                         std::vector<float>* char_logp) const {
     std::vector<TextChar> out;
+    if (char_logp) char_logp->clear();
     if (steps.empty() || ctc_input_len == 0) return out;
     const Rect line_rect = line.bounds;
     const float x_scale = (float)line_rect.width() / (float)line.resized_width;
@@ -900,6 +966,7 @@ std::vector<TextChar> ocrs_engine::text_line_from_result(const RecLine& line, ui
         if (!polygon_slice_bounding_rect(line.polygon, sx, ex, &r))
             fail(OCRS_ERR_RUN_FAILED, "invalid X coords");  // recognition.rs:299
         out.push_back(TextChar{ch, r});
+        if (char_logp) char_logp->push_back((*step_logp)[i]);   // padding steps are skipped with their chars
     }
     return out;
 }

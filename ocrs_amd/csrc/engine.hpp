@@ -23,10 +23,24 @@ namespace ocrs {
 
 struct CtcStep { uint32_t label, pos; };
 
-// ctc_beam.cpp — rten decode_beam (recognition.rs:512-514)
-std::vector<CtcStep> ctc_beam_search(const float* logp, int T, int C, int row_stride, uint32_t width);
+// ctc_beam.cpp — rten decode_beam (recognition.rs:512-514).  score (optional): the best beam's lse(pb, pnb).
+std::vector<CtcStep> ctc_beam_search(const float* logp, int T, int C, int row_stride, uint32_t width, double* score = nullptr);
 // the same function written as the algorithm is usually stated (trie + candidate map); tests compare the two
-std::vector<CtcStep> ctc_beam_search_reference(const float* logp, int T, int C, int row_stride, uint32_t width);
+std::vector<CtcStep> ctc_beam_search_reference(const float* logp, int T, int C, int row_stride, uint32_t width,
+                                               double* score = nullptr);
+
+// Recognition confidence (DESIGN.md "Recognition confidence"), per line and indexed like the steps: each step's
+// log-prob L[pos][label] and the line score (greedy: the float64 sum of the masked row maxima in ascending t; beam:
+// the best beam's lse(pb, pnb)).  A line without rows has no steps and score 0.
+struct RecScores {
+    std::vector<std::vector<float>> step_logp;
+    std::vector<double> line_score;
+};
+// The host form of the above for one line whose log-probs are on the host: row t at logp + t * row_stride, labels
+// flagged in `excluded` ([C] or null) read as -inf.  beam_score given: the line score is that value (beam search);
+// null: the greedy path's.  The GPU kernels compute the same bits (ctc_collapse_scored_packed, ctc_beam_packed).
+void score_line(const float* logp, int T, int C, size_t row_stride, const uint8_t* excluded, const std::vector<CtcStep>& steps,
+                const double* beam_score, std::vector<float>* step_logp, double* line_score);
 
 struct TextChar {  // text_items.rs:48-54
     uint32_t ch;
@@ -55,6 +69,7 @@ struct RecRequest : CoalescedBase {
     std::vector<std::vector<CtcStep>>* steps = nullptr;
     std::vector<RecLine>* rec_lines = nullptr;
     std::vector<uint32_t>* ctc_len = nullptr;
+    RecScores* scores = nullptr;   // null: the caller did not ask for confidence
 };
 
 }  // namespace ocrs
@@ -102,26 +117,31 @@ struct ocrs_engine {
     void recognize(const ocrs_page* const* pages, size_t n_pages,
                    const std::vector<std::vector<std::vector<ocrs::geom::RotatedRect>>>& lines_per_page,
                    std::vector<std::vector<ocrs::CtcStep>>* steps, std::vector<ocrs::RecLine>* rec_lines,
-                   std::vector<uint32_t>* ctc_input_len) const;
+                   std::vector<uint32_t>* ctc_input_len, ocrs::RecScores* scores = nullptr) const;
     void recognize_now(const ocrs_page* const* pages, size_t n_pages,
                        const std::vector<std::vector<std::vector<ocrs::geom::RotatedRect>>>& lines_per_page,
                        std::vector<std::vector<ocrs::CtcStep>>* steps, std::vector<ocrs::RecLine>* rec_lines,
-                       std::vector<uint32_t>* ctc_input_len, std::vector<std::vector<float>>* logp = nullptr) const;
+                       std::vector<uint32_t>* ctc_input_len, std::vector<std::vector<float>>* logp = nullptr,
+                       ocrs::RecScores* scores = nullptr) const;
     void init_coalescers();
     mutable std::unique_ptr<ocrs::Coalescer<ocrs::DetRequest>> det_queue;
     mutable std::unique_ptr<ocrs::Coalescer<ocrs::RecRequest>> rec_queue;
     // one sub-request of `recognize` (within the activation budget); outputs indexed like `lines`
     // logp (optional): per line the model's log-probabilities [T][C] (TextRecognizer::run, recognition.rs:341-360), unmasked
+    // scores (optional): per line the step log-probs and line score; null launches nothing extra
     void recognize_lines(const ocrs_page* const* pages, size_t n_pages, const std::vector<ocrs::RecLine>& lines,
                          std::vector<std::vector<ocrs::CtcStep>>* steps, std::vector<uint32_t>* ctc_input_len,
-                         std::vector<std::vector<float>>* logp = nullptr) const;
+                         std::vector<std::vector<float>>* logp = nullptr, ocrs::RecScores* scores = nullptr) const;
     // the recognition model's output for the lines of one page, no coalescing (parity / tolerance checks); split into
     // sub-requests within the activation budget as `recognize` is
     void recognize_logits(const ocrs_page* page, const std::vector<std::vector<ocrs::geom::RotatedRect>>& lines,
                           std::vector<std::vector<float>>* logp, int* classes) const;
 
+    // step_logp (optional, indexed like steps): char_logp receives the log-prob of every char's step, aligned with the result
     std::vector<ocrs::TextChar> text_line_from_result(const ocrs::RecLine& line, uint32_t ctc_input_len,
-                                                      const std::vector<ocrs::CtcStep>& steps) const;
+                                                      const std::vector<ocrs::CtcStep>& steps,
+                                                      const std::vector<float>* step_logp = nullptr,
+                                                      std::vector<float>* char_logp = nullptr) const;
 
     uint32_t rec_input_height() const;
     ocrs::RecLine make_rec_line(const std::vector<ocrs::geom::RotatedRect>& words, size_t page, size_t index) const;

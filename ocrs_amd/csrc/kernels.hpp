@@ -145,10 +145,10 @@ void to_seq(const float* x, int n, int w, int c, float* y, hipStream_t s);
 // gx: [2][T*N][3H] (dir-major), gh: [2][N][3H], h: [2][N][H], y: [T][N][2H].
 void gru_gates(const float* gx, const float* gh, float* h, float* y, int T, int N, int H, int step, hipStream_t s);
 // log_softmax over C (+ optional -inf masking of excluded labels) + argmax.
-// logits/logp: [rows][C]; labels: [rows] (first max).  logp may be null.  Returns false (nothing launched)
-// if C is too large for the kernel's LDS staging (more than ~630 classes).
+// logits/logp: [rows][C]; labels: [rows] (first max).  logp may be null.  maxlp (optional): [rows] the masked
+// maximum itself.  Returns false (nothing launched) if C is too large for the kernel's LDS staging (more than ~630 classes).
 bool log_softmax_argmax(const float* logits, int64_t rows, int c, const uint8_t* d_excluded /*[C] or null*/,
-                        float* logp, int32_t* labels, hipStream_t s);
+                        float* logp, int32_t* labels, hipStream_t s, float* maxlp = nullptr);
 // Ragged sequence batch (lines sorted by length, rows off[t] + m); see kernels_nn.hip.
 void to_seq_packed(const float* x, int n, int T, int c, const int32_t* d_pos, const int32_t* d_off, float* y,
                    hipStream_t s);
@@ -185,15 +185,21 @@ bool gru_persistent_split(const float* gx, const float* wh, const float* bh, flo
                           const int32_t* h_Tm, int64_t R, int M, int Tmax, int H, int np, uint32_t* d_sync, hipStream_t s);
 void ctc_collapse_packed(const int32_t* labels, const int32_t* d_Tm, const int32_t* d_off, int M, int Tmax,
                          uint32_t* out_labels, uint32_t* out_pos, int32_t* out_count, hipStream_t s);
+// ctc_collapse_packed plus confidence: out_logp [M][Tmax] each step's maxlp, out_score [M] the float64 sum of maxlp over
+// the line's rows in ascending t (the greedy path's log-probability)
+void ctc_collapse_scored_packed(const int32_t* labels, const float* maxlp, const int32_t* d_Tm, const int32_t* d_off, int M,
+                                int Tmax, uint32_t* out_labels, uint32_t* out_pos, float* out_logp, int32_t* out_count,
+                                double* out_score, hipStream_t s);
 void argmax_rows(const float* x, int64_t rows, int c, const uint8_t* d_excluded, int32_t* labels, hipStream_t s);
 // ---- kernels_beam.hip: CTC prefix beam search (rten decode_beam) on the packed log-probabilities, one workgroup
 // per line; same results as the host's ctc_beam_search.  d_nodes / d_posn: M * ctc_beam_arena_entries(Tmax, width)
 // int2 each (scratch).  Outputs in the layout of ctc_collapse_packed.  false if (C, width) is not supported.
+// out_score (optional): [M] the best beam's lse(pb, pnb); out_logp (optional): [M][Tmax] each step's masked log-prob.
 bool ctc_beam_supported(int C, int width);
 size_t ctc_beam_arena_entries(int Tmax, int width);
 bool ctc_beam_packed(const float* logp, const int32_t* d_Tm, const int32_t* d_off, int M, int Tmax, int C, int width,
                      const uint8_t* d_excluded, int2* d_nodes, int2* d_posn, uint32_t* out_labels, uint32_t* out_pos,
-                     int32_t* out_count, hipStream_t s);
+                     int32_t* out_count, hipStream_t s, double* out_score = nullptr, float* out_logp = nullptr);
 // Greedy CTC collapse (rten decode_greedy): labels [T][N] -> per line (label,pos) lists.
 void ctc_collapse(const int32_t* labels, int T, int N, uint32_t* out_labels, uint32_t* out_pos, int32_t* out_count,
                   hipStream_t s);

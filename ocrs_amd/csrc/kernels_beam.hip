@@ -39,6 +39,8 @@ struct BeamArgs {
     uint32_t* out_labels;     // [M][Tmax]
     uint32_t* out_pos;        // [M][Tmax]
     int32_t* out_count;       // [M]
+    double* out_score;        // [M] or null: the best beam's lse(pb, pnb)
+    float* out_logp;          // [M][Tmax] or null: each returned step's masked log-prob L[pos][label]
     int M, C, W, Tmax, cap;
 };
 
@@ -331,10 +333,17 @@ ctc_beam_kernel(BeamArgs a) {
         int n = 0;
         for (int ln = node[best]; ln > 0; ln = nodes[ln].x) n++;
         a.out_count[m] = n;
+        if (a.out_score) a.out_score[m] = bs;
         int ln = node[best], pn = pos[best];
         for (int q = n - 1; q >= 0; q--) {
-            a.out_labels[(size_t)m * a.Tmax + q] = (uint32_t)nodes[ln].y;
-            a.out_pos[(size_t)m * a.Tmax + q] = (uint32_t)posn[pn].y;
+            const int label = nodes[ln].y, tp = posn[pn].y;
+            a.out_labels[(size_t)m * a.Tmax + q] = (uint32_t)label;
+            a.out_pos[(size_t)m * a.Tmax + q] = (uint32_t)tp;
+            if (a.out_logp) {   // gathered from the resident log-probs, masked as in step 1
+                float v = a.logp[((size_t)a.off[tp] + m) * C + label];
+                if (a.excluded && a.excluded[label]) v = -__builtin_huge_valf();
+                a.out_logp[(size_t)m * a.Tmax + q] = v;
+            }
             ln = nodes[ln].x;
             pn = posn[pn].x;
         }
@@ -364,12 +373,13 @@ size_t ctc_beam_arena_entries(int Tmax, int width) { return (size_t)Tmax * width
 
 bool ctc_beam_packed(const float* logp, const int32_t* d_Tm, const int32_t* d_off, int M, int Tmax, int C, int width,
                      const uint8_t* d_excluded, int2* d_nodes, int2* d_posn, uint32_t* out_labels, uint32_t* out_pos,
-                     int32_t* out_count, hipStream_t s) {
+                     int32_t* out_count, hipStream_t s, double* out_score, float* out_logp) {
     if (M <= 0) return true;
     if (!ctc_beam_supported(C, width)) return false;
     BeamArgs a{};
     a.logp = logp; a.Tm = d_Tm; a.off = d_off; a.excluded = d_excluded; a.nodes = d_nodes; a.posn = d_posn;
     a.out_labels = out_labels; a.out_pos = out_pos; a.out_count = out_count;
+    a.out_score = out_score; a.out_logp = out_logp;
     a.M = M; a.C = C; a.W = width; a.Tmax = Tmax; a.cap = (int)ctc_beam_arena_entries(Tmax, width);
     const size_t lds = beam_lds_bytes(width, C);
     static std::atomic<uint64_t> lds_ok{0};

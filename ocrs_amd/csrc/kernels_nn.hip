@@ -1155,9 +1155,9 @@ void gru_gates(const float* gx, const float* gh, float* h, float* y, int T, int 
 // ---------------------------------------------------------------------------
 constexpr int LSM_ROWS = 64;
 
-__global__ void __launch_bounds__(LSM_ROWS)
-log_softmax_argmax_kernel(const float* __restrict__ logits, int64_t rows, int c, const uint8_t* __restrict__ excl,
-                          float* __restrict__ logp, int32_t* __restrict__ labels) {
+__device__ __forceinline__ void log_softmax_argmax_body(const float* __restrict__ logits, int64_t rows, int c,
+                                                        const uint8_t* __restrict__ excl, float* __restrict__ logp,
+                                                        int32_t* __restrict__ labels, float* __restrict__ maxlp) {
     extern __shared__ float tile[];  // [LSM_ROWS][c] (c odd or padded -> conflict-free row walks)
     const int cp = (c & 1) ? c : c + 1;
     const int64_t r0 = (int64_t)blockIdx.x * LSM_ROWS;
@@ -1187,6 +1187,7 @@ log_softmax_argmax_kernel(const float* __restrict__ logits, int64_t rows, int c,
             if (v > bv) { bv = v; best = j; }
         }
         if (labels) labels[r0 + threadIdx.x] = best;
+        if (maxlp) maxlp[r0 + threadIdx.x] = bv;   // the masked maximum: the greedy step's log-prob
     }
     __syncthreads();
     if (logp)
@@ -1196,8 +1197,22 @@ log_softmax_argmax_kernel(const float* __restrict__ logits, int64_t rows, int c,
         }
 }
 
+__global__ void __launch_bounds__(LSM_ROWS)
+log_softmax_argmax_kernel(const float* __restrict__ logits, int64_t rows, int c, const uint8_t* __restrict__ excl,
+                          float* __restrict__ logp, int32_t* __restrict__ labels) {
+    log_softmax_argmax_body(logits, rows, c, excl, logp, labels, nullptr);
+}
+
+// the same, also keeping each row's masked maximum (recognition confidence; a kernel of its own so that the unscored
+// launch sequence stays what it was)
+__global__ void __launch_bounds__(LSM_ROWS)
+log_softmax_argmax_max_kernel(const float* __restrict__ logits, int64_t rows, int c, const uint8_t* __restrict__ excl,
+                              float* __restrict__ logp, int32_t* __restrict__ labels, float* __restrict__ maxlp) {
+    log_softmax_argmax_body(logits, rows, c, excl, logp, labels, maxlp);
+}
+
 bool log_softmax_argmax(const float* logits, int64_t rows, int c, const uint8_t* d_excluded, float* logp,
-                        int32_t* labels, hipStream_t s) {
+                        int32_t* labels, hipStream_t s, float* maxlp) {
     if (rows <= 0) return true;
     int cp = (c & 1) ? c : c + 1;
     size_t lds = (size_t)LSM_ROWS * cp * sizeof(float);
@@ -1206,12 +1221,17 @@ bool log_softmax_argmax(const float* logits, int64_t rows, int c, const uint8_t*
     // instead of a generic launch failure
     if (lds > 160 * 1024) return false;
     if (lds > 64 * 1024) {
-        static std::atomic<uint64_t> lds_ok{0};
-        allow_dynamic_lds(reinterpret_cast<const void*>(&log_softmax_argmax_kernel), lds_ok);
+        static std::atomic<uint64_t> lds_ok{0}, lds_ok_max{0};
+        if (maxlp) allow_dynamic_lds(reinterpret_cast<const void*>(&log_softmax_argmax_max_kernel), lds_ok_max);
+        else allow_dynamic_lds(reinterpret_cast<const void*>(&log_softmax_argmax_kernel), lds_ok);
     }
     int grid = (int)((rows + LSM_ROWS - 1) / LSM_ROWS);
-    hipLaunchKernelGGL(log_softmax_argmax_kernel, dim3(grid), dim3(LSM_ROWS), lds, s, logits, rows, c, d_excluded, logp,
-                       labels);
+    if (maxlp)
+        hipLaunchKernelGGL(log_softmax_argmax_max_kernel, dim3(grid), dim3(LSM_ROWS), lds, s, logits, rows, c, d_excluded,
+                           logp, labels, maxlp);
+    else
+        hipLaunchKernelGGL(log_softmax_argmax_kernel, dim3(grid), dim3(LSM_ROWS), lds, s, logits, rows, c, d_excluded, logp,
+                           labels);
     return true;
 }
 
@@ -1445,6 +1465,70 @@ void ctc_collapse_packed(const int32_t* labels, const int32_t* d_Tm, const int32
     if (M <= 0) return;
     hipLaunchKernelGGL(ctc_collapse_packed_kernel, dim3((M + 63) / 64), dim3(64), 0, s, labels, d_Tm, d_off, M, Tmax,
                        out_labels, out_pos, out_count);
+}
+
+// The same collapse with confidence (DESIGN.md "Recognition confidence"): each emitted step also carries its row's
+// masked maximum log-prob (log_softmax_argmax's maxlp), and the line gets the float64 log-probability of the greedy
+// path, s = sum over t = 0 .. T-1 of (double) maxlp, added in ascending t.  One lane per line: row off[t] + m makes
+// a wave's reads at one t contiguous.  The walk runs in blocks of CTC_U steps whose loads are all issued before any
+// is consumed, so a lane keeps CTC_U rows in flight instead of one dependent load per step.
+constexpr int CTC_U = 16;
+
+__global__ void __launch_bounds__(64)
+ctc_collapse_scored_packed_kernel(const int32_t* __restrict__ labels, const float* __restrict__ maxlp,
+                                  const int32_t* __restrict__ Tm, const int32_t* __restrict__ off, int M, int Tmax,
+                                  uint32_t* __restrict__ out_labels, uint32_t* __restrict__ out_pos,
+                                  float* __restrict__ out_logp, int32_t* __restrict__ out_count,
+                                  double* __restrict__ out_score) {
+    const int m = blockIdx.x * blockDim.x + threadIdx.x;
+    const int T = m < M ? Tm[m] : 0;
+    int Tw = T;   // the wave's longest line bounds the (wave-uniform) block loop
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) Tw = max(Tw, __shfl_xor(Tw, d));
+    int last = 0, cnt = 0;
+    double s = 0.0;
+    const int64_t base = (int64_t)m * Tmax;
+    for (int t0 = 0; t0 < Tw; t0 += CTC_U) {
+        int l[CTC_U];
+        float v[CTC_U];
+#pragma unroll
+        for (int u = 0; u < CTC_U; u++) {
+            const int t = t0 + u;
+            l[u] = 0;
+            v[u] = 0.0f;
+            if (t < T) {
+                const int64_t r = (int64_t)off[t] + m;
+                l[u] = labels[r];
+                v[u] = maxlp[r];
+            }
+        }
+#pragma unroll
+        for (int u = 0; u < CTC_U; u++) {
+            const int t = t0 + u;
+            if (t >= T) break;
+            s += (double)v[u];
+            if (l[u] == last) continue;
+            last = l[u];
+            if (l[u] > 0) {
+                out_labels[base + cnt] = (uint32_t)l[u];
+                out_pos[base + cnt] = (uint32_t)t;
+                out_logp[base + cnt] = v[u];
+                cnt++;
+            }
+        }
+    }
+    if (m < M) {
+        out_count[m] = cnt;
+        out_score[m] = s;
+    }
+}
+
+void ctc_collapse_scored_packed(const int32_t* labels, const float* maxlp, const int32_t* d_Tm, const int32_t* d_off, int M,
+                                int Tmax, uint32_t* out_labels, uint32_t* out_pos, float* out_logp, int32_t* out_count,
+                                double* out_score, hipStream_t s) {
+    if (M <= 0) return;
+    hipLaunchKernelGGL(ctc_collapse_scored_packed_kernel, dim3((M + 63) / 64), dim3(64), 0, s, labels, maxlp, d_Tm, d_off, M,
+                       Tmax, out_labels, out_pos, out_logp, out_count, out_score);
 }
 
 // Arg-max only (for caller-implemented models whose output is already

@@ -1046,7 +1046,7 @@ int HipModel::packed_split() const {
 
 int HipModel::run_recognition_packed(Workspace& ws, const std::vector<PackedGroup>& groups, const PackedPlan& plan, int h,
                                      StageTimers* timers, const uint8_t* d_excluded, int32_t* d_labels,
-                                     float** d_logp) const {
+                                     float** d_logp, float* d_maxlp) const {
     const int ts = packed_split();
     if (ts < 0) fail(OCRS_ERR_RUN_FAILED, "model run failed: graph is not <conv stack> TOSEQ GRU* LINEAR LOGSOFTMAX");
     hipStream_t st = ws.s();
@@ -1235,7 +1235,7 @@ int HipModel::run_recognition_packed(Workspace& ws, const std::vector<PackedGrou
             }
             timed(KC_LOGSOFTMAX_ARGMAX, 0, 4.0 * R * curC * (lp ? 2.0 : 1.0),
                   [&] {
-                      if (!k::log_softmax_argmax(cur, R, curC, d_excluded, lp, d_labels, st))
+                      if (!k::log_softmax_argmax(cur, R, curC, d_excluded, lp, d_labels, st, d_maxlp))
                           fail(OCRS_ERR_CAPACITY, "LogSoftmax over %d classes exceeds the kernel's LDS staging (max ~630)", curC);
                   });
             if (tok >= 0) timers->end(tok, st);

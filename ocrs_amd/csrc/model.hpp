@@ -117,9 +117,10 @@ struct HipModel : ModelBase {
     };
     // Writes arg-max labels of every packed row to d_labels [R]; returns class count.
     // d_logp (optional): receives the packed log-probabilities [R][classes] (model output, unmasked).
+    // d_maxlp (optional): [R] each row's masked maximum log-prob (the greedy step's).
     int run_recognition_packed(Workspace& ws, const std::vector<PackedGroup>& groups, const PackedPlan& plan, int h,
                                StageTimers* timers, const uint8_t* d_excluded, int32_t* d_labels,
-                               float** d_logp = nullptr) const;
+                               float** d_logp = nullptr, float* d_maxlp = nullptr) const;
     // Conv stack (ops [0, ts)) over all groups at once; writes packed feature rows.  Returns
     // nullptr if the stack has an op the ragged kernels do not cover.
     // Kernels are launched on `exec` (which may differ from ws.s(); the caller links the two with events).

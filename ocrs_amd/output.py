@@ -15,23 +15,30 @@ def rounded_vertex_coords(rect6):
     return [[_rround(x), _rround(y)] for x, y in rotated_rect_corners(rect6)]
 
 
-def ocr_json(input_path, input_hw, text_lines):
-    """output.rs:34-76.  text_lines: list of TextLine | None."""
+def ocr_json(input_path, input_hw, text_lines, confidence=False):
+    """output.rs:34-76.  text_lines: list of TextLine | None.  confidence (no reference counterpart): every line and word
+    object also gets "confidence" (TextLine / TextWord.confidence; the lines must come from a scored recognize_text)."""
     line_items = []
     for line in text_lines:
         if line is None:
             continue
-        words = [{"text": str(w), "vertices": rounded_vertex_coords(w.rotated_rect())} for w in line.words()]
+        words = []
+        for w in line.words():
+            words.append({"text": str(w), "vertices": rounded_vertex_coords(w.rotated_rect())})
+            if confidence:
+                words[-1]["confidence"] = w.confidence
         line_items.append({"text": str(line), "words": words, "vertices": rounded_vertex_coords(line.rotated_rect())})
+        if confidence:
+            line_items[-1]["confidence"] = line.confidence
     height, width = input_hw
     return {"url": input_path, "image_width": width, "image_height": height, "paragraphs": [{"lines": line_items}]}
 
 
-def format_json_output(input_path, input_hw, text_lines):
+def format_json_output(input_path, input_hw, text_lines, confidence=False):
     """output.rs:98-101 (serde_json::to_string_pretty).  serde_json without `preserve_order` keeps `json!` maps in a
     BTreeMap, so the reference emits every object's keys in alphabetical order (ocrs-cli/test-data/
     format-json-expected.json: image_height, image_width, paragraphs, url / text, vertices, words): sort_keys."""
-    return json.dumps(ocr_json(input_path, input_hw, text_lines), indent=2, ensure_ascii=False, sort_keys=True)
+    return json.dumps(ocr_json(input_path, input_hw, text_lines, confidence), indent=2, ensure_ascii=False, sort_keys=True)
 
 
 def format_text_output(text_lines):
