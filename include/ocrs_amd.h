@@ -393,6 +393,18 @@ OCRS_API ocrs_status ocrs_engine_recognize_logits(const ocrs_engine* e, const oc
                                          const size_t* line_offsets, size_t n_lines, float** logp, size_t** row_offsets,
                                          int* classes);
 
+/* Test hook: ops [first_op, last_op] of the recognition model (graph order, as in the model file) over n_lines lines of
+ * model-input widths line_widths[i] (the model's input height), through the engine's own packed path — its options,
+ * numerics, stream lease, ragged packing and launches.  `input`: op first_op's input, line after line in the per-line layout
+ * of the graph ([H][W][C] NHWC in the conv stack and at the TOSEQ, [T][1][C] after it), input_len floats in all.  *out: op
+ * last_op's output in the same layout, or with gx_only (last_op a GRU) that layer's input projections [2 directions][T][3H];
+ * *out_offsets [n_lines + 1] float offsets of the lines in *out, *out_shapes [n_lines][3] their dims.  A range that starts
+ * or ends inside a fused launch (conv1 + conv2 + pools, conv + pooled epilogue, average pool + TOSEQ) fails
+ * (OCRS_ERR_INVALID_ARGUMENT) with the launch's bounds in ocrs_last_error().  Outputs are malloc'ed (ocrs_buffer_free). */
+OCRS_API ocrs_status ocrs_engine_run_recognition_ops(const ocrs_engine* e, const int32_t* line_widths, size_t n_lines, int first_op,
+                                                     int last_op, int gx_only, const float* input, size_t input_len, float** out,
+                                                     size_t** out_offsets, int32_t** out_shapes);
+
 /* TextItem::rotated_rect (text_items.rs:18-30) for a TextLine / TextWord given its characters'
  * rects (n x {top,left,bottom,right}): minimum-area rectangle of the box corners, oriented
  * towards "up" (y = -1).  out6 = (center.x, center.y, up.x, up.y, width, height).  Host side. */

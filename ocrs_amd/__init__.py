@@ -601,6 +601,32 @@ class OcrEngine:
         lib().ocrs_buffer_free(roff)
         return out
 
+    def run_recognition_ops(self, widths, first_op, last_op, inputs, gx_only=False):
+        """Test hook (ocrs_engine_run_recognition_ops): recognition ops [first_op, last_op] through the engine's packed path
+        over lines of model-input widths `widths`.  inputs: op first_op's input per line, the oracle's slot without its
+        batch axis ([H, W, C] in the conv stack and at the TOSEQ, [T, 1, C] after it).  Returns op last_op's output per line
+        in the same layout ([2, T, 3H] with gx_only)."""
+        w = np.ascontiguousarray(widths, np.int32)
+        flat = np.ascontiguousarray(np.concatenate([np.asarray(a, np.float32).ravel() for a in inputs]), np.float32)
+        out = C.POINTER(C.c_float)()
+        offs = C.POINTER(C.c_size_t)()
+        shp = C.POINTER(C.c_int32)()
+        check(lib().ocrs_engine_run_recognition_ops(self._h, w.ctypes.data_as(C.POINTER(C.c_int32)), C.c_size_t(len(w)),
+                                                    int(first_op), int(last_op), int(bool(gx_only)),
+                                                    flat.ctypes.data_as(C.POINTER(C.c_float)), C.c_size_t(flat.size),
+                                                    C.byref(out), C.byref(offs), C.byref(shp)))
+        n = len(w)
+        res = []
+        for i in range(n):
+            a, b = offs[i], offs[i + 1]
+            d = (shp[3 * i], shp[3 * i + 1], shp[3 * i + 2])
+            v = np.ctypeslib.as_array(out, shape=(max(offs[n], 1),))[a:b].copy() if b > a else np.zeros(0, np.float32)
+            res.append(v.reshape(d))
+        lib().ocrs_buffer_free(out)
+        lib().ocrs_buffer_free(offs)
+        lib().ocrs_buffer_free(shp)
+        return res
+
     # ---- lib.rs:268-278
     def prepare_recognition_input(self, inp, line):
         a = _rects_to_array(line)

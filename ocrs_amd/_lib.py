@@ -73,6 +73,7 @@ DECLARED_SYMBOLS = [
     "ocrs_group_member_stats", "ocrs_numa_parse_cpulist", "ocrs_numa_bind_selftest", "ocrs_engine_recognize_logits", "ocrs_engine_set_option", "ocrs_engine_get_option", "ocrs_option_name", "ocrs_device_pool_stats", "ocrs_device_pool_configure", "ocrs_device_pool_trim",
     "ocrs_device_set_isolation", "ocrs_device_isolation", "ocrs_group_set_replay", "ocrs_abi_version",
     "ocrs_engine_recognize_text_scored", "ocrs_engine_recognize_text_batch_scored", "ocrs_ctc_beam_search_scored",
+    "ocrs_engine_run_recognition_ops",
 ]
 
 ABI_VERSION = 6   # include/ocrs_amd.h OCRS_ABI_VERSION

@@ -762,6 +762,23 @@ ocrs_status ocrs_engine_recognize_logits(const ocrs_engine* e, const ocrs_page* 
     });
 }
 
+ocrs_status ocrs_engine_run_recognition_ops(const ocrs_engine* e, const int32_t* line_widths, size_t n_lines, int first_op,
+                                            int last_op, int gx_only, const float* input, size_t input_len, float** out,
+                                            size_t** out_offsets, int32_t** out_shapes) {
+    return guarded_engine(e, [&] {
+        if (!e || !line_widths || !input || !out || !out_offsets || !out_shapes) fail(OCRS_ERR_INVALID_ARGUMENT, "null argument");
+        std::vector<float> flat;
+        std::vector<int32_t> shapes;
+        e->run_recognition_ops(line_widths, n_lines, first_op, last_op, gx_only != 0, input, input_len, &flat, &shapes);
+        std::vector<size_t> offs{0};
+        for (size_t i = 0; i < n_lines; i++)
+            offs.push_back(offs.back() + (size_t)shapes[3 * i] * shapes[3 * i + 1] * shapes[3 * i + 2]);
+        *out = dup_buffer(flat);
+        *out_offsets = dup_buffer(offs);
+        *out_shapes = dup_buffer(shapes);
+    });
+}
+
 ocrs_status ocrs_text_item_rotated_rect(const int32_t* rects_tlbr, size_t n_chars, float out6[6]) {
     return guarded([&] {
         if (!rects_tlbr || !out6 || n_chars == 0) fail(OCRS_ERR_INVALID_ARGUMENT, "expected valid rect");

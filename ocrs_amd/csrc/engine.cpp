@@ -534,6 +534,128 @@ void ocrs_engine::recognize_logits(const ocrs_page* page, const std::vector<std:
     *classes = (int)alphabet.size() + 1;
 }
 
+void ocrs_engine::run_recognition_ops(const int32_t* widths, size_t n, int first_op, int last_op, bool gx_only, const float* in,
+                                      size_t in_len, std::vector<float>* out, std::vector<int32_t>* shapes) const {
+    if (!recognition) fail(OCRS_ERR_MODEL_NOT_LOADED, "Recognition model not loaded");
+    if (recognition->is_callback()) fail(OCRS_ERR_INVALID_ARGUMENT, "run_recognition_ops needs a model of the fixed-graph executor");
+    const auto* hm = static_cast<const HipModel*>(recognition);
+    const int ts = hm->packed_split();
+    if (ts < 0) fail(OCRS_ERR_INVALID_ARGUMENT, "recognition graph is not <conv stack> TOSEQ GRU* LINEAR LOGSOFTMAX");
+    const int nops = (int)hm->ops.size();
+    if (n == 0) fail(OCRS_ERR_INVALID_ARGUMENT, "no lines");
+    if (first_op < 0 || first_op > last_op || last_op >= nops)
+        fail(OCRS_ERR_INVALID_ARGUMENT, "op range [%d, %d] is not inside the model's ops [0, %d]", first_op, last_op, nops - 1);
+    if (gx_only && hm->ops[last_op].type != OP_GRU) fail(OCRS_ERR_INVALID_ARGUMENT, "gx_only: op %d is not a GRU", last_op);
+    const int h = (int)rec_input_height();
+    const int in_slot = hm->ops[first_op].in0, out_slot = hm->ops[last_op].out, seq_slot = hm->ops[ts].out;
+    std::vector<std::vector<TensorShape>> shp(n);
+    std::vector<int> T(n);
+    for (size_t i = 0; i < n; i++) {
+        if (widths[i] < 1) fail(OCRS_ERR_INVALID_ARGUMENT, "line %zu: width %d", i, widths[i]);
+        hm->infer(1, h, widths[i], &shp[i]);
+        T[i] = shp[i][seq_slot].n;
+        if (T[i] <= 0) fail(OCRS_ERR_INVALID_ARGUMENT, "line %zu: width %d gives no sequence", i, widths[i]);
+    }
+    // lines by width (the width groups of the ragged batch), then by sequence length (rows off[t] + m, as recognize_lines)
+    std::map<int32_t, std::vector<size_t>> by_w;
+    for (size_t i = 0; i < n; i++) by_w[widths[i]].push_back(i);
+    std::vector<size_t> order;   // line order of the ragged layout
+    for (auto& kv : by_w) order.insert(order.end(), kv.second.begin(), kv.second.end());
+    Workspace ws;
+    HipModel::PackedPlan plan;
+    uint32_t status[8] = {0};
+    plan.h_status = status;
+    std::vector<int32_t> layout_T;
+    for (size_t i : order) layout_T.push_back(T[i]);
+    std::vector<size_t> slot_layout;
+    const int32_t* d_pos = HipModel::make_packed_plan(ws, layout_T, &plan, &slot_layout);
+    std::vector<int32_t> slot_of(n);   // line i's row slot m
+    for (int m = 0; m < plan.M; m++) slot_of[order[slot_layout[m]]] = m;
+    const std::vector<int32_t>& hoff = plan.h_off;
+
+    // op first_op's input in the layout of the packed path
+    const bool seq_in = first_op > ts;
+    const int in_c = shp[0][in_slot].c;
+    std::vector<float> packed;
+    std::vector<size_t> line_at(n);   // offset of each line's input in `in`
+    {
+        size_t acc = 0;
+        for (size_t i = 0; i < n; i++) {
+            if (shp[i][in_slot].c != in_c) fail(OCRS_ERR_INVALID_ARGUMENT, "op %d: input channels differ between lines", first_op);
+            line_at[i] = acc;
+            acc += (size_t)shp[i][in_slot].count();
+        }
+        if (acc != in_len) fail(OCRS_ERR_INVALID_ARGUMENT, "input has %zu floats, op %d of these lines reads %zu", in_len, first_op, acc);
+    }
+    if (seq_in) {
+        packed.resize((size_t)plan.R * in_c);
+        for (size_t i = 0; i < n; i++)
+            for (int t = 0; t < T[i]; t++)
+                std::copy_n(in + line_at[i] + (size_t)t * in_c, in_c, &packed[((size_t)hoff[t] + slot_of[i]) * in_c]);
+    } else {
+        for (size_t i : order) packed.insert(packed.end(), in + line_at[i], in + line_at[i] + shp[i][in_slot].count());
+    }
+
+    float* d_in = ws.alloc_n<float>(std::max<size_t>(packed.size(), 1));
+    ws.upload(d_in, packed.data(), packed.size() * sizeof(float));
+    std::vector<HipModel::PackedGroup> pg;
+    {
+        size_t at = 0, pos = 0;
+        for (auto& kv : by_w) {
+            const size_t ng = kv.second.size();
+            pg.push_back(HipModel::PackedGroup{d_in + (seq_in ? 0 : at), (int)ng, (int)kv.first, d_pos + pos});
+            for (size_t i : kv.second) at += (size_t)shp[i][in_slot].count();
+            pos += ng;
+        }
+    }
+    int32_t* d_labels = ws.alloc_n<int32_t>((size_t)plan.R);
+    HipModel::OpRange r;
+    r.first = first_op;
+    r.last = last_op;
+    r.gx_only = gx_only;
+    r.seq_in = seq_in ? d_in : nullptr;
+    r.in_c = in_c;
+    hm->run_recognition_packed(ws, pg, plan, h, nullptr, nullptr, d_labels, nullptr, nullptr, &r);
+
+    // op last_op's output, back in line order
+    const bool seq_out = last_op >= ts;
+    const int oc = r.out_c;
+    std::vector<float> host;
+    if (seq_out) {
+        host.resize((size_t)(gx_only ? 2 : 1) * plan.R * oc);
+    } else {
+        size_t total = 0;
+        for (size_t i = 0; i < n; i++) total += (size_t)shp[i][out_slot].count();
+        host.resize(total);
+    }
+    ws.download(host.data(), r.out, host.size() * sizeof(float));
+    ws.sync();
+    for (uint32_t st8 : status)
+        if (st8) fail(OCRS_ERR_DEVICE, "GRU recurrence kernel timed out waiting for a peer workgroup (status 0x%x)", st8);
+    out->clear();
+    shapes->clear();
+    if (seq_out) {
+        for (size_t i = 0; i < n; i++) {
+            for (int d = 0; d < (gx_only ? 2 : 1); d++)
+                for (int t = 0; t < T[i]; t++) {
+                    const float* row = &host[((size_t)d * plan.R + hoff[t] + slot_of[i]) * oc];
+                    out->insert(out->end(), row, row + oc);
+                }
+            shapes->insert(shapes->end(), gx_only ? std::initializer_list<int32_t>{2, T[i], oc} : std::initializer_list<int32_t>{T[i], 1, oc});
+        }
+    } else {
+        std::vector<size_t> at(n);
+        size_t acc = 0;
+        for (size_t i : order) { at[i] = acc; acc += (size_t)shp[i][out_slot].count(); }
+        for (size_t i = 0; i < n; i++) {
+            const TensorShape& s = shp[i][out_slot];
+            if (s.c != oc) fail(OCRS_ERR_RUN_FAILED, "op %d: %d output channels, the model says %d", last_op, oc, s.c);
+            out->insert(out->end(), host.begin() + at[i], host.begin() + at[i] + s.count());
+            shapes->insert(shapes->end(), {s.h, s.w, s.c});
+        }
+    }
+}
+
 void ocrs_engine::recognize_lines(const ocrs_page* const* pages, size_t n_pages, const std::vector<RecLine>& lines,
                                   std::vector<std::vector<CtcStep>>* steps_out, std::vector<uint32_t>* ctc_len_out,
                                   std::vector<std::vector<float>>* logp_out, RecScores* scores) const {
@@ -752,45 +874,29 @@ void ocrs_engine::recognize_lines(const ocrs_page* const* pages, size_t n_pages,
 
         auto launch = [&](size_t c0, size_t c1, Workspace& w, Sub& sub) {
             hipStream_t sst = w.s();
-            for (size_t c = c0; c < c1; c++)
-                for (size_t j = 0; j < chunks[c].members.size(); j++)
-                    if (chunk_T[c] > 0) sub.slots.push_back(Slot{chunk_T[c], chunks[c].members[j], c, j});
-            std::stable_sort(sub.slots.begin(), sub.slots.end(), [](const Slot& x, const Slot& y) { return x.T > y.T; });
-            const int M = (int)sub.slots.size();
-            if (M == 0) return;
+            std::vector<int32_t> lineT;                      // the lines of chunks c0 .. c1 in chunk order
+            std::vector<std::pair<size_t, size_t>> at;       // (chunk, member)
+            std::vector<size_t> pos_at(c1 - c0);             // index of each chunk's first line
+            for (size_t c = c0; c < c1; c++) {
+                pos_at[c - c0] = lineT.size();
+                for (size_t j = 0; j < chunks[c].members.size(); j++) {
+                    lineT.push_back(chunk_T[c]);
+                    at.emplace_back(c, j);
+                }
+            }
             HipModel::PackedPlan plan;
             plan.h_status = sub.gru_status;
-            plan.M = M;
-            plan.Tmax = sub.slots[0].T;
-            plan.active.assign(plan.Tmax, 0);
-            std::vector<int32_t> hTm(M), hoff(plan.Tmax + 1, 0);
-            std::vector<std::vector<int32_t>> hpos(c1 - c0);
-            for (size_t c = c0; c < c1; c++) hpos[c - c0].assign(chunks[c].members.size(), 0);
-            for (int m = 0; m < M; m++) {
-                hTm[m] = sub.slots[m].T;
-                hpos[sub.slots[m].chunk - c0][sub.slots[m].j] = m;
-                for (int t = 0; t < sub.slots[m].T; t++) plan.active[t]++;
-            }
-            for (int t = 0; t < plan.Tmax; t++) hoff[t + 1] = hoff[t] + plan.active[t];
-            plan.R = hoff[plan.Tmax];
-            std::vector<int32_t> meta;  // Tm | off | pos of every chunk (contiguous, chunk order)
-            meta.insert(meta.end(), hTm.begin(), hTm.end());
-            meta.insert(meta.end(), hoff.begin(), hoff.end());
-            std::vector<size_t> pos_at(c1 - c0);
-            for (size_t c = c0; c < c1; c++) {
-                pos_at[c - c0] = meta.size();
-                meta.insert(meta.end(), hpos[c - c0].begin(), hpos[c - c0].end());
-            }
-            int32_t* d_meta = w.alloc_n<int32_t>(meta.size());
-            w.upload(d_meta, meta.data(), meta.size() * sizeof(int32_t));
-            plan.d_Tm = d_meta;
-            plan.h_Tm = hTm;
-            plan.d_off = d_meta + M;
+            std::vector<size_t> order;
+            const int32_t* d_pos = HipModel::make_packed_plan(w, lineT, &plan, &order);
+            if (!d_pos) return;
+            for (size_t i : order)
+                sub.slots.push_back(Slot{lineT[i], chunks[at[i].first].members[at[i].second], at[i].first, at[i].second});
+            const int M = plan.M;
             std::vector<HipModel::PackedGroup> pg;
             for (size_t c = c0; c < c1; c++)
                 if (chunk_T[c] > 0)
                     pg.push_back(HipModel::PackedGroup{chunk_ptr(chunks[c]), (int)chunks[c].members.size(), (int)chunks[c].gw,
-                                                       d_meta + pos_at[c - c0]});
+                                                       d_pos + pos_at[c - c0]});
             int32_t* d_labels = w.alloc_n<int32_t>((size_t)plan.R);
             float* d_logp = nullptr;
             float* d_maxlp = (scores && !beam) ? w.alloc_n<float>((size_t)plan.R) : nullptr;
@@ -798,7 +904,7 @@ void ocrs_engine::recognize_lines(const ocrs_page* const* pages, size_t n_pages,
                                        d_maxlp);
             if (logp_out) {
                 sub.logp.resize((size_t)plan.R * C);
-                sub.off = hoff;
+                sub.off = plan.h_off;
                 w.download(sub.logp.data(), d_logp, sub.logp.size() * sizeof(float), sst);
             }
             if (beam && option(OPT_BEAM_GPU) && k::ctc_beam_supported(C, (int)beam_width)) {
@@ -837,7 +943,7 @@ void ocrs_engine::recognize_lines(const ocrs_page* const* pages, size_t n_pages,
                 sub.Tmax = plan.Tmax;
                 if (!logp_out) {
                     sub.logp.resize((size_t)plan.R * C);
-                    sub.off = hoff;
+                    sub.off = plan.h_off;
                     w.download(sub.logp.data(), d_logp, sub.logp.size() * sizeof(float), sst);
                 }
                 return;

@@ -136,6 +136,12 @@ struct ocrs_engine {
     // sub-requests within the activation budget as `recognize` is
     void recognize_logits(const ocrs_page* page, const std::vector<std::vector<ocrs::geom::RotatedRect>>& lines,
                           std::vector<std::vector<float>>* logp, int* classes) const;
+    // test hook (ocrs_engine_run_recognition_ops): ops [first_op, last_op] of the recognition model through
+    // run_recognition_packed, over lines of model-input widths `widths`.  `in`: op first_op's input, line after line in the
+    // oracle's per-line layout ([H][W][C] in the conv stack and at the TOSEQ, [T][1][C] after it); `out` likewise for op
+    // last_op's output ([2][T][3H]: gx_only, a GRU's input projections), `shapes` three dims per line.
+    void run_recognition_ops(const int32_t* widths, size_t n, int first_op, int last_op, bool gx_only, const float* in,
+                             size_t in_len, std::vector<float>* out, std::vector<int32_t>* shapes) const;
 
     // step_logp (optional, indexed like steps): char_logp receives the log-prob of every char's step, aligned with the result
     std::vector<ocrs::TextChar> text_line_from_result(const ocrs::RecLine& line, uint32_t ctc_input_len,

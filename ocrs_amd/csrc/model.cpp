@@ -742,7 +742,7 @@ float* HipModel::run_device(Workspace& ws, const float* d_in, int n, int h, int 
 // ---------------------------------------------------------------------------
 float* HipModel::run_prefix_ragged(Workspace& ws, hipStream_t exec, const std::vector<PackedGroup>& groups,
                                    const PackedPlan& plan, int h, int ts, StageTimers* timers, int* feat_c,
-                                   const std::function<void()>& before_launch) const {
+                                   const std::function<void()>& before_launch, const OpRange* range) const {
     // supported stack: CONV 3x3 (Cin == 1 directly followed by MAXPOOL 2x2, or Cin % 32 == 0), MAXPOOL, AVGPOOL,
     // each consuming the previous op's output
     const int G = (int)groups.size();
@@ -769,7 +769,8 @@ float* HipModel::run_prefix_ragged(Workspace& ws, hipStream_t exec, const std::v
             if (ops[i].type == OP_MAXPOOL || ops[i].type == OP_AVGPOOL) hh /= ops[i].kh;
         }
     }
-    for (int g = 0; g + 1 < G; g++)  // groups must be contiguous in memory
+    // groups must be contiguous in memory (an op range that starts later hands in one ragged buffer: groups[0].d_batch)
+    for (int g = 0; g + 1 < G && !(range && range->first > 0); g++)
         if (groups[g].d_batch + (size_t)groups[g].n * h * groups[g].w != groups[g + 1].d_batch) return nullptr;
 
     hipStream_t st = exec;
@@ -935,40 +936,56 @@ float* HipModel::run_prefix_ragged(Workspace& ws, hipStream_t exec, const std::v
         return arena[best].as<float>();
     };
     size_t prev_bytes = 0;
+    // an op range (test hook): the launches before it are planned, not run, and none may straddle either end of it
+    const int first = range ? range->first : 0, last = range ? range->last : ts;
+    auto launches = [&](int i, int j) {   // the launch of ops [i, j] runs?
+        if (i < first && j >= first)
+            fail(OCRS_ERR_INVALID_ARGUMENT, "op range: op %d lies inside the fused launch of ops %d..%d (a range starts at %d)", first, i, j, i);
+        if (i <= last && j > last)
+            fail(OCRS_ERR_INVALID_ARGUMENT, "op range: op %d lies inside the fused launch of ops %d..%d (a range ends at %d)", last, i, j, j);
+        return i >= first;
+    };
+    int at = ts;   // the op at which the stack loop stopped (ts: all of it ran)
     for (int i = 0; i < ts; i++) {
         const GraphOp& op = ops[i];
         const k::RaggedView vin = view(i);
         float* y = nullptr;
         size_t ybytes = 0;
+        bool run = false;
         // conv1 + pool + conv2 + pool in one kernel where the shapes allow (kernels_rec.hip: conv12_fused_ragged)
         if (op.type == OP_CONV && op.cin == 1 && i + 3 < ts && ops[i + 2].type == OP_CONV && ops[i + 2].cin == op.cout &&
             ops[i + 2].relu && ops[i + 3].type == OP_MAXPOOL && ops[i + 3].kh == 2 && ops[i + 3].kw == 2) {
             const GraphOp& op2 = ops[i + 2];
             const k::RaggedView vmid = view(i + 2), vout = view(i + 4);
             bool ok = k::conv12_fused_ragged(nullptr, vin, vmid, nullptr, nullptr, op.cout, nullptr, nullptr, op2.cout, nullptr, vout, st);
-            float* y2 = ok ? get((size_t)vout.pixels * op2.cout) : nullptr;
-            if (ok) {
+            if (ok && launches(i, i + 3)) {
+                float* y2 = get((size_t)vout.pixels * op2.cout);
                 // counted as conv2's launch with conv2's FLOPs (the matrix-core work); conv1's VALU work rides along
                 timed(KC_GEMM_CONV3X3, 2.0 * vmid.pixels * 9.0 * op2.cin * op2.cout,
                       4.0 * (vin.pixels + vout.pixels * op2.cout) + 4.0 * op2.wcount[0],
                       [&] { k::conv12_fused_ragged(cur, vin, vmid, op.w[0], op.w[1], op.cout, op2.w[0], op2.w[1], op2.cout, y2, vout, st, op2.wsplit); });
                 y = y2;
                 ybytes = (size_t)vout.pixels * op2.cout * sizeof(float);
-                curC = op2.cout;
-                i += 3;
                 if (prev_buf) spare.emplace_back(prev_buf, prev_bytes);
                 prev_buf = y;
                 prev_bytes = ybytes;
                 cur = y;
+            }
+            if (ok) {
+                curC = op2.cout;
+                i += 3;
+                if (i >= last) { at = i; break; }
                 continue;
             }
         }
         if (op.type == OP_CONV && op.cin == 1) {
             const k::RaggedView vout = view(i + 2);  // after the fused MaxPool 2x2
-            ybytes = (size_t)vout.pixels * op.cout * sizeof(float);
-            y = get((size_t)vout.pixels * op.cout);
-            timed(KC_CONV_DIRECT, 2.0 * vin.pixels * 9 * op.cout, 4.0 * vin.pixels + 4.0 * vout.pixels * op.cout,
-                  [&] { k::conv1_relu_pool_ragged(cur, vin, op.w[0], op.w[1], op.cout, y, vout, st); });
+            if ((run = launches(i, i + 1))) {
+                ybytes = (size_t)vout.pixels * op.cout * sizeof(float);
+                y = get((size_t)vout.pixels * op.cout);
+                timed(KC_CONV_DIRECT, 2.0 * vin.pixels * 9 * op.cout, 4.0 * vin.pixels + 4.0 * vout.pixels * op.cout,
+                      [&] { k::conv1_relu_pool_ragged(cur, vin, op.w[0], op.w[1], op.cout, y, vout, st); });
+            }
             curC = op.cout;
             i += 1;  // the pool is fused
         } else if (op.type == OP_CONV) {
@@ -977,41 +994,55 @@ float* HipModel::run_prefix_ragged(Workspace& ws, hipStream_t exec, const std::v
                               (ops[i + 1].kw == 1 || ops[i + 1].kw == 2) && vin.H % 2 == 0;
             const int ph = fuse ? 2 : 1, pw = fuse ? ops[i + 1].kw : 1;
             const k::RaggedView vout = view(fuse ? i + 2 : i + 1);
-            ybytes = (size_t)vout.pixels * op.cout * sizeof(float);
-            y = get((size_t)vout.pixels * op.cout);
-            bool ok = false;
-            timed(KC_GEMM_CONV3X3, 2.0 * vin.pixels * 9.0 * op.cin * op.cout,
-                  4.0 * (vin.pixels * op.cin + vout.pixels * op.cout) + 4.0 * op.wcount[0],
-                  [&] { ok = k::conv3x3_ragged(cur, vin, op.cin, op.w[0], op.w[1], op.cout, op.relu, ph, pw, y, vout, st, op.wsplit); });
-            if (!ok) fail(OCRS_ERR_RUN_FAILED, "model run failed: ragged conv %d->%d at height %d not supported", op.cin, op.cout, vin.H);
+            if ((run = launches(i, fuse ? i + 1 : i))) {
+                ybytes = (size_t)vout.pixels * op.cout * sizeof(float);
+                y = get((size_t)vout.pixels * op.cout);
+                bool ok = false;
+                timed(KC_GEMM_CONV3X3, 2.0 * vin.pixels * 9.0 * op.cin * op.cout,
+                      4.0 * (vin.pixels * op.cin + vout.pixels * op.cout) + 4.0 * op.wcount[0],
+                      [&] { ok = k::conv3x3_ragged(cur, vin, op.cin, op.w[0], op.w[1], op.cout, op.relu, ph, pw, y, vout, st, op.wsplit); });
+                if (!ok) fail(OCRS_ERR_RUN_FAILED, "model run failed: ragged conv %d->%d at height %d not supported", op.cin, op.cout, vin.H);
+            }
             curC = op.cout;
             if (fuse) i += 1;
         } else if (op.type == OP_AVGPOOL && i + 1 == ts && op.kw == 1 && op.kh == vin.H && (curC & 3) == 0) {
+            launches(i, ts);
             break;   // the column average down to height 1 that ends the stack: done together with the sequence packing below
-        } else {
+        } else if ((run = launches(i, i))) {
             const k::RaggedView vout = view(i + 1);
             ybytes = (size_t)vout.pixels * curC * sizeof(float);
             y = get((size_t)vout.pixels * curC);
             timed(KC_POOL, 0, 4.0 * curC * (vin.pixels + vout.pixels),
                   [&] { k::pool_ragged(cur, vin, curC, op.kh, op.kw, op.type == OP_AVGPOOL, y, vout, st); });
         }
-        if (prev_buf) spare.emplace_back(prev_buf, prev_bytes);
-        prev_buf = y;
-        prev_bytes = ybytes;
-        cur = y;
+        if (run) {
+            if (prev_buf) spare.emplace_back(prev_buf, prev_bytes);
+            prev_buf = y;
+            prev_bytes = ybytes;
+            cur = y;
+        }
+        if (i >= last) { at = i; break; }
     }
-    const k::RaggedView vf = view(ts);
-    if (vf.H != 1) fail(OCRS_ERR_RUN_FAILED, "model run failed: TOSEQ expects height 1, got %d", vf.H);
-    float* X = ws.alloc_n<float>((size_t)plan.R * curC);
-    const bool pool_here = ts >= 1 && ops[ts - 1].type == OP_AVGPOOL && ops[ts - 1].kw == 1 && (curC & 3) == 0 &&
-                           ops[ts - 1].kh == view(ts - 1).H;
-    if (pool_here) {
-        const k::RaggedView vp = view(ts - 1);
-        timed(KC_POOL, 0, 4.0 * curC * (vp.pixels + vf.pixels),
-              [&] { k::avgpool_to_seq_ragged(cur, vp, vf, curC, groups[0].d_pos, plan.d_off, X, st); });
+    float* X = nullptr;
+    if (at < ts) {
+        // the range ends inside the stack: its output, out of the (possibly shared) arena into the request's own workspace
+        X = ws.alloc_n<float>(prev_bytes / sizeof(float));
+        OCRS_HIP(hipMemcpyAsync(X, prev_buf, prev_bytes, hipMemcpyDeviceToDevice, st));
     } else {
-        timed(KC_OTHER, 0, 8.0 * vf.pixels * curC,
-              [&] { k::to_seq_packed_ragged(cur, vf, curC, groups[0].d_pos, plan.d_off, X, st); });
+        const k::RaggedView vf = view(ts);
+        if (vf.H != 1) fail(OCRS_ERR_RUN_FAILED, "model run failed: TOSEQ expects height 1, got %d", vf.H);
+        X = ws.alloc_n<float>((size_t)plan.R * curC);
+        const bool pool_here = ts >= 1 && ops[ts - 1].type == OP_AVGPOOL && ops[ts - 1].kw == 1 && (curC & 3) == 0 &&
+                               ops[ts - 1].kh == view(ts - 1).H;
+        if (pool_here) {
+            const k::RaggedView vp = view(ts - 1);
+            timed(KC_POOL, 0, 4.0 * curC * (vp.pixels + vf.pixels),
+                  [&] { k::avgpool_to_seq_ragged(cur, vp, vf, curC, groups[0].d_pos, plan.d_off, X, st); });
+        } else {
+            launches(ts, ts);
+            timed(KC_OTHER, 0, 8.0 * vf.pixels * curC,
+                  [&] { k::to_seq_packed_ragged(cur, vf, curC, groups[0].d_pos, plan.d_off, X, st); });
+        }
     }
     if (tok >= 0) timers->end(tok, st);
     if (exec != ws.s()) {  // the request's stream continues once the conv stack has drained
@@ -1021,6 +1052,37 @@ float* HipModel::run_prefix_ragged(Workspace& ws, hipStream_t exec, const std::v
     }
     *feat_c = curC;
     return X;
+}
+
+const int32_t* HipModel::make_packed_plan(Workspace& ws, const std::vector<int32_t>& T, PackedPlan* plan,
+                                          std::vector<size_t>* order) {
+    order->clear();
+    for (size_t i = 0; i < T.size(); i++)
+        if (T[i] > 0) order->push_back(i);
+    std::stable_sort(order->begin(), order->end(), [&](size_t a, size_t b) { return T[a] > T[b]; });
+    const int M = (int)order->size();
+    if (M == 0) return nullptr;
+    plan->M = M;
+    plan->Tmax = T[(*order)[0]];
+    plan->active.assign(plan->Tmax, 0);
+    std::vector<int32_t> hTm(M), hoff(plan->Tmax + 1, 0), hpos(T.size(), 0);
+    for (int m = 0; m < M; m++) {
+        hTm[m] = T[(*order)[m]];
+        hpos[(*order)[m]] = m;
+        for (int t = 0; t < hTm[m]; t++) plan->active[t]++;
+    }
+    for (int t = 0; t < plan->Tmax; t++) hoff[t + 1] = hoff[t] + plan->active[t];
+    plan->R = hoff[plan->Tmax];
+    std::vector<int32_t> meta(hTm);   // Tm | off | pos
+    meta.insert(meta.end(), hoff.begin(), hoff.end());
+    meta.insert(meta.end(), hpos.begin(), hpos.end());
+    int32_t* d_meta = ws.alloc_n<int32_t>(meta.size());
+    ws.upload(d_meta, meta.data(), meta.size() * sizeof(int32_t));
+    plan->d_Tm = d_meta;
+    plan->d_off = d_meta + M;
+    plan->h_Tm = std::move(hTm);
+    plan->h_off = std::move(hoff);
+    return d_meta + M + plan->Tmax + 1;
 }
 
 int HipModel::packed_split() const {
@@ -1046,9 +1108,10 @@ int HipModel::packed_split() const {
 
 int HipModel::run_recognition_packed(Workspace& ws, const std::vector<PackedGroup>& groups, const PackedPlan& plan, int h,
                                      StageTimers* timers, const uint8_t* d_excluded, int32_t* d_labels,
-                                     float** d_logp, float* d_maxlp) const {
+                                     float** d_logp, float* d_maxlp, OpRange* range) const {
     const int ts = packed_split();
     if (ts < 0) fail(OCRS_ERR_RUN_FAILED, "model run failed: graph is not <conv stack> TOSEQ GRU* LINEAR LOGSOFTMAX");
+    const int first = range ? range->first : 0, last = range ? range->last : (int)ops.size() - 1;
     hipStream_t st = ws.s();
     auto timed = [&](int cls, double flops, double bytes, auto&& launch) {
         int tok = timers ? timers->kbegin(cls, st, flops, bytes) : -1;
@@ -1067,13 +1130,13 @@ int HipModel::run_recognition_packed(Workspace& ws, const std::vector<PackedGrou
     // to the request's own stream by events) and everything after it overlaps freely.
     float* X = nullptr;
     int C0 = 0;
-    {
+    if (first <= ts) {
         // all conv stacks of a device go through ONE stream, in request order.  The lock is taken by the hook, i.e. after
         // the request's geometry has been worked out and its metadata uploads are queued.
         std::unique_lock<std::mutex> heavy(ctx().heavy_phase, std::defer_lock);
         const hipStream_t conv = ws.stream.conv_stream();   // the device's conv-stack stream
         try {
-            X = run_prefix_ragged(ws, conv, groups, plan, h, ts, timers, &C0, [&] { heavy.lock(); });
+            X = run_prefix_ragged(ws, conv, groups, plan, h, ts, timers, &C0, [&] { heavy.lock(); }, range);
         } catch (...) {
             // Kernels of this request may already be queued on the shared stream, reading and writing scratch
             // that ~Workspace hands back to the pool after draining only the request's OWN stream: make that
@@ -1089,7 +1152,15 @@ int HipModel::run_recognition_packed(Workspace& ws, const std::vector<PackedGrou
             throw;
         }
     }
-    if (!X)
+    if (range && first <= ts) {
+        if (!X) fail(OCRS_ERR_INVALID_ARGUMENT, "op range: this model's conv stack has no ragged form");
+        if (last < ts) {
+            range->out = X;
+            range->out_c = C0;
+            return 0;
+        }
+    }
+    if (!X && first <= ts)
     for (const PackedGroup& g : groups) {
         TensorShape fs;
         float* feat = run_device(ws, g.d_batch, g.n, h, g.w, &fs, timers, nullptr, nullptr, true, false, ts);
@@ -1102,17 +1173,17 @@ int HipModel::run_recognition_packed(Workspace& ws, const std::vector<PackedGrou
         timed(KC_OTHER, 0, 8.0 * fs.count(), [&] { k::to_seq_packed(feat, g.n, fs.w, fs.c, g.d_pos, plan.d_off, X, st); });
         if (tok >= 0) timers->end(tok, st);
     }
-    if (!X) return 0;
+    if (!X && first <= ts) return 0;
 
-    const float* cur = X;
-    int curC = C0;
+    const float* cur = first <= ts ? X : range->seq_in;
+    int curC = first <= ts ? C0 : range->in_c;
     int classes = 0;
     int gru_layer = 0;
     float* gx_buf = nullptr;
     size_t gx_cap = 0;
     void* hx_buf = nullptr;   // the recurrences' hand-off buffer: likewise one for all layers (a layer's marks are written after the
     size_t hx_cap = 0;        // previous layer's recurrence has finished: this stream waits for it)
-    for (size_t i = ts + 1; i < ops.size(); i++) {
+    for (int i = std::max(ts + 1, first); i <= last; i++) {
         const GraphOp& op = ops[i];
         if (op.type == OP_GRU) {
             const int H = op.hidden, I = op.cin;
@@ -1145,6 +1216,11 @@ int HipModel::run_recognition_packed(Workspace& ws, const std::vector<PackedGrou
             // (round 3's option gx_heavy queued these projections on the conv-stack stream: every MFMA class then ran at its
             // alone speed at the same or slightly lower pages/s — a zero-sum trade, removed in round 5)
             timed(KC_GEMM_GRU_INPUT, gx_flops, gx_bytes, [&] { k::gemm(d, st); });
+            if (range && range->gx_only && i == last) {
+                range->out = gx;
+                range->out_c = 3 * H;
+                return 0;
+            }
             bool ran_persistent = false;
             if (persistent) {
                 // ONE launch for all Tmax steps of both directions (kernels_gru.hip).  Its workgroups wait on
@@ -1229,9 +1305,9 @@ int HipModel::run_recognition_packed(Workspace& ws, const std::vector<PackedGrou
         } else {  // LOGSOFTMAX (+ arg-max)
             int tok = timers ? timers->begin(ST_REC_HEAD, st, 0) : -1;
             float* lp = nullptr;
-            if (d_logp) {
+            if (d_logp || range) {
                 lp = ws.alloc_n<float>((size_t)R * curC);
-                *d_logp = lp;
+                if (d_logp) *d_logp = lp;
             }
             timed(KC_LOGSOFTMAX_ARGMAX, 0, 4.0 * R * curC * (lp ? 2.0 : 1.0),
                   [&] {
@@ -1240,7 +1316,12 @@ int HipModel::run_recognition_packed(Workspace& ws, const std::vector<PackedGrou
                   });
             if (tok >= 0) timers->end(tok, st);
             classes = curC;
+            if (range) cur = lp;
         }
+    }
+    if (range) {
+        range->out = cur;
+        range->out_c = curC;
     }
     OCRS_HIP(hipGetLastError());
     return classes;

@@ -112,23 +112,44 @@ struct HipModel : ModelBase {
         const int32_t* d_off = nullptr;  // [Tmax + 1]
         std::vector<int> active;         // [Tmax] host
         std::vector<int32_t> h_Tm;       // [M] host copy of d_Tm
+        std::vector<int32_t> h_off;      // [Tmax + 1] host copy of d_off
         uint32_t* h_status = nullptr;    // host [8]: slot i receives the time-out word of the i-th GRU layer's
                                          // persistent kernel after the workspace's next sync (0 = fine)
     };
+    // A range of ops [first, last] of the packed path (the test hook ocrs_engine_run_recognition_ops; production runs every
+    // op and passes none).  Op `first`'s input is the groups' d_batch in the ragged layout of its geometry when it lies in the
+    // conv stack or is the TOSEQ, else `seq_in`: packed rows [R][in_c].  The run leaves op `last`'s output in `out`: ragged
+    // [pixels][out_c] inside the stack, packed rows [R][out_c] after it, or, with gx_only at a GRU, that layer's input
+    // projections [2][R][3H].  A range that starts or ends inside a fused launch is refused.
+    struct OpRange {
+        int first = 0, last = 0;
+        bool gx_only = false;
+        const float* seq_in = nullptr;
+        int in_c = 0;
+        const float* out = nullptr;
+        int out_c = 0;
+    };
+    // The packed plan of a request's lines, given their sequence lengths T in the order of the ragged layout (group after
+    // group; T = 0: a line without rows): rows off[t] + m with the lines sorted by T descending (ties in layout order), and its
+    // metadata Tm [M] | off [Tmax + 1] | pos [lines] (pos[i]: line i's m, 0 without rows) uploaded to `ws` in one blob.
+    // order[m] = the layout index of the line in slot m.  Returns the device pos array, or nullptr if no line has rows.
+    static const int32_t* make_packed_plan(Workspace& ws, const std::vector<int32_t>& T, PackedPlan* plan, std::vector<size_t>* order);
     // Writes arg-max labels of every packed row to d_labels [R]; returns class count.
     // d_logp (optional): receives the packed log-probabilities [R][classes] (model output, unmasked).
     // d_maxlp (optional): [R] each row's masked maximum log-prob (the greedy step's).
     int run_recognition_packed(Workspace& ws, const std::vector<PackedGroup>& groups, const PackedPlan& plan, int h,
                                StageTimers* timers, const uint8_t* d_excluded, int32_t* d_labels,
-                               float** d_logp = nullptr, float* d_maxlp = nullptr) const;
+                               float** d_logp = nullptr, float* d_maxlp = nullptr, OpRange* range = nullptr) const;
     // Conv stack (ops [0, ts)) over all groups at once; writes packed feature rows.  Returns
     // nullptr if the stack has an op the ragged kernels do not cover.
     // Kernels are launched on `exec` (which may differ from ws.s(); the caller links the two with events).
     // before_launch: called once after the host-side planning and the metadata uploads, before the first launch on `exec`
     // (the caller takes the shared stream's lock there).
+    // range: launches only ops [range->first, range->last] (range->last < ts: returns that op's output, ragged, in a buffer
+    // of `ws`); the ops before it are planned, not run.
     float* run_prefix_ragged(Workspace& ws, hipStream_t exec, const std::vector<PackedGroup>& groups,
                              const PackedPlan& plan, int h, int ts, StageTimers* timers, int* feat_c,
-                             const std::function<void()>& before_launch = nullptr) const;
+                             const std::function<void()>& before_launch = nullptr, const OpRange* range = nullptr) const;
 };
 
 }  // namespace ocrs

@@ -194,8 +194,74 @@ def log_softmax(x):
     return y, np.broadcast_to(bound, y.shape).copy()
 
 
+# ---------------------------------------------------------------- relaxed / reduced numerics
+# A bf16-split contraction (split_mfma.hpp, kernels_gru_split.hip) cuts both operands of every product into NP bf16 planes by
+# round-to-nearest of the running residual, x = hi + mid + lo, and sums the kept plane products in fp32 in the matrix core's
+# order.  Per product a w:
+#   * the dropped plane products are at most SPLIT_DROP[NP] |a w| (NP 3 keeps hh hm mh mm hl lh: <= 2^-23; NP 2 keeps hh hm mh:
+#     <= 1.5 * 2^-15), and the kept ones add up, in magnitude, to at most (1 + 2^-9 + 2^-8 + 2^-16)^2 |a w| < SPLIT_MAG |a w|
+#     (|hi| <= (1 + 2^-9) |x|, |mid| <= 2^-8 |x|, |lo| <= 2^-16 |x|);
+#   * each kept plane product is exact in fp32 (8 x 8 significant bits);
+#   * the bias and the SPLIT_TERMS[NP] K partial products are summed in an unspecified order: any order of n additions
+#     rounds at most n times, so the sum is within gamma(n) of the sum of their magnitudes (Higham §4.2, order-free form);
+#   * partial products below the normal range may be flushed: one 2^-126 per addition.
+SPLIT_DROP = {3: 2.0 ** -23, 2: 1.5 * 2.0 ** -15}
+SPLIT_TERMS = {3: 6, 2: 3}
+SPLIT_MAG = 1.02
+
+
+def split_bound(mag, bias_mag, k, np_):
+    """Bound of b + sum_k a_k w_k as a bf16-split contraction of NP planes; mag = sum_k |a_k w_k|, bias_mag = |b|."""
+    n = SPLIT_TERMS[np_] * k
+    return SPLIT_DROP[np_] * mag + gamma(n) * (bias_mag + SPLIT_MAG * mag) + n * MIN_NORMAL
+
+
+def conv_split(x, w, b, np_, relu=0):
+    """conv() under the bf16-split contraction of NP planes (conv3x3_ragged_kernel<..., NP>, conv2 of conv12_fused_split)."""
+    y, _ = conv(x, w, b, relu)
+    x, w, b = _f64(x), _f64(w), _f64(b)
+    kh, kw, cin, cout = w.shape
+    n, h, wd, _ = x.shape
+    xp = np.zeros((n, h + kh - 1, wd + kw - 1, cin))
+    xp[:, kh // 2:kh // 2 + h, kw // 2:kw // 2 + wd] = np.abs(x)
+    mag = np.zeros((n, h, wd, cout))
+    for ky in range(kh):
+        for kx in range(kw):
+            mag += xp[:, ky:ky + h, kx:kx + wd] @ np.abs(w[ky, kx])
+    return y, split_bound(mag, np.abs(b), kh * kw * cin, np_)
+
+
+def linear_split(x, w, b, np_):
+    """linear() under the bf16-split contraction (gemm_split_kernel<NP>: the GRU input projections)."""
+    x, w, b = _f64(x), _f64(w), _f64(b)
+    return x @ w + b, split_bound(np.abs(x) @ np.abs(w), np.abs(b), w.shape[0], np_)
+
+
+# The gates of the relaxed and reduced recurrences (kernels_gru_split.hip; the FAST path of kernels_gru.hip) use the hardware
+# v_exp_f32 (exp2) and v_rcp_f32, 1 ulp (<= 2^-23 relative) each:
+#   sigmoid(x) = rcp(1 + exp2(x * -log2 e)):  the product rounds (u |x log2 e| in the exponent: u |x| relative in the power, and
+#     as much again for the rounded constant), exp2 and rcp 2^-23 each, the sum u.  s = 1 / (1 + E) has |ds / s| <= |dE / E|, so
+#     the relative error is FAST_EXP_REL + FAST_RCP_REL + u + 2 u |x|; an exponent beyond the range (E = inf or a flushed
+#     power) costs at most one smallest normal absolutely.
+#   tanh(x) = (t - 1) rcp(t + 1), t = exp2(min(x, 40) * 2 log2 e):  t is off by (2^-23 + 4 u |x|) relative; d tanh / dt =
+#     2 / (t + 1)^2 <= 1 / (2 t), so that moves tanh by at most half of it absolutely; t - 1, t + 1, rcp and the product add
+#     3 u + 2^-23 relative to |tanh| (t - 1 is exact where it cancels).
+FAST_EXP_REL = 2.0 ** -23
+FAST_RCP_REL = 2.0 ** -23
+
+
+def fast_sigmoid_bound(x, s):
+    x, s = np.abs(_f64(x)), _f64(s)
+    return (FAST_EXP_REL + FAST_RCP_REL + U + 2 * U * x) * 1.01 * s + MIN_NORMAL
+
+
+def fast_tanh_bound(x, t):
+    x, t = np.minimum(np.abs(_f64(x)), 40.0), np.abs(_f64(t))
+    return 0.5 * (FAST_EXP_REL + 4 * U * x) * 1.01 + (3 * U + FAST_RCP_REL) * 1.01 * t + MIN_NORMAL
+
+
 # ---------------------------------------------------------------- GRU
-def gru_dir(x, wi, bi, wh, bh, h_prev_fp32, reverse=False):
+def gru_dir(x, wi, bi, wh, bh, h_prev_fp32, reverse=False, proj_np=0, hid_np=0, fast_gates=False):
     """One direction of an ONNX / PyTorch GRU (gate order r, z, n; linear_before_reset = 1; h0 = 0), bounded one step
     at a time: h_t is compared with the float64 cell applied to the fp32 h_{t-1} that the evaluation under test
     produced itself (`h_prev_fp32` [T][N][H], its own output of this direction), so the bound does not grow with T.
@@ -206,7 +272,11 @@ def gru_dir(x, wi, bi, wh, bh, h_prev_fp32, reverse=False):
         h' = (1 - z) n + z h
 
     Bound: the two projections by the contraction bound; the gate pre-activations add one rounding; sigmoid is
-    1/4-Lipschitz and tanh 1-Lipschitz, plus their own bounds; the spec's h' = fmaf(z, h - n, n) rounds twice."""
+    1/4-Lipschitz and tanh 1-Lipschitz, plus their own bounds; the spec's h' = fmaf(z, h - n, n) rounds twice.
+
+    The relaxed / reduced numerics: proj_np / hid_np = NP (3 or 2) bounds the input projection / the recurrence's h Wh by
+    split_bound instead of the k-ascending chain (0), fast_gates the gates by fast_sigmoid_bound / fast_tanh_bound instead of
+    the spec's.  The rest of the step is the same arithmetic."""
     x, wi, bi, wh, bh = _f64(x), _f64(wi), _f64(bi), _f64(wh), _f64(bh)
     hs = _f64(h_prev_fp32)
     T, N, I = x.shape
@@ -217,16 +287,24 @@ def gru_dir(x, wi, bi, wh, bh, h_prev_fp32, reverse=False):
     h = np.zeros((N, H))
     for t in order:
         gx = x[t] @ wi + bi
-        ex = gamma(I + 1) * (np.abs(x[t]) @ np.abs(wi) + np.abs(bi)) + I * TINY
+        mx = np.abs(x[t]) @ np.abs(wi)
+        ex = split_bound(mx, np.abs(bi), I, proj_np) if proj_np else gamma(I + 1) * (mx + np.abs(bi)) + I * TINY
         gh = h @ wh + bh
-        eh = gamma(H + 1) * (np.abs(h) @ np.abs(wh) + np.abs(bh)) + H * TINY
+        mh = np.abs(h) @ np.abs(wh)
+        eh = split_bound(mh, np.abs(bh), H, hid_np) if hid_np else gamma(H + 1) * (mh + np.abs(bh)) + H * TINY
         ar, az = gx[:, :H] + gh[:, :H], gx[:, H:2 * H] + gh[:, H:2 * H]
         r, z = _sigmoid64(ar), _sigmoid64(az)
-        er = 0.25 * (ex[:, :H] + eh[:, :H] + U * np.abs(ar)) + SIGMOID_ULP * ulp(np.maximum(r, MIN_NORMAL))
-        ez = 0.25 * (ex[:, H:2 * H] + eh[:, H:2 * H] + U * np.abs(az)) + SIGMOID_ULP * ulp(np.maximum(z, MIN_NORMAL))
+        if fast_gates:
+            sr, sz = fast_sigmoid_bound(ar, r), fast_sigmoid_bound(az, z)
+        else:
+            sr, sz = SIGMOID_ULP * ulp(np.maximum(r, MIN_NORMAL)), SIGMOID_ULP * ulp(np.maximum(z, MIN_NORMAL))
+        er = 0.25 * (ex[:, :H] + eh[:, :H] + U * np.abs(ar)) + sr
+        ez = 0.25 * (ex[:, H:2 * H] + eh[:, H:2 * H] + U * np.abs(az)) + sz
         an = gx[:, 2 * H:] + r * gh[:, 2 * H:]
         n = np.tanh(an)
-        en = ex[:, 2 * H:] + er * np.abs(gh[:, 2 * H:]) + (r + er) * eh[:, 2 * H:] + U * np.abs(an) + TANH_ABS
+        # (the argument's own error, at most ea below, also moves the fast tanh's argument-dependent term: negligible)
+        ea = ex[:, 2 * H:] + er * np.abs(gh[:, 2 * H:]) + (r + er) * eh[:, 2 * H:] + U * np.abs(an)
+        en = ea + (fast_tanh_bound(np.abs(an) + ea, n) if fast_gates else TANH_ABS)
         hn = (1 - z) * n + z * h
         e = ez * np.abs(h - n) + (z + ez) * (en + U * np.abs(h - n)) + en + U * np.abs(hn)
         y[t] = hn
@@ -235,12 +313,12 @@ def gru_dir(x, wi, bi, wh, bh, h_prev_fp32, reverse=False):
     return y, bound
 
 
-def gru_bidir(x, ws, y_fp32):
+def gru_bidir(x, ws, y_fp32, **numerics):
     """Bidirectional GRU -> [T][N][2H] (forward, then backward); ws = (wi, bi, wh, bh) x 2 as in the model file;
-    y_fp32 is the fp32 output under test, whose halves supply each direction's previous state."""
+    y_fp32 is the fp32 output under test, whose halves supply each direction's previous state; numerics: gru_dir's flags."""
     H = _f64(ws[2]).shape[0]
-    yf, bf = gru_dir(x, *ws[0:4], y_fp32[..., :H], reverse=False)
-    yb, bb = gru_dir(x, *ws[4:8], y_fp32[..., H:], reverse=True)
+    yf, bf = gru_dir(x, *ws[0:4], y_fp32[..., :H], reverse=False, **numerics)
+    yb, bb = gru_dir(x, *ws[4:8], y_fp32[..., H:], reverse=True, **numerics)
     return np.concatenate([yf, yb], axis=-1), np.concatenate([bf, bb], axis=-1)
 
 
@@ -322,3 +400,35 @@ def check_graph(buf, x, what=""):
         err = np.abs(np.asarray(slots[op["out"]], np.float64) - ref[0])
         worst.append((name, float(np.max(np.where(ref[1] > 0, err / np.maximum(ref[1], 1e-300), 0), initial=0))))
     return worst
+
+
+# ---------------------------------------------------------------- exact probes of the split contractions
+def bf16_rne(x):
+    """fp32 -> the nearest bf16 (ties to even), as fp32 (v_cvt_pk_bf16_f32 and split_weights for finite values)."""
+    u = np.asarray(x, np.float32).view(np.uint32).astype(np.uint64)
+    return (((u + 0x7FFF + ((u >> 16) & 1)) >> 16) << 16).astype(np.uint32).view(np.float32)
+
+
+def bf16_planes(x):
+    """(hi, mid, lo): each the bf16 nearest to the running residual of the fp32 value x (the residuals are exact)."""
+    x = np.asarray(x, np.float32)
+    hi = bf16_rne(x)
+    r = (x - hi).astype(np.float32)
+    mid = bf16_rne(r)
+    lo = bf16_rne((r - mid).astype(np.float32))
+    return hi, mid, lo
+
+
+# (activation, weight, relaxed result, reduced result): one product each, operands whose planes are known, every partial
+# sum an integer or half-integer below 2^24, so each result is exact in fp32 in any order.  257 = 256 + 1 (hi, mid): relaxed
+# keeps mid x mid, reduced drops it; 65664.5 = 65536 + 128 + 0.5 (128.5 ties to the even 128): relaxed keeps lo x hi,
+# reduced has no lo plane.  tests/test_numeric_spec.py checks these premises on the CPU.
+SPLIT_PROBES = [(257.0, 257.0, 66049.0, 66048.0), (65664.5, 1.0, 65664.5, 65664.0), (1.0, 65664.5, 65664.5, 65664.0)]
+
+
+def split_probe_value(a, w, np_):
+    """The sum of the plane products an NP-plane contraction keeps, in float64, for one product a w."""
+    ah, am, al = (float(v) for v in bf16_planes(a))
+    wh, wm, wl = (float(v) for v in bf16_planes(w))
+    kept = [ah * wh, ah * wm, am * wh] + ([am * wm, ah * wl, al * wh] if np_ == 3 else [])
+    return sum(kept), kept

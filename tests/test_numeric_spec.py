@@ -310,3 +310,36 @@ def test_graph_walk_fails_on_an_op_without_a_definition():
         pass
     with pytest.raises(AssertionError, match="no float64 definition"):
         R._op_ref(_Op(type=11, in0=0, out=1, w=[], kh=0, kw=0, cin=0, cout=0, hidden=0, relu=0), {0: np.zeros(1)})
+
+
+# ------------------------------------------------------------------ premises of the split-contraction probes
+def test_split_probe_premises():
+    """The exact probes of tests/test_gpu_numerics_split.py: every operand's bf16 planes (numpy round-to-nearest-even of the
+    running residual) are the documented ones, the kept plane products of each mode add up to the stated result, every
+    partial sum of them is exact in fp32, and relaxed equals the true product.  (Each probe output holds one product, so its
+    partial sums are those of the kept plane products: non-negative half-integers whose total is below 2^24 — a partial sum
+    in any order is then a half-integer in [0, total], which fp32 holds exactly.)"""
+    planes = {257.0: (256.0, 1.0, 0.0), 1.0: (1.0, 0.0, 0.0), 65664.5: (65536.0, 128.0, 0.5)}
+    for v, want in planes.items():
+        got = tuple(float(p) for p in R.bf16_planes(np.float32(v)))
+        assert got == want, (v, got, want)
+        assert sum(got) == v
+    assert float(R.bf16_rne(np.float32(128.5))) == 128.0          # the tie goes to the even 128, not 129
+    for a, w, relaxed, reduced in R.SPLIT_PROBES:
+        for np_, want in ((3, relaxed), (2, reduced)):
+            total, kept = R.split_probe_value(a, w, np_)
+            assert total == want, (a, w, np_, total, want)
+            assert all(k >= 0 and 2 * k == int(2 * k) for k in kept), kept
+            assert sum(kept) < 2 ** 24
+        assert relaxed == float(np.float64(a) * np.float64(w)) and relaxed != reduced
+        assert np.float32(relaxed) == relaxed and np.float32(reduced) == reduced
+
+
+def test_split_bounds_cover_the_dropped_terms():
+    """split_bound is at least the documented dropped-term fraction of |a w| and grows with the number of additions."""
+    mag = np.array([1.0, 100.0])
+    for np_ in (3, 2):
+        b = R.split_bound(mag, 0.0, 64, np_)
+        assert np.all(b >= R.SPLIT_DROP[np_] * mag)
+        assert np.all(R.split_bound(mag, 0.0, 1152, np_) > b)
+    assert R.SPLIT_DROP[2] > 100 * R.SPLIT_DROP[3]
