@@ -319,6 +319,20 @@ OCRS_API ocrs_status ocrs_engine_detect_words(const ocrs_engine* e, const ocrs_p
 OCRS_API ocrs_status ocrs_engine_detect_words_batch(const ocrs_engine* e, const ocrs_page* const* pages, size_t n_pages,
                                            float** rects, size_t* offsets);
 
+/* Detection confidence: the two calls above, plus, per returned rect and indexed like the rects,
+ *   pixels: the number of text-mask pixels of the word's connected component (8-connected foreground; holes and what lies
+ *           inside them do not count);
+ *   score:  the mean text probability of those pixels, computed from an integer sum so that it never depends on batching
+ *           or scheduling: (float)(sum of floor(clamp(p, 0, 1) * 2^24) / (pixels * 2^24)), p from the map
+ *           ocrs_engine_detect_text_pixels returns.  The fixed point costs less than 2^-24 a pixel; at most 1.
+ * Both malloc'ed (ocrs_buffer_free).  The rects are those of the unscored calls.  Filtering by score is the caller's: there
+ * is no engine option for it.  Scores say how sure the model was, not whether it is right: calibrate on real models before
+ * thresholding. */
+OCRS_API ocrs_status ocrs_engine_detect_words_scored(const ocrs_engine* e, const ocrs_page* page, float** rects, size_t* n,
+                                                     float** score, uint32_t** pixels);
+OCRS_API ocrs_status ocrs_engine_detect_words_batch_scored(const ocrs_engine* e, const ocrs_page* const* pages, size_t n_pages,
+                                                           float** rects, size_t* offsets, float** score, uint32_t** pixels);
+
 /* OcrEngine::detect_text_pixels (lib.rs:207-213 -> detection.rs:131-200):
  * writes the [H,W] probability map. */
 OCRS_API ocrs_status ocrs_engine_detect_text_pixels(const ocrs_engine* e, const ocrs_page* page, float* out_hw);
@@ -341,6 +355,17 @@ OCRS_API ocrs_status ocrs_engine_find_text_lines(const ocrs_engine* e, const ocr
 OCRS_API ocrs_status ocrs_engine_find_text_lines_batch(const ocrs_engine* e, size_t n_pages, const float* word_rects,
                                                        const size_t* word_offsets, float** line_rects,
                                                        size_t** line_offsets, size_t** page_line_offsets);
+
+/* The two calls above, plus *word_index (malloc'ed, one entry per output rect): word_index[k] is the index, within its
+ * page's input words, of output rect k — what a caller needs to carry anything per word (a detection score, a label)
+ * across the permutation.  A permutation per page; identical input rects keep distinct indices. */
+OCRS_API ocrs_status ocrs_engine_find_text_lines_indexed(const ocrs_engine* e, const ocrs_page* page, const float* word_rects,
+                                                         size_t n_words, float** line_rects, size_t** line_offsets,
+                                                         size_t* n_lines, size_t** word_index);
+OCRS_API ocrs_status ocrs_engine_find_text_lines_batch_indexed(const ocrs_engine* e, size_t n_pages, const float* word_rects,
+                                                               const size_t* word_offsets, float** line_rects,
+                                                               size_t** line_offsets, size_t** page_line_offsets,
+                                                               size_t** word_index);
 
 /* One recognised character: TextChar (text_items.rs:48-54). */
 typedef struct ocrs_text_char {
@@ -520,6 +545,10 @@ OCRS_API ocrs_status ocrs_group_prepare_input_device_batch(const ocrs_engine_gro
  * member); output as ocrs_engine_detect_words_batch. */
 OCRS_API ocrs_status ocrs_group_detect_words_batch(ocrs_engine_group* g, const ocrs_page* const* pages, size_t n_pages,
                                                    float** rects, size_t* offsets);
+/* The same with detection confidence; output as ocrs_engine_detect_words_batch_scored.  Scores and pixel counts travel in
+ * the per-request payload next to the rects, through either gather transport. */
+OCRS_API ocrs_status ocrs_group_detect_words_batch_scored(ocrs_engine_group* g, const ocrs_page* const* pages, size_t n_pages,
+                                                          float** rects, size_t* offsets, float** score, uint32_t** pixels);
 /* OcrEngine::recognize_text (lib.rs:237-256); arguments and output as ocrs_engine_recognize_text_batch.
  * (find_text_lines is host work: ocrs_engine_find_text_lines_batch serves a group as it is.) */
 OCRS_API ocrs_status ocrs_group_recognize_text_batch(ocrs_engine_group* g, const ocrs_page* const* pages, size_t n_pages,

@@ -304,6 +304,35 @@ def _rects_to_array(rects):
     return a
 
 
+def _take(ptr, n, dtype):
+    """Copies n items out of a malloc'ed result array and frees it."""
+    out = np.ctypeslib.as_array(ptr, shape=(max(n, 1),))[:n].astype(dtype, copy=True)
+    lib().ocrs_buffer_free(ptr)
+    return out
+
+
+def _detect_words_batch(name, handle, inputs, scores):
+    """ocrs_{engine,group}_detect_words_batch[_scored] (name without the suffix) -> rects per page [, score per page,
+    pixels per page]."""
+    n = len(inputs)
+    pages = (C.c_void_p * n)(*[i._h for i in inputs])
+    rects = C.POINTER(C.c_float)()
+    offs = (C.c_size_t * (n + 1))()
+    if scores:
+        sc, px = C.POINTER(C.c_float)(), C.POINTER(C.c_uint32)()
+        check(getattr(lib(), name + "_scored")(handle, pages, C.c_size_t(n), C.byref(rects), offs, C.byref(sc), C.byref(px)))
+    else:
+        check(getattr(lib(), name)(handle, pages, C.c_size_t(n), C.byref(rects), offs))
+    total = offs[n]
+    flat = np.ctypeslib.as_array(rects, shape=(max(total, 1) * 6,))[: total * 6].reshape(-1, 6).copy()
+    lib().ocrs_buffer_free(rects)
+    words = [flat[offs[i]:offs[i + 1]] for i in range(n)]
+    if not scores:
+        return words
+    fs, fp = _take(sc, total, np.float32), _take(px, total, np.uint32)
+    return words, [fs[offs[i]:offs[i + 1]] for i in range(n)], [fp[offs[i]:offs[i + 1]] for i in range(n)]
+
+
 def _pack_lines(lines):
     offs = [0]
     flat = []
@@ -411,24 +440,25 @@ class OcrEngine:
         return OcrInput(h_out), cb.value
 
     # ---- lib.rs:193-199
-    def detect_words(self, inp):
+    def detect_words(self, inp, scores=False):
+        """scores=True: through ocrs_engine_detect_words_scored -> (words, score float32 [n], pixels uint32 [n]): per word
+        the mean text probability of its component's pixels and their number."""
         rects = C.POINTER(C.c_float)()
         n = C.c_size_t(0)
-        check(lib().ocrs_engine_detect_words(self._h, inp._h, C.byref(rects), C.byref(n)))
+        if scores:
+            sc, px = C.POINTER(C.c_float)(), C.POINTER(C.c_uint32)()
+            check(lib().ocrs_engine_detect_words_scored(self._h, inp._h, C.byref(rects), C.byref(n), C.byref(sc), C.byref(px)))
+        else:
+            check(lib().ocrs_engine_detect_words(self._h, inp._h, C.byref(rects), C.byref(n)))
         out = np.ctypeslib.as_array(rects, shape=(max(n.value, 1) * 6,))[: n.value * 6].reshape(-1, 6).copy()
         lib().ocrs_buffer_free(rects)
-        return out
+        if not scores:
+            return out
+        return out, _take(sc, n.value, np.float32), _take(px, n.value, np.uint32)
 
-    def detect_words_batch(self, inputs):
-        n = len(inputs)
-        pages = (C.c_void_p * n)(*[i._h for i in inputs])
-        rects = C.POINTER(C.c_float)()
-        offs = (C.c_size_t * (n + 1))()
-        check(lib().ocrs_engine_detect_words_batch(self._h, pages, C.c_size_t(n), C.byref(rects), offs))
-        total = offs[n]
-        flat = np.ctypeslib.as_array(rects, shape=(max(total, 1) * 6,))[: total * 6].reshape(-1, 6).copy()
-        lib().ocrs_buffer_free(rects)
-        return [flat[offs[i]:offs[i + 1]] for i in range(n)]
+    def detect_words_batch(self, inputs, scores=False):
+        """scores=True: -> (words per page, score per page, pixels per page)."""
+        return _detect_words_batch("ocrs_engine_detect_words_batch", self._h, inputs, scores)
 
     # ---- lib.rs:207-213
     def detect_text_pixels(self, inp):
@@ -438,22 +468,32 @@ class OcrEngine:
         return out
 
     # ---- lib.rs:222-228
-    def find_text_lines(self, inp, words):
+    def find_text_lines(self, inp, words, index=False):
+        """index=True: -> (lines, index per line): index[l][k] is the position in `words` of rect k of line l."""
         a = _rects_to_array(words)
         lr = C.POINTER(C.c_float)()
         lo = C.POINTER(C.c_size_t)()
         nl = C.c_size_t(0)
-        check(lib().ocrs_engine_find_text_lines(self._h, inp._h if inp is not None else None,
-                                                a.ctypes.data_as(C.POINTER(C.c_float)), C.c_size_t(len(a)), C.byref(lr),
-                                                C.byref(lo), C.byref(nl)))
+        args = (self._h, inp._h if inp is not None else None, a.ctypes.data_as(C.POINTER(C.c_float)), C.c_size_t(len(a)),
+                C.byref(lr), C.byref(lo), C.byref(nl))
+        if index:
+            wi = C.POINTER(C.c_size_t)()
+            check(lib().ocrs_engine_find_text_lines_indexed(*args, C.byref(wi)))
+        else:
+            check(lib().ocrs_engine_find_text_lines(*args))
         offs = [lo[i] for i in range(nl.value + 1)]
         flat = np.ctypeslib.as_array(lr, shape=(max(len(a), 1) * 6,))[: len(a) * 6].reshape(-1, 6).copy()
         lib().ocrs_buffer_free(lr)
         lib().ocrs_buffer_free(lo)
-        return [flat[offs[i]:offs[i + 1]] for i in range(nl.value)]
+        lines = [flat[offs[i]:offs[i + 1]] for i in range(nl.value)]
+        if not index:
+            return lines
+        widx = _take(wi, len(a), np.uintp).astype(np.int64)
+        return lines, [widx[offs[i]:offs[i + 1]] for i in range(nl.value)]
 
-    def find_text_lines_batch_raw(self, words_per_page):
-        """Threaded over pages.  Returns (rects [n,6], line_offsets, page_line_offsets) as numpy arrays."""
+    def find_text_lines_batch_raw(self, words_per_page, index=False):
+        """Threaded over pages.  Returns (rects [n,6], line_offsets, page_line_offsets) as numpy arrays; index=True: plus
+        word_index [n] (for every output rect its position in its page's input words)."""
         n = len(words_per_page)
         woffs = np.zeros(n + 1, dtype=np.uintp)
         for i, w in enumerate(words_per_page):
@@ -462,15 +502,21 @@ class OcrEngine:
         lr = C.POINTER(C.c_float)()
         lo = C.POINTER(C.c_size_t)()
         po = C.POINTER(C.c_size_t)()
-        check(lib().ocrs_engine_find_text_lines_batch(self._h, C.c_size_t(n), allw.ctypes.data_as(C.POINTER(C.c_float)),
-                                                      woffs.ctypes.data_as(C.POINTER(C.c_size_t)), C.byref(lr), C.byref(lo),
-                                                      C.byref(po)))
+        args = (self._h, C.c_size_t(n), allw.ctypes.data_as(C.POINTER(C.c_float)), woffs.ctypes.data_as(C.POINTER(C.c_size_t)),
+                C.byref(lr), C.byref(lo), C.byref(po))
+        if index:
+            wi = C.POINTER(C.c_size_t)()
+            check(lib().ocrs_engine_find_text_lines_batch_indexed(*args, C.byref(wi)))
+        else:
+            check(lib().ocrs_engine_find_text_lines_batch(*args))
         poffs = np.ctypeslib.as_array(po, shape=(n + 1,)).astype(np.uintp)
         nl = int(poffs[n])
         loffs = np.ctypeslib.as_array(lo, shape=(nl + 1,)).astype(np.uintp)
         rects = np.ctypeslib.as_array(lr, shape=(max(len(allw), 1) * 6,))[: len(allw) * 6].reshape(-1, 6).copy()
         for p in (lr, lo, po):
             lib().ocrs_buffer_free(p)
+        if index:
+            return rects, loffs, poffs, _take(wi, len(allw), np.uintp).astype(np.int64)
         return rects, loffs, poffs
 
     def recognize_text_batch_raw(self, inputs, rects, line_offsets, page_line_offsets, scores=False):
@@ -800,19 +846,12 @@ class EngineGroup:
                                                           h, w, c, out))
         return [OcrInput(C.c_void_p(out[i])) for i in range(n)]
 
-    def detect_words_batch(self, inputs):
-        n = len(inputs)
-        pages = (C.c_void_p * n)(*[i._h for i in inputs])
-        rects = C.POINTER(C.c_float)()
-        offs = (C.c_size_t * (n + 1))()
-        check(lib().ocrs_group_detect_words_batch(self._h, pages, C.c_size_t(n), C.byref(rects), offs))
-        total = offs[n]
-        flat = np.ctypeslib.as_array(rects, shape=(max(total, 1) * 6,))[: total * 6].reshape(-1, 6).copy()
-        lib().ocrs_buffer_free(rects)
-        return [flat[offs[i]:offs[i + 1]] for i in range(n)]
+    def detect_words_batch(self, inputs, scores=False):
+        """scores=True: -> (words per page, score per page, pixels per page), as OcrEngine.detect_words_batch."""
+        return _detect_words_batch("ocrs_group_detect_words_batch", self._h, inputs, scores)
 
-    def find_text_lines_batch_raw(self, words_per_page):
-        return self.member(0)[0].find_text_lines_batch_raw(words_per_page)   # host work: any engine handle serves
+    def find_text_lines_batch_raw(self, words_per_page, index=False):
+        return self.member(0)[0].find_text_lines_batch_raw(words_per_page, index=index)   # host work: any engine handle serves
 
     def recognize_text_batch_raw(self, inputs, rects, line_offsets, page_line_offsets):
         n = len(inputs)

@@ -74,6 +74,8 @@ DECLARED_SYMBOLS = [
     "ocrs_device_set_isolation", "ocrs_device_isolation", "ocrs_group_set_replay", "ocrs_abi_version",
     "ocrs_engine_recognize_text_scored", "ocrs_engine_recognize_text_batch_scored", "ocrs_ctc_beam_search_scored",
     "ocrs_engine_run_recognition_ops",
+    "ocrs_engine_detect_words_scored", "ocrs_engine_detect_words_batch_scored", "ocrs_group_detect_words_batch_scored",
+    "ocrs_engine_find_text_lines_indexed", "ocrs_engine_find_text_lines_batch_indexed",
 ]
 
 ABI_VERSION = 6   # include/ocrs_amd.h OCRS_ABI_VERSION

@@ -45,6 +45,12 @@ def main(argv=None):
     ap.add_argument("--confidence", action="store_true",
                     help="with -j: a \"confidence\" per line and word, exp of the mean log-prob of its chars (no reference "
                          "counterpart; uncalibrated: DESIGN.md \"Recognition confidence\")")
+    ap.add_argument("--detection-confidence", action="store_true",
+                    help="with -j: \"word_boxes\" per line, the detector's word boxes in reading order with \"confidence\" (mean "
+                         "text probability of the box's pixels) and \"pixels\" (no reference counterpart; uncalibrated: "
+                         "DESIGN.md 7.1)")
+    ap.add_argument("--min-word-score", type=float, metavar="X",
+                    help="drop detected words whose detection confidence is below X before lines are formed")
     ap.add_argument("-o", "--output")
     ap.add_argument("--debug", action="store_true")
     ap.add_argument("--text-map", action="store_true", help="write text-map.png (detect_text_pixels)")
@@ -57,6 +63,8 @@ def main(argv=None):
     args = ap.parse_args(argv)
     if args.confidence and not args.json:
         ap.error("--confidence is only valid with -j/--json")
+    if args.detection_confidence and not args.json:
+        ap.error("--detection-confidence is only valid with -j/--json")
 
     from . import DecodeMethod, DimOrder, ImageSource, Model, OcrEngine, models, output
     from ._lib import OcrsError
@@ -90,15 +98,25 @@ def main(argv=None):
             write_image("text-map.png", tm)
         if args.text_mask:
             write_image("text-mask.png", (tm > np.float32(engine.detection_threshold())).astype(np.float32))
-    words = engine.detect_words(inp)
-    lines = engine.find_text_lines(inp, words)
+    word_boxes = None
+    if args.detection_confidence or args.min_word_score is not None:
+        words, wscore, wpixels = engine.detect_words(inp, scores=True)
+        if args.min_word_score is not None:
+            keep = wscore >= np.float32(args.min_word_score)
+            words, wscore, wpixels = words[keep], wscore[keep], wpixels[keep]
+        lines, index = engine.find_text_lines(inp, words, index=True)
+        if args.detection_confidence:
+            word_boxes = [[(words[k], wscore[k], wpixels[k]) for k in idx] for idx in index]
+    else:
+        words = engine.detect_words(inp)
+        lines = engine.find_text_lines(inp, words)
     if args.text_line_images:  # main.rs:66-86
         os.makedirs("lines", exist_ok=True)
         for i, line in enumerate(lines):
             write_image("lines/line-%d.png" % i, engine.prepare_recognition_input(inp, line) + np.float32(0.5))
     texts = engine.recognize_text(inp, lines, scores=args.confidence)
     if args.json:
-        content = output.format_json_output(args.image, tuple(shape_hw), texts, confidence=args.confidence)
+        content = output.format_json_output(args.image, tuple(shape_hw), texts, confidence=args.confidence, word_boxes=word_boxes)
     else:
         content = output.format_text_output(texts)
     if args.output:

@@ -538,14 +538,19 @@ ocrs_status ocrs_page_image(const ocrs_page* p, float* out_hw) {
     });
 }
 
-ocrs_status ocrs_engine_detect_words_batch(const ocrs_engine* e, const ocrs_page* const* pages, size_t n_pages,
-                                           float** rects, size_t* offsets) {
+namespace {
+
+// ocrs_engine_detect_words[_batch][_scored]: score / pixels null for the unscored calls
+ocrs_status detect_words_batch(const ocrs_engine* e, const ocrs_page* const* pages, size_t n_pages, float** rects,
+                               size_t* offsets, bool scored, float** score, uint32_t** pixels) {
     return guarded_engine(e, [&] {
-        if (!e || !pages || !rects || !offsets) fail(OCRS_ERR_INVALID_ARGUMENT, "null argument");
+        if (!e || !pages || !rects || !offsets || (scored && (!score || !pixels))) fail(OCRS_ERR_INVALID_ARGUMENT, "null argument");
         check_pages_on(e, pages, n_pages);
         std::vector<std::vector<RotatedRect>> rr;
-        e->detect(pages, n_pages, &rr, nullptr);
-        std::vector<float> flat;
+        DetScores sc;
+        e->detect(pages, n_pages, &rr, nullptr, scored ? &sc : nullptr);
+        std::vector<float> flat, fscore;
+        std::vector<uint32_t> fpixels;
         offsets[0] = 0;
         for (size_t i = 0; i < n_pages; i++) {
             for (const RotatedRect& r : rr[i]) {
@@ -553,15 +558,43 @@ ocrs_status ocrs_engine_detect_words_batch(const ocrs_engine* e, const ocrs_page
                 r.to_array(a);
                 flat.insert(flat.end(), a, a + 6);
             }
+            if (scored) {
+                fscore.insert(fscore.end(), sc.score[i].begin(), sc.score[i].end());
+                fpixels.insert(fpixels.end(), sc.pixels[i].begin(), sc.pixels[i].end());
+            }
             offsets[i + 1] = flat.size() / 6;
+        }
+        if (scored) {
+            *score = dup_buffer(fscore);
+            *pixels = dup_buffer(fpixels);
         }
         *rects = dup_buffer(flat);
     });
 }
 
+}  // namespace
+
+ocrs_status ocrs_engine_detect_words_batch(const ocrs_engine* e, const ocrs_page* const* pages, size_t n_pages,
+                                           float** rects, size_t* offsets) {
+    return detect_words_batch(e, pages, n_pages, rects, offsets, false, nullptr, nullptr);
+}
+
 ocrs_status ocrs_engine_detect_words(const ocrs_engine* e, const ocrs_page* page, float** rects, size_t* n) {
     size_t offs[2] = {0, 0};
     ocrs_status s = ocrs_engine_detect_words_batch(e, &page, page ? 1 : 0, rects, offs);
+    if (s == OCRS_OK && n) *n = offs[1];
+    return s;
+}
+
+ocrs_status ocrs_engine_detect_words_batch_scored(const ocrs_engine* e, const ocrs_page* const* pages, size_t n_pages,
+                                                  float** rects, size_t* offsets, float** score, uint32_t** pixels) {
+    return detect_words_batch(e, pages, n_pages, rects, offsets, true, score, pixels);
+}
+
+ocrs_status ocrs_engine_detect_words_scored(const ocrs_engine* e, const ocrs_page* page, float** rects, size_t* n,
+                                            float** score, uint32_t** pixels) {
+    size_t offs[2] = {0, 0};
+    ocrs_status s = ocrs_engine_detect_words_batch_scored(e, &page, page ? 1 : 0, rects, offs, score, pixels);
     if (s == OCRS_OK && n) *n = offs[1];
     return s;
 }
@@ -576,46 +609,85 @@ ocrs_status ocrs_engine_detect_text_pixels(const ocrs_engine* e, const ocrs_page
 
 float ocrs_engine_detection_threshold(const ocrs_engine* e) { return e ? e->text_threshold : 0.2f; }
 
-ocrs_status ocrs_engine_find_text_lines(const ocrs_engine* e, const ocrs_page* page, const float* word_rects,
-                                        size_t n_words, float** line_rects, size_t** line_offsets, size_t* n_lines) {
-    (void)e; (void)page;
+namespace {
+
+// ocrs_engine_find_text_lines[_indexed]: word_index null for the plain call
+ocrs_status find_text_lines_one(const float* word_rects, size_t n_words, float** line_rects, size_t** line_offsets,
+                                size_t* n_lines, bool indexed, size_t** word_index) {
     return guarded([&] {
-        if (!line_rects || !line_offsets || !n_lines || (n_words && !word_rects))
+        if (!line_rects || !line_offsets || !n_lines || (n_words && !word_rects) || (indexed && !word_index))
             fail(OCRS_ERR_INVALID_ARGUMENT, "null argument");
         std::vector<RotatedRect> words(n_words);
         for (size_t i = 0; i < n_words; i++) words[i] = RotatedRect::from_array(word_rects + 6 * i);
-        auto lines = find_text_lines(words);
+        std::vector<std::vector<size_t>> index;
+        auto lines = find_text_lines(words, indexed ? &index : nullptr);
         std::vector<float> flat;
-        std::vector<size_t> offs{0};
-        for (const auto& l : lines) {
-            for (const RotatedRect& r : l) {
+        std::vector<size_t> offs{0}, widx;
+        for (size_t li = 0; li < lines.size(); li++) {
+            for (const RotatedRect& r : lines[li]) {
                 float a[6];
                 r.to_array(a);
                 flat.insert(flat.end(), a, a + 6);
             }
+            if (indexed) widx.insert(widx.end(), index[li].begin(), index[li].end());
             offs.push_back(flat.size() / 6);
         }
+        if (indexed) *word_index = dup_buffer(widx);
         *line_rects = dup_buffer(flat);
         *line_offsets = dup_buffer(offs);
         *n_lines = lines.size();
     });
 }
 
+ocrs_status find_text_lines_many(const ocrs_engine* e, size_t n_pages, const float* word_rects, const size_t* word_offsets,
+                                 float** line_rects, size_t** line_offsets, size_t** page_line_offsets, bool indexed,
+                                 size_t** word_index);
+
+}  // namespace
+
+ocrs_status ocrs_engine_find_text_lines(const ocrs_engine* e, const ocrs_page* page, const float* word_rects,
+                                        size_t n_words, float** line_rects, size_t** line_offsets, size_t* n_lines) {
+    (void)e; (void)page;
+    return find_text_lines_one(word_rects, n_words, line_rects, line_offsets, n_lines, false, nullptr);
+}
+
+ocrs_status ocrs_engine_find_text_lines_indexed(const ocrs_engine* e, const ocrs_page* page, const float* word_rects,
+                                                size_t n_words, float** line_rects, size_t** line_offsets, size_t* n_lines,
+                                                size_t** word_index) {
+    (void)e; (void)page;
+    return find_text_lines_one(word_rects, n_words, line_rects, line_offsets, n_lines, true, word_index);
+}
+
 ocrs_status ocrs_engine_find_text_lines_batch(const ocrs_engine* e, size_t n_pages, const float* word_rects,
                                               const size_t* word_offsets, float** line_rects, size_t** line_offsets,
                                               size_t** page_line_offsets) {
+    return find_text_lines_many(e, n_pages, word_rects, word_offsets, line_rects, line_offsets, page_line_offsets, false, nullptr);
+}
+
+ocrs_status ocrs_engine_find_text_lines_batch_indexed(const ocrs_engine* e, size_t n_pages, const float* word_rects,
+                                                      const size_t* word_offsets, float** line_rects, size_t** line_offsets,
+                                                      size_t** page_line_offsets, size_t** word_index) {
+    return find_text_lines_many(e, n_pages, word_rects, word_offsets, line_rects, line_offsets, page_line_offsets, true, word_index);
+}
+
+namespace {
+
+ocrs_status find_text_lines_many(const ocrs_engine* e, size_t n_pages, const float* word_rects, const size_t* word_offsets,
+                                 float** line_rects, size_t** line_offsets, size_t** page_line_offsets, bool indexed,
+                                 size_t** word_index) {
     return guarded([&] {
         TuningScope tune(e ? &e->tuning : nullptr);   // option "layout_threads" of this engine
-        if (!word_offsets || !line_rects || !line_offsets || !page_line_offsets)
+        if (!word_offsets || !line_rects || !line_offsets || !page_line_offsets || (indexed && !word_index))
             fail(OCRS_ERR_INVALID_ARGUMENT, "null argument");
         std::vector<std::vector<std::vector<RotatedRect>>> per_page(n_pages);
+        std::vector<std::vector<std::vector<size_t>>> per_page_index(indexed ? n_pages : 0);
         std::vector<std::string> errors(n_pages);
         auto work = [&](size_t p) {
             try {
                 std::vector<RotatedRect> words;
                 for (size_t k = word_offsets[p]; k < word_offsets[p + 1]; k++)
                     words.push_back(RotatedRect::from_array(word_rects + 6 * k));
-                per_page[p] = find_text_lines(words);
+                per_page[p] = find_text_lines(words, indexed ? &per_page_index[p] : nullptr);
             } catch (const std::exception& ex) {
                 errors[p] = ex.what();
             }
@@ -628,23 +700,27 @@ ocrs_status ocrs_engine_find_text_lines_batch(const ocrs_engine* e, size_t n_pag
         for (const std::string& er : errors)
             if (!er.empty()) fail(OCRS_ERR_RUN_FAILED, "%s", er.c_str());
         std::vector<float> flat;
-        std::vector<size_t> loffs{0}, poffs{0};
+        std::vector<size_t> loffs{0}, poffs{0}, widx;
         for (size_t p = 0; p < n_pages; p++) {
-            for (const auto& l : per_page[p]) {
-                for (const RotatedRect& r : l) {
+            for (size_t li = 0; li < per_page[p].size(); li++) {
+                for (const RotatedRect& r : per_page[p][li]) {
                     float a[6];
                     r.to_array(a);
                     flat.insert(flat.end(), a, a + 6);
                 }
+                if (indexed) widx.insert(widx.end(), per_page_index[p][li].begin(), per_page_index[p][li].end());
                 loffs.push_back(flat.size() / 6);
             }
             poffs.push_back(loffs.size() - 1);
         }
+        if (indexed) *word_index = dup_buffer(widx);
         *line_rects = dup_buffer(flat);
         *line_offsets = dup_buffer(loffs);
         *page_line_offsets = dup_buffer(poffs);
     });
 }
+
+}  // namespace
 
 namespace {
 

@@ -14,10 +14,12 @@ using namespace ocrs::geom;
 // Detection — detection.rs:104-200
 // ===========================================================================
 void ocrs_engine::detect_now(const ocrs_page* const* pages, size_t n, std::vector<std::vector<RotatedRect>>* rects_out,
-                             float* host_map) const {
+                             float* host_map, DetScores* scores) const {
     if (!detection) fail(OCRS_ERR_MODEL_NOT_LOADED, "Detection model not loaded");
+    if (scores && !rects_out) fail(OCRS_ERR_INVALID_ARGUMENT, "detection scores come with the rects");
     if (n == 0) {
         if (rects_out) rects_out->clear();
+        if (scores) { scores->score.clear(); scores->pixels.clear(); }
         return;
     }
     const int64_t in_h64 = detection->input_shape[2], in_w64 = detection->input_shape[3];
@@ -34,10 +36,13 @@ void ocrs_engine::detect_now(const ocrs_page* const* pages, size_t n, std::vecto
         int pad_bottom = 0, pad_right = 0, max_comp = 0;
         int64_t px = 0, arena = 0;
         uint8_t* d_mask = nullptr;
+        float* d_map = nullptr;                          // page-resolution probabilities: scored requests (and host_map) only
         k::CclBuffers b{};
         std::vector<int32_t> counts, ovf;
         std::vector<float> hr_all;
         std::vector<uint8_t> hv_all;
+        std::vector<uint32_t> hp_all;                    // scored: the candidates' pixel counts and fixed-point sums
+        std::vector<uint64_t> hs_all;
     };
     std::vector<SizeGroup> groups;
     std::vector<int> order(n), group_of(n);
@@ -138,13 +143,22 @@ void ocrs_engine::detect_now(const ocrs_page* const* pages, size_t n, std::vecto
         b.keep = ws.alloc_n<uint8_t>((size_t)np * ar);
         b.rects = ws.alloc_n<float>((size_t)np * mc * 6);
         b.valid = ws.alloc_n<uint8_t>((size_t)np * mc);
+        if (scores) {
+            b.score_pixels = ws.alloc_n<uint32_t>((size_t)np * mc);
+            b.score_sums = ws.alloc_n<unsigned long long>((size_t)np * mc);
+        }
         if (zero) OCRS_HIP(hipMemsetAsync(b.overflow, 0, np * sizeof(int32_t), cs));
         return b;
     };
-    auto run_ccl = [&](const uint8_t* mask, int np, int h, int w, const k::CclBuffers& b, int mc, int64_t ar, hipStream_t cs, bool prepared) {
+    auto run_ccl = [&](const uint8_t* mask, const float* map, int np, int h, int w, const k::CclBuffers& b, int mc, int64_t ar,
+                       hipStream_t cs, bool prepared) {
         {
             StageScope sc(T, ST_CCL, cs, prepared ? 3 : 4);
             k::ccl_label(mask, np, h, w, b, mc, cs, prepared);
+        }
+        if (scores) {   // two fills and one kernel, counted with the component stage
+            StageScope sc(T, ST_CCL, cs, 3);
+            k::component_scores(mask, map, np, h, w, b, mc, cs);
         }
         {
             StageScope sc(T, ST_CONTOUR_RECTS, cs, prepared ? 1 : 2);
@@ -167,8 +181,10 @@ void ocrs_engine::detect_now(const ocrs_page* const* pages, size_t n, std::vecto
                 g.arena = 2 * g.px + 64;
                 g.b = alloc_ccl(g.count, g.h, g.px, g.max_comp, g.arena, ex, false);
             }
+            // a scored request keeps every size's map (host_map: one size, one array)
+            g.d_map = d_map ? d_map : scores ? ws.alloc_n<float>((size_t)g.count * g.px) : nullptr;
             prepared[gi] = k::resize_threshold(d_prob + (size_t)g.first * in_h * in_w, g.count, in_h, in_w, in_h - g.pad_bottom, in_w - g.pad_right,
-                                               text_threshold, g.d_mask, d_map, g.h, g.w, ex, g.b.labels, g.b.overflow, g.b.offsets);
+                                               text_threshold, g.d_mask, g.d_map, g.h, g.w, ex, g.b.labels, g.b.overflow, g.b.offsets);
             if (rects_out && !prepared[gi]) OCRS_HIP(hipMemsetAsync(g.b.overflow, 0, g.count * sizeof(int32_t), ex));
         }
     }
@@ -185,7 +201,7 @@ void ocrs_engine::detect_now(const ocrs_page* const* pages, size_t n, std::vecto
     constexpr int kSpec = 2048;
     for (size_t gi = 0; gi < groups.size(); gi++) {
         SizeGroup& g = groups[gi];
-        run_ccl(g.d_mask, g.count, g.h, g.w, g.b, g.max_comp, g.arena, ex, prepared[gi] != 0);
+        run_ccl(g.d_mask, g.d_map, g.count, g.h, g.w, g.b, g.max_comp, g.arena, ex, prepared[gi] != 0);
         const int spec = std::min(g.max_comp, kSpec);
         g.counts.resize(g.count); g.ovf.resize(g.count);
         g.hr_all.resize((size_t)g.count * spec * 6); g.hv_all.resize((size_t)g.count * spec);
@@ -195,11 +211,18 @@ void ocrs_engine::detect_now(const ocrs_page* const* pages, size_t n, std::vecto
         // kernel that waits for CU slots like any other)
         ws.download_2d(g.hr_all.data(), g.b.rects, (size_t)g.max_comp * 6 * sizeof(float), (size_t)spec * 6 * sizeof(float), g.count);
         ws.download_2d(g.hv_all.data(), g.b.valid, (size_t)g.max_comp, (size_t)spec, g.count);
+        if (scores) {
+            g.hp_all.resize((size_t)g.count * spec); g.hs_all.resize((size_t)g.count * spec);
+            ws.download_2d(g.hp_all.data(), g.b.score_pixels, (size_t)g.max_comp * sizeof(uint32_t), (size_t)spec * sizeof(uint32_t), g.count);
+            ws.download_2d(g.hs_all.data(), g.b.score_sums, (size_t)g.max_comp * sizeof(uint64_t), (size_t)spec * sizeof(uint64_t), g.count);
+        }
     }
     ws.sync();   // one wait for all sizes
     std::vector<int32_t> counts(N);
     std::vector<std::vector<float>> hr(N);
     std::vector<std::vector<uint8_t>> hv(N);
+    std::vector<std::vector<uint32_t>> hpx(scores ? N : 0);
+    std::vector<std::vector<uint64_t>> hsum(scores ? N : 0);
     rects_out->assign(n, {});
     bool more = false;
     std::vector<int> big;   // pages (grouped order) whose component stage did not fit
@@ -212,6 +235,10 @@ void ocrs_engine::detect_now(const ocrs_page* const* pages, size_t n, std::vecto
             if (cnt <= spec) {
                 hr[i].assign(g.hr_all.begin() + (size_t)j * spec * 6, g.hr_all.begin() + (size_t)(j + 1) * spec * 6);
                 hv[i].assign(g.hv_all.begin() + (size_t)j * spec, g.hv_all.begin() + (size_t)(j + 1) * spec);
+                if (scores) {
+                    hpx[i].assign(g.hp_all.begin() + (size_t)j * spec, g.hp_all.begin() + (size_t)(j + 1) * spec);
+                    hsum[i].assign(g.hs_all.begin() + (size_t)j * spec, g.hs_all.begin() + (size_t)(j + 1) * spec);
+                }
                 continue;
             }
             more = true;
@@ -219,6 +246,12 @@ void ocrs_engine::detect_now(const ocrs_page* const* pages, size_t n, std::vecto
             hv[i].resize(cnt);
             ws.download(hr[i].data(), g.b.rects + (size_t)j * g.max_comp * 6, hr[i].size() * sizeof(float));
             ws.download(hv[i].data(), g.b.valid + (size_t)j * g.max_comp, cnt);
+            if (scores) {
+                hpx[i].resize(cnt);
+                hsum[i].resize(cnt);
+                ws.download(hpx[i].data(), g.b.score_pixels + (size_t)j * g.max_comp, (size_t)cnt * sizeof(uint32_t));
+                ws.download(hsum[i].data(), g.b.score_sums + (size_t)j * g.max_comp, (size_t)cnt * sizeof(uint64_t));
+            }
         }
     }
     if (more) ws.sync();
@@ -231,7 +264,8 @@ void ocrs_engine::detect_now(const ocrs_page* const* pages, size_t n, std::vecto
             fail(OCRS_ERR_CAPACITY, "text mask of page %d: %lld pixels exceed the 32-bit contour arena", order[i], (long long)g.px);
         const int mc = (int)mc64;
         const k::CclBuffers bb = alloc_ccl(1, g.h, g.px, mc, ar_big, st, true);
-        run_ccl(g.d_mask + (size_t)(i - g.first) * g.px, 1, g.h, g.w, bb, mc, ar_big, st, false);
+        run_ccl(g.d_mask + (size_t)(i - g.first) * g.px, g.d_map ? g.d_map + (size_t)(i - g.first) * g.px : nullptr, 1, g.h, g.w, bb, mc,
+                ar_big, st, false);
         int32_t cnt = 0, o = 0;
         ws.download(&cnt, bb.n_roots, sizeof cnt);
         ws.download(&o, bb.overflow, sizeof o);
@@ -243,12 +277,26 @@ void ocrs_engine::detect_now(const ocrs_page* const* pages, size_t n, std::vecto
         hv[i].resize(cnt);
         ws.download(hr[i].data(), bb.rects, hr[i].size() * sizeof(float));
         ws.download(hv[i].data(), bb.valid, cnt);
+        if (scores) {
+            hpx[i].resize(cnt);
+            hsum[i].resize(cnt);
+            ws.download(hpx[i].data(), bb.score_pixels, (size_t)cnt * sizeof(uint32_t));
+            ws.download(hsum[i].data(), bb.score_sums, (size_t)cnt * sizeof(uint64_t));
+        }
         ws.sync();
     }
+    if (scores) { scores->score.assign(n, {}); scores->pixels.assign(n, {}); }
     for (int i = 0; i < N; i++) {
         auto& out = (*rects_out)[order[i]];
-        for (int c = 0; c < counts[i]; c++)
-            if (hv[i][c]) out.push_back(RotatedRect::from_array(&hr[i][(size_t)c * 6]));
+        for (int c = 0; c < counts[i]; c++) {
+            if (!hv[i][c]) continue;
+            out.push_back(RotatedRect::from_array(&hr[i][(size_t)c * 6]));
+            if (scores) {   // the compaction by valid[] that compacts the rects
+                const uint32_t px = hpx[i][c];
+                scores->pixels[order[i]].push_back(px);
+                scores->score[order[i]].push_back(px ? (float)((double)hsum[i][c] / ((double)px * 16777216.0)) : 0.0f);
+            }
+        }
     }
     if (T) T->collect();
 }
@@ -288,18 +336,27 @@ void ocrs_engine::init_coalescers() {
             run_batch(
                 batch,
                 [&] {
-                    if (batch.size() == 1) { detect_now(batch[0]->pages, batch[0]->n, batch[0]->rects, nullptr); return; }
+                    if (batch.size() == 1) { detect_now(batch[0]->pages, batch[0]->n, batch[0]->rects, nullptr, batch[0]->scores); return; }
                     std::vector<const ocrs_page*> pages;
-                    for (DetRequest* r : batch) pages.insert(pages.end(), r->pages, r->pages + r->n);
+                    bool any_scores = false;   // scored if any member asked; the rects are the same either way
+                    for (DetRequest* r : batch) {
+                        pages.insert(pages.end(), r->pages, r->pages + r->n);
+                        any_scores = any_scores || r->scores;
+                    }
                     std::vector<std::vector<RotatedRect>> rects;
-                    detect_now(pages.data(), pages.size(), &rects, nullptr);
+                    DetScores sc;
+                    detect_now(pages.data(), pages.size(), &rects, nullptr, any_scores ? &sc : nullptr);
                     size_t at = 0;
                     for (DetRequest* r : batch) {
                         r->rects->assign(std::make_move_iterator(rects.begin() + at), std::make_move_iterator(rects.begin() + at + r->n));
+                        if (r->scores) {
+                            r->scores->score.assign(std::make_move_iterator(sc.score.begin() + at), std::make_move_iterator(sc.score.begin() + at + r->n));
+                            r->scores->pixels.assign(std::make_move_iterator(sc.pixels.begin() + at), std::make_move_iterator(sc.pixels.begin() + at + r->n));
+                        }
                         at += r->n;
                     }
                 },
-                [&](DetRequest& r) { detect_now(r.pages, r.n, r.rects, nullptr); });
+                [&](DetRequest& r) { detect_now(r.pages, r.n, r.rects, nullptr, r.scores); });
         },
         [](const DetRequest&, const DetRequest&) { return true; });   // pages of any sizes share a batch (detect_now groups them by size)
     rec_queue = std::make_unique<Coalescer<RecRequest>>(
@@ -353,17 +410,17 @@ void ocrs_engine::init_coalescers() {
 }
 
 void ocrs_engine::detect(const ocrs_page* const* pages, size_t n, std::vector<std::vector<RotatedRect>>* rects_out,
-                         float* host_map) const {
+                         float* host_map, DetScores* scores) const {
     const int max_active = option(OPT_COALESCE);   // (r4: 4 / 6 / 12 detection batches in flight instead of 2: 188-193 pages/s from 12 threads either way)
     const size_t max_pages = (size_t)std::max(1, option(OPT_COALESCE_PAGES));
     // merged only where it cannot be observed: HIP executor (a caller's `trait Model` sees every run), rects only
     if (max_active <= 0 || !det_queue || !rects_out || host_map || n == 0 || 2 * n >= max_pages || !detection ||
         detection->is_callback() || debug) {
-        detect_now(pages, n, rects_out, host_map);
+        detect_now(pages, n, rects_out, host_map, scores);
         return;
     }
     DetRequest r;
-    r.pages = pages; r.n = n; r.rects = rects_out; r.weight = n;
+    r.pages = pages; r.n = n; r.rects = rects_out; r.scores = scores; r.weight = n;
     det_queue->submit(r, max_active, max_pages, option_long(OPT_COALESCE_WINDOW_US));
 }
 

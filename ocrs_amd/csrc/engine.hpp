@@ -56,11 +56,18 @@ struct RecLine {  // TextRecLine (recognition.rs:80-89) + owning page
     uint32_t group_width = 0;
 };
 
+// Detection confidence, indexed [page][word] like the rects of the same call.
+struct DetScores {
+    std::vector<std::vector<float>> score;      // mean text probability of the word's component, from the fixed-point sum
+    std::vector<std::vector<uint32_t>> pixels;  // pixels of that component
+};
+
 // One caller's detection / recognition request while it waits in the engine's coalescer (coalesce.hpp).
 struct DetRequest : CoalescedBase {
     const ocrs_page* const* pages = nullptr;
     size_t n = 0;
     std::vector<std::vector<geom::RotatedRect>>* rects = nullptr;
+    DetScores* scores = nullptr;   // null: the caller did not ask for confidence
 };
 struct RecRequest : CoalescedBase {
     const ocrs_page* const* pages = nullptr;
@@ -108,10 +115,11 @@ struct ocrs_engine {
     // detection.rs:104-200 over a batch of equally sized pages.  Small requests (fewer pages than half of option
     // "coalesce_pages") that only want rects are merged with concurrent ones (coalesce.hpp); results are those of
     // detect_now on the caller's pages alone.
+    // scores (optional, with rects): per word the component's score and pixel count; null allocates and launches nothing extra.
     void detect(const ocrs_page* const* pages, size_t n, std::vector<std::vector<ocrs::geom::RotatedRect>>* rects,
-                float* host_map /* [n,h,w] or null */) const;
+                float* host_map /* [n,h,w] or null */, ocrs::DetScores* scores = nullptr) const;
     void detect_now(const ocrs_page* const* pages, size_t n, std::vector<std::vector<ocrs::geom::RotatedRect>>* rects,
-                    float* host_map) const;
+                    float* host_map, ocrs::DetScores* scores = nullptr) const;
 
     // recognition.rs:404-540 over the lines of several pages; small requests are merged likewise.
     void recognize(const ocrs_page* const* pages, size_t n_pages,

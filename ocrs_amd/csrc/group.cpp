@@ -630,18 +630,23 @@ ocrs_status ocrs_group_prepare_input_device_batch(const ocrs_engine_group* g, co
     return guarded([&] { group_prepare(const_cast<ocrs_engine_group*>(g), d_pixels, n, true, type, order, height, width, channels, out); });
 }
 
-ocrs_status ocrs_group_detect_words_batch(ocrs_engine_group* g, const ocrs_page* const* pages, size_t n_pages, float** rects,
-                                          size_t* offsets) {
+// ocrs_group_detect_words_batch[_scored]: score / pixels null for the unscored call, whose payload is unchanged
+static ocrs_status group_detect_words_batch(ocrs_engine_group* g, const ocrs_page* const* pages, size_t n_pages, float** rects,
+                                            size_t* offsets, bool scored, float** score, uint32_t** pixels) {
     return guarded([&] {
-        if (!g || !rects || !offsets || (n_pages && !pages)) fail(OCRS_ERR_INVALID_ARGUMENT, "null argument");
+        if (!g || !rects || !offsets || (n_pages && !pages) || (scored && (!score || !pixels)))
+            fail(OCRS_ERR_INVALID_ARGUMENT, "null argument");
+        if (scored && g->replay_mode == 2) fail(OCRS_ERR_INVALID_ARGUMENT, "replay: detection scores are not recorded");
         const auto of_member = deal_pages(g, pages, n_pages);
         const size_t G = g->size();
-        // member m's payload: for each of its pages (in page order) [u64 word count | count x 6 f32]
+        // member m's payload: for each of its pages (in page order) [u64 word count | count x 6 f32], and in a scored
+        // request [count x f32 score | count x u32 pixels] after the rects
         std::vector<std::vector<uint8_t>> payloads(G);
         for_each_member(g, of_member, [&](size_t m) {
             std::vector<const ocrs_page*> mine;
             for (size_t i : of_member[m]) mine.push_back(pages[i]);
             std::vector<std::vector<RotatedRect>> rr;
+            DetScores sc;
             if (g->replay_mode == 2) {
                 {
                     std::lock_guard<std::mutex> lk(g->replay_mu);
@@ -653,20 +658,24 @@ ocrs_status ocrs_group_detect_words_batch(ocrs_engine_group* g, const ocrs_page*
                 }
                 std::this_thread::sleep_for(std::chrono::duration<double>(g->replay_s[1]));
             } else {
-                g->members[m].engine->detect(mine.data(), mine.size(), &rr, nullptr);
+                g->members[m].engine->detect(mine.data(), mine.size(), &rr, nullptr, scored ? &sc : nullptr);
                 if (g->replay_mode == 1) {
                     std::lock_guard<std::mutex> lk(g->replay_mu);
                     for (size_t j = 0; j < mine.size(); j++) g->replay_rects[mine[j]->source] = rr[j];
                 }
             }
             auto& pl = payloads[m];
-            for (const auto& page_rects : rr) {
-                const uint64_t cnt = page_rects.size();
+            for (size_t j = 0; j < rr.size(); j++) {
+                const uint64_t cnt = rr[j].size();
                 append_bytes(pl, &cnt, 1);
-                for (const RotatedRect& r : page_rects) {
+                for (const RotatedRect& r : rr[j]) {
                     float a[6];
                     r.to_array(a);
                     append_bytes(pl, a, 6);
+                }
+                if (scored) {
+                    append_bytes(pl, sc.score[j].data(), cnt);
+                    append_bytes(pl, sc.pixels[j].data(), cnt);
                 }
             }
         });
@@ -675,18 +684,41 @@ ocrs_status ocrs_group_detect_words_batch(ocrs_engine_group* g, const ocrs_page*
         // back to page order: a member's pages appear in its payload in ascending page order
         std::vector<Cursor> cur = cursors(all, moffs);
         const std::vector<size_t> mo = member_of_page(of_member, n_pages);
-        std::vector<float> flat;
+        std::vector<float> flat, fscore;
+        std::vector<uint32_t> fpixels;
         offsets[0] = 0;
         for (size_t i = 0; i < n_pages; i++) {
             Cursor& c = cur[mo[i]];
             const uint64_t cnt = c.count();
-            if (cnt > (c.end - c.at) / (6 * sizeof(float))) c.need(SIZE_MAX);
+            if (cnt > (c.end - c.at) / ((scored ? 8 : 6) * sizeof(float))) c.need(SIZE_MAX);
             const float* src = reinterpret_cast<const float*>(c.take(cnt * 6 * sizeof(float)));
             flat.insert(flat.end(), src, src + cnt * 6);
+            if (scored) {
+                fscore.resize(fscore.size() + cnt);
+                fpixels.resize(fpixels.size() + cnt);
+                if (cnt) {   // (memcpy: the payload is byte-packed)
+                    memcpy(fscore.data() + fscore.size() - cnt, c.take(cnt * sizeof(float)), cnt * sizeof(float));
+                    memcpy(fpixels.data() + fpixels.size() - cnt, c.take(cnt * sizeof(uint32_t)), cnt * sizeof(uint32_t));
+                }
+            }
             offsets[i + 1] = flat.size() / 6;
+        }
+        if (scored) {
+            *score = dup_buffer(fscore);
+            *pixels = dup_buffer(fpixels);
         }
         *rects = dup_buffer(flat);
     });
+}
+
+ocrs_status ocrs_group_detect_words_batch(ocrs_engine_group* g, const ocrs_page* const* pages, size_t n_pages, float** rects,
+                                          size_t* offsets) {
+    return group_detect_words_batch(g, pages, n_pages, rects, offsets, false, nullptr, nullptr);
+}
+
+ocrs_status ocrs_group_detect_words_batch_scored(ocrs_engine_group* g, const ocrs_page* const* pages, size_t n_pages, float** rects,
+                                                 size_t* offsets, float** score, uint32_t** pixels) {
+    return group_detect_words_batch(g, pages, n_pages, rects, offsets, true, score, pixels);
 }
 
 ocrs_status ocrs_group_recognize_text_batch(ocrs_engine_group* g, const ocrs_page* const* pages, size_t n_pages,

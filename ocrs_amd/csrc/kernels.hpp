@@ -45,6 +45,8 @@ struct CclBuffers {
     uint8_t* keep;        // [n, arena]
     float* rects;         // [n, max_comp, 6]
     uint8_t* valid;       // [n, max_comp]
+    uint32_t* score_pixels;            // [n, max_comp]  scored requests only (else null): pixels of the slot's component
+    unsigned long long* score_sums;    // [n, max_comp]  ... and the sum of floor(clamp(p, 0, 1) * 2^24) over them
 };
 // mask [n,h,w] -> per page: raster-ordered external components -> rects
 // (find_contours(External) -> simplify_polygon(2) -> min_area_rect -> resize(+2*expand)
@@ -53,6 +55,12 @@ struct CclBuffers {
 void ccl_label(const uint8_t* d_mask, int n, int h, int w, const CclBuffers& b, int max_comp, hipStream_t s, bool prepared = false);
 void contour_rects(const uint8_t* d_mask, int n, int h, int w, const CclBuffers& b, int max_comp, int64_t arena,
                    float expand, float min_area, float eps, hipStream_t s, bool prepared = false);
+
+// (kernels_score.hip)  Per slot of b.roots: the component's pixel count and fixed-point probability sum, into b.score_pixels /
+// b.score_sums (zeroed here).  After ccl_label, on its stream; d_map: the page-resolution probabilities [n, h, w] the mask
+// was thresholded from.  A page whose roots overflowed max_comp is left at zero (it is re-run, like its rects).
+void component_scores(const uint8_t* d_mask, const float* d_map, int n, int h, int w, const CclBuffers& b, int max_comp,
+                      hipStream_t s);
 
 // ---- kernels_nn.hip -------------------------------------------------------
 // C[M,N] = act(A[M,K] . B[K,N] + bias[N]) as an exact fp32 MFMA chain, k ascending.

@@ -268,11 +268,13 @@ struct WordInfo {  // cached per-word quantities for group_into_lines
     float ledge_cx, redge_cx;
     float ledge_y0, ledge_y1, redge_y0, redge_y1;  // y-extent of the downwards() edges
     int32_t cx_i;
+    size_t index;  // position in the caller's list
 };
 
-// layout_analysis.rs:19-71
+// layout_analysis.rs:19-71.  index (optional): shaped like the result, each word's position in `rects`.
 std::vector<std::vector<RotatedRect>> group_into_lines(const std::vector<RotatedRect>& rects,
-                                                       const std::vector<LineF>& separators) {
+                                                       const std::vector<LineF>& separators,
+                                                       std::vector<std::vector<size_t>>* index = nullptr) {
     std::vector<WordInfo> ws;
     ws.reserve(rects.size());
     for (const RotatedRect& r : rects) {
@@ -285,6 +287,7 @@ std::vector<std::vector<RotatedRect>> group_into_lines(const std::vector<Rotated
         w.ledge_y0 = le.start.y; w.ledge_y1 = le.end.y;
         w.redge_y0 = re.start.y; w.redge_y1 = re.end.y;
         w.cx_i = as_i32(r.cx);
+        w.index = ws.size();
         ws.push_back(w);
     }
     std::stable_sort(ws.begin(), ws.end(), [](const WordInfo& a, const WordInfo& b) { return a.left_i < b.left_i; });
@@ -304,14 +307,17 @@ std::vector<std::vector<RotatedRect>> group_into_lines(const std::vector<Rotated
     const float max_h_overlap = 5.0f;
     std::vector<char> used(ws.size(), 0);
     std::vector<std::vector<RotatedRect>> lines;
+    if (index) index->clear();
     size_t first_unused = 0;
     while (true) {
         while (first_unused < ws.size() && used[first_unused]) first_unused++;
         if (first_unused >= ws.size()) break;
         std::vector<RotatedRect> line;
+        std::vector<size_t> line_index;
         size_t last_i = first_unused;
         used[last_i] = 1;
         line.push_back(ws[last_i].rect);
+        line_index.push_back(ws[last_i].index);
         while (true) {
             const WordInfo& last = ws[last_i];
             long best = -1;
@@ -347,9 +353,11 @@ std::vector<std::vector<RotatedRect>> group_into_lines(const std::vector<Rotated
             if (best < 0) break;
             used[best] = 1;
             line.push_back(ws[best].rect);
+            line_index.push_back(ws[best].index);
             last_i = (size_t)best;
         }
         lines.push_back(std::move(line));
+        if (index) index->push_back(std::move(line_index));
     }
     return lines;
 }
@@ -411,7 +419,8 @@ std::vector<Rect> find_block_separators(const std::vector<RotatedRect>& words) {
 }
 
 // layout_analysis.rs:158-233
-std::vector<std::vector<RotatedRect>> find_text_lines(const std::vector<RotatedRect>& words) {
+std::vector<std::vector<RotatedRect>> find_text_lines(const std::vector<RotatedRect>& words,
+                                                      std::vector<std::vector<size_t>>* index) {
     const std::vector<Rect> separators = find_block_separators(words);
     std::vector<LineF> vertical, horizontal;
     for (const Rect& r : separators) {
@@ -419,10 +428,23 @@ std::vector<std::vector<RotatedRect>> find_text_lines(const std::vector<RotatedR
         vertical.push_back(LineF{PointF{(float)c.x, (float)r.top}, PointF{(float)c.x, (float)r.bottom}});
         horizontal.push_back(LineF{PointF{(float)r.left, (float)c.y}, PointF{(float)r.right, (float)c.y}});
     }
-    auto lines = group_into_lines(words, vertical);
-    std::stable_sort(lines.begin(), lines.end(), [](const auto& a, const auto& b) {
-        return as_i32(midpoint_line(a).center().y) < as_i32(midpoint_line(b).center().y);
-    });
+    std::vector<std::vector<size_t>> lines_index;
+    auto lines = group_into_lines(words, vertical, index ? &lines_index : nullptr);
+    {   // stable sort by the midpoint line's y; done on an order vector so that the index lists follow the lines
+        std::vector<int32_t> key(lines.size());
+        std::vector<size_t> ord(lines.size());
+        for (size_t i = 0; i < lines.size(); i++) { key[i] = as_i32(midpoint_line(lines[i]).center().y); ord[i] = i; }
+        std::stable_sort(ord.begin(), ord.end(), [&](size_t a, size_t b) { return key[a] < key[b]; });
+        std::vector<std::vector<RotatedRect>> sorted(lines.size());
+        std::vector<std::vector<size_t>> sorted_index(lines_index.size());
+        for (size_t i = 0; i < ord.size(); i++) {
+            sorted[i] = std::move(lines[ord[i]]);
+            if (index) sorted_index[i] = std::move(lines_index[ord[i]]);
+        }
+        lines.swap(sorted);
+        lines_index.swap(sorted_index);
+    }
+    if (index) index->clear();
 
     auto is_separated_by = [&](const LineF& a, const LineF& b) {
         LineF a_to_b{a.center(), b.center()};
@@ -437,6 +459,7 @@ std::vector<std::vector<RotatedRect>> find_text_lines(const std::vector<RotatedR
         if (used[seed]) continue;
         used[seed] = 1;
         out.push_back(lines[seed]);
+        if (index) index->push_back(lines_index[seed]);
         LineF prev = midpoint_line(lines[seed]);
         for (size_t i = seed + 1; i < lines.size(); i++) {
             if (used[i]) continue;
@@ -444,6 +467,7 @@ std::vector<std::vector<RotatedRect>> find_text_lines(const std::vector<RotatedR
             if (prev.horizontal_overlap(cand) > 0.0f && !is_separated_by(prev, cand)) {
                 used[i] = 1;
                 out.push_back(lines[i]);
+                if (index) index->push_back(lines_index[i]);
                 prev = cand;
             }
         }
