@@ -134,6 +134,8 @@ OCRS_API ocrs_status ocrs_coalescer_selftest(int n_threads, int requests_per_thr
  *   "conv_flat"       recognition 3x3 convs: the 128-pixel patches tile a width group's strip of images side by side
  *                     (1, default: only a group's last patch is ragged) or every image on its own (0)
  *   "beam_gpu"        1 = DecodeMethod::BeamSearch runs on the GPU (default), 0 = on the host (threaded over lines)
+ *   "det_tile_batch"  tiled detection (ocrs_engine_detect_words_tiled ...): tiles per run of the detection model, 1 .. 1024
+ *                     (default 16); bounds the activation memory of a request whatever its page sizes, never changes a result
  *
  * OCRS_ERR_INVALID_ARGUMENT for an unknown name.  (Rounds 2-4 carried 28 process-wide options, many of them switches for
  * experiments that had lost their A/B; round 5 removed those kernels and moved what is configuration — numerics, request
@@ -336,6 +338,33 @@ OCRS_API ocrs_status ocrs_engine_detect_words_batch_scored(const ocrs_engine* e,
 /* OcrEngine::detect_text_pixels (lib.rs:207-213 -> detection.rs:131-200):
  * writes the [H,W] probability map. */
 OCRS_API ocrs_status ocrs_engine_detect_text_pixels(const ocrs_engine* e, const ocrs_page* page, float* out_hw);
+
+/* Tiled detection, opt-in per call: a page larger than the detection model's input Hm x Wm is not squeezed
+ * into it but cut into Hm x Wm tiles at its own resolution; the tiles run through the model as a batch (about one detector
+ * run per tile) and every page pixel takes its probability from the one tile that owns it.  From that map on the call is the
+ * untiled one.  Along an axis of page length L and model length M, with overlap v (0 <= v <= min(Hm, Wm) / 2, integer
+ * arithmetic): L <= M: one tile at 0 owning [0, L).  Else n = ceil((L - v) / (M - v)) tiles at o_i = (i * (L - M)) / (n - 1),
+ * tile i owning [b_i, b_i+1) with b_0 = 0, b_n = L, b_i = (o_i-1 + M + o_i) / 2.  Tiles of a page: rows x columns, row-major.
+ * A tile's input is the page cut at its origin, -0.5 where it reaches past the page; nothing is ever resized.  A page no
+ * larger than the model input has one tile and the results of the untiled call, bit for bit.  A page's result never depends
+ * on the rest of the batch or on "det_tile_batch".
+ * overlap: pixels; negative = OCRS_TILE_OVERLAP_DEFAULT (a value chosen on synthetic weights, not a claim about real
+ * models); beyond min(Hm, Wm) / 2: OCRS_ERR_INVALID_ARGUMENT.  Tiled requests are never merged with concurrent requests.
+ * A caller-implemented model (ocrs_model_from_callback) is run once per tile, in tile order within the caller's page order.
+ *
+ * ocrs_detection_tile_plan: the plan the engine uses (host only, no GPU): *ny x *nx tiles; origin_y [ny], bound_y [ny + 1],
+ * origin_x [nx], bound_x [nx + 1], malloc'ed int32 (ocrs_buffer_free). */
+#define OCRS_TILE_OVERLAP_DEFAULT 100
+OCRS_API ocrs_status ocrs_detection_tile_plan(int page_h, int page_w, int model_h, int model_w, int overlap, size_t* ny, size_t* nx,
+                                              int32_t** origin_y, int32_t** bound_y, int32_t** origin_x, int32_t** bound_x);
+/* Output as ocrs_engine_detect_words[_batch]_scored; score and pixels may BOTH be NULL (then nothing extra is allocated or
+ * launched, as in the unscored calls). */
+OCRS_API ocrs_status ocrs_engine_detect_words_tiled(const ocrs_engine* e, const ocrs_page* page, int overlap, float** rects, size_t* n,
+                                                    float** score, uint32_t** pixels);
+OCRS_API ocrs_status ocrs_engine_detect_words_batch_tiled(const ocrs_engine* e, const ocrs_page* const* pages, size_t n_pages, int overlap,
+                                                          float** rects, size_t* offsets, float** score, uint32_t** pixels);
+/* The stitched [H,W] probability map of the tiled call. */
+OCRS_API ocrs_status ocrs_engine_detect_text_pixels_tiled(const ocrs_engine* e, const ocrs_page* page, int overlap, float* out_hw);
 
 /* OcrEngine::detection_threshold (lib.rs:282-287). */
 OCRS_API float ocrs_engine_detection_threshold(const ocrs_engine* e);
@@ -549,6 +578,10 @@ OCRS_API ocrs_status ocrs_group_detect_words_batch(ocrs_engine_group* g, const o
  * the per-request payload next to the rects, through either gather transport. */
 OCRS_API ocrs_status ocrs_group_detect_words_batch_scored(ocrs_engine_group* g, const ocrs_page* const* pages, size_t n_pages,
                                                           float** rects, size_t* offsets, float** score, uint32_t** pixels);
+/* Tiled detection (ocrs_engine_detect_words_batch_tiled) with every page on the member of its device; score and pixels may
+ * both be NULL.  Results are gathered as the scored call gathers them. */
+OCRS_API ocrs_status ocrs_group_detect_words_batch_tiled(ocrs_engine_group* g, const ocrs_page* const* pages, size_t n_pages, int overlap,
+                                                         float** rects, size_t* offsets, float** score, uint32_t** pixels);
 /* OcrEngine::recognize_text (lib.rs:237-256); arguments and output as ocrs_engine_recognize_text_batch.
  * (find_text_lines is host work: ocrs_engine_find_text_lines_batch serves a group as it is.) */
 OCRS_API ocrs_status ocrs_group_recognize_text_batch(ocrs_engine_group* g, const ocrs_page* const* pages, size_t n_pages,

@@ -311,14 +311,44 @@ def _take(ptr, n, dtype):
     return out
 
 
-def _detect_words_batch(name, handle, inputs, scores):
-    """ocrs_{engine,group}_detect_words_batch[_scored] (name without the suffix) -> rects per page [, score per page,
-    pixels per page]."""
+def _tile_overlap(tiled):
+    """The `tiled` keyword of the detection calls -> None (untiled) or the overlap argument of the _tiled entry points:
+    False / None: untiled; True: the default overlap (-1); an int: that many pixels (0 is a valid overlap)."""
+    if tiled is False or tiled is None:
+        return None
+    if tiled is True:
+        return -1
+    v = int(tiled)
+    if v < 0:
+        raise ValueError("tiled: an overlap in pixels, or True for the default")
+    return v
+
+
+def tile_plan(page_hw, model_hw, overlap=None):
+    """ocrs_detection_tile_plan (host only): the tiles a page of page_hw is cut into for a detection model whose input is
+    model_hw -> (origin_y [ny], bound_y [ny + 1], origin_x [nx], bound_x [nx + 1]), int32.  Tile (i, j)
+    starts at (origin_y[i], origin_x[j]) and owns rows bound_y[i] .. bound_y[i + 1], columns bound_x[j] .. bound_x[j + 1].
+    overlap=None: the default (_lib.TILE_OVERLAP_DEFAULT)."""
+    ny, nx = C.c_size_t(0), C.c_size_t(0)
+    p = [C.POINTER(C.c_int32)() for _ in range(4)]
+    check(lib().ocrs_detection_tile_plan(int(page_hw[0]), int(page_hw[1]), int(model_hw[0]), int(model_hw[1]),
+                                         -1 if overlap is None else int(overlap), C.byref(ny), C.byref(nx), *[C.byref(x) for x in p]))
+    return tuple(_take(x, k, np.int32) for x, k in zip(p, (ny.value, ny.value + 1, nx.value, nx.value + 1)))
+
+
+def _detect_words_batch(name, handle, inputs, scores, tiled=False):
+    """ocrs_{engine,group}_detect_words_batch[_scored | _tiled] (name without the suffix) -> rects per page [, score per
+    page, pixels per page]."""
     n = len(inputs)
     pages = (C.c_void_p * n)(*[i._h for i in inputs])
     rects = C.POINTER(C.c_float)()
     offs = (C.c_size_t * (n + 1))()
-    if scores:
+    overlap = _tile_overlap(tiled)
+    if overlap is not None:
+        sc, px = C.POINTER(C.c_float)(), C.POINTER(C.c_uint32)()
+        check(getattr(lib(), name + "_tiled")(handle, pages, C.c_size_t(n), C.c_int(overlap), C.byref(rects), offs,
+                                              C.byref(sc) if scores else None, C.byref(px) if scores else None))
+    elif scores:
         sc, px = C.POINTER(C.c_float)(), C.POINTER(C.c_uint32)()
         check(getattr(lib(), name + "_scored")(handle, pages, C.c_size_t(n), C.byref(rects), offs, C.byref(sc), C.byref(px)))
     else:
@@ -440,12 +470,19 @@ class OcrEngine:
         return OcrInput(h_out), cb.value
 
     # ---- lib.rs:193-199
-    def detect_words(self, inp, scores=False):
+    def detect_words(self, inp, scores=False, tiled=False):
         """scores=True: through ocrs_engine_detect_words_scored -> (words, score float32 [n], pixels uint32 [n]): per word
-        the mean text probability of its component's pixels and their number."""
+        the mean text probability of its component's pixels and their number.
+        tiled=True | <overlap>: through ocrs_engine_detect_words_tiled: the page is cut into model-sized tiles at its own
+        resolution instead of being resized to the model input (about one detector run per tile)."""
         rects = C.POINTER(C.c_float)()
         n = C.c_size_t(0)
-        if scores:
+        overlap = _tile_overlap(tiled)
+        if overlap is not None:
+            sc, px = C.POINTER(C.c_float)(), C.POINTER(C.c_uint32)()
+            check(lib().ocrs_engine_detect_words_tiled(self._h, inp._h, C.c_int(overlap), C.byref(rects), C.byref(n),
+                                                       C.byref(sc) if scores else None, C.byref(px) if scores else None))
+        elif scores:
             sc, px = C.POINTER(C.c_float)(), C.POINTER(C.c_uint32)()
             check(lib().ocrs_engine_detect_words_scored(self._h, inp._h, C.byref(rects), C.byref(n), C.byref(sc), C.byref(px)))
         else:
@@ -456,15 +493,20 @@ class OcrEngine:
             return out
         return out, _take(sc, n.value, np.float32), _take(px, n.value, np.uint32)
 
-    def detect_words_batch(self, inputs, scores=False):
-        """scores=True: -> (words per page, score per page, pixels per page)."""
-        return _detect_words_batch("ocrs_engine_detect_words_batch", self._h, inputs, scores)
+    def detect_words_batch(self, inputs, scores=False, tiled=False):
+        """scores=True: -> (words per page, score per page, pixels per page).  tiled: as detect_words."""
+        return _detect_words_batch("ocrs_engine_detect_words_batch", self._h, inputs, scores, tiled)
 
     # ---- lib.rs:207-213
-    def detect_text_pixels(self, inp):
+    def detect_text_pixels(self, inp, tiled=False):
+        """tiled=True | <overlap>: the stitched map of the tiled call."""
         _, h, w = inp.shape
         out = np.empty((h, w), np.float32)
-        check(lib().ocrs_engine_detect_text_pixels(self._h, inp._h, out.ctypes.data_as(C.POINTER(C.c_float))))
+        overlap = _tile_overlap(tiled)
+        if overlap is not None:
+            check(lib().ocrs_engine_detect_text_pixels_tiled(self._h, inp._h, C.c_int(overlap), out.ctypes.data_as(C.POINTER(C.c_float))))
+        else:
+            check(lib().ocrs_engine_detect_text_pixels(self._h, inp._h, out.ctypes.data_as(C.POINTER(C.c_float))))
         return out
 
     # ---- lib.rs:222-228
@@ -846,9 +888,9 @@ class EngineGroup:
                                                           h, w, c, out))
         return [OcrInput(C.c_void_p(out[i])) for i in range(n)]
 
-    def detect_words_batch(self, inputs, scores=False):
-        """scores=True: -> (words per page, score per page, pixels per page), as OcrEngine.detect_words_batch."""
-        return _detect_words_batch("ocrs_group_detect_words_batch", self._h, inputs, scores)
+    def detect_words_batch(self, inputs, scores=False, tiled=False):
+        """scores=True: -> (words per page, score per page, pixels per page), as OcrEngine.detect_words_batch; tiled likewise."""
+        return _detect_words_batch("ocrs_group_detect_words_batch", self._h, inputs, scores, tiled)
 
     def find_text_lines_batch_raw(self, words_per_page, index=False):
         return self.member(0)[0].find_text_lines_batch_raw(words_per_page, index=index)   # host work: any engine handle serves

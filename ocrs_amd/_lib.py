@@ -76,9 +76,12 @@ DECLARED_SYMBOLS = [
     "ocrs_engine_run_recognition_ops",
     "ocrs_engine_detect_words_scored", "ocrs_engine_detect_words_batch_scored", "ocrs_group_detect_words_batch_scored",
     "ocrs_engine_find_text_lines_indexed", "ocrs_engine_find_text_lines_batch_indexed",
+    "ocrs_detection_tile_plan", "ocrs_engine_detect_words_tiled", "ocrs_engine_detect_words_batch_tiled",
+    "ocrs_engine_detect_text_pixels_tiled", "ocrs_group_detect_words_batch_tiled",
 ]
 
 ABI_VERSION = 6   # include/ocrs_amd.h OCRS_ABI_VERSION
+TILE_OVERLAP_DEFAULT = 100   # include/ocrs_amd.h OCRS_TILE_OVERLAP_DEFAULT
 
 _lib = None
 

@@ -51,6 +51,10 @@ def main(argv=None):
                          "DESIGN.md 7.1)")
     ap.add_argument("--min-word-score", type=float, metavar="X",
                     help="drop detected words whose detection confidence is below X before lines are formed")
+    ap.add_argument("--tiled", nargs="?", type=int, const=-1, default=None, metavar="OVERLAP",
+                    help="tiled detection for pages larger than the detector's input: the page is cut into model-sized tiles "
+                         "at its own resolution, OVERLAP pixels shared between neighbours (default 100), instead of being "
+                         "resized; about one detector run per tile (no reference counterpart: DESIGN.md 7.2)")
     ap.add_argument("-o", "--output")
     ap.add_argument("--debug", action="store_true")
     ap.add_argument("--text-map", action="store_true", help="write text-map.png (detect_text_pixels)")
@@ -92,15 +96,16 @@ def main(argv=None):
         img = load_image(args.image)
         shape_hw = img.shape[:2]
         inp = engine.prepare_input(ImageSource.from_tensor(img, DimOrder.Hwc))
+    tiled = False if args.tiled is None else True if args.tiled < 0 else args.tiled
     if args.text_map or args.text_mask:
-        tm = engine.detect_text_pixels(inp)
+        tm = engine.detect_text_pixels(inp, tiled=tiled)
         if args.text_map:
             write_image("text-map.png", tm)
         if args.text_mask:
             write_image("text-mask.png", (tm > np.float32(engine.detection_threshold())).astype(np.float32))
     word_boxes = None
     if args.detection_confidence or args.min_word_score is not None:
-        words, wscore, wpixels = engine.detect_words(inp, scores=True)
+        words, wscore, wpixels = engine.detect_words(inp, scores=True, tiled=tiled)
         if args.min_word_score is not None:
             keep = wscore >= np.float32(args.min_word_score)
             words, wscore, wpixels = words[keep], wscore[keep], wpixels[keep]
@@ -108,7 +113,7 @@ def main(argv=None):
         if args.detection_confidence:
             word_boxes = [[(words[k], wscore[k], wpixels[k]) for k in idx] for idx in index]
     else:
-        words = engine.detect_words(inp)
+        words = engine.detect_words(inp, tiled=tiled)
         lines = engine.find_text_lines(inp, words)
     if args.text_line_images:  # main.rs:66-86
         os.makedirs("lines", exist_ok=True)

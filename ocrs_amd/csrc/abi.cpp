@@ -540,15 +540,15 @@ ocrs_status ocrs_page_image(const ocrs_page* p, float* out_hw) {
 
 namespace {
 
-// ocrs_engine_detect_words[_batch][_scored]: score / pixels null for the unscored calls
+// ocrs_engine_detect_words[_batch][_scored | _tiled]: score / pixels null for the unscored calls; tile_overlap < 0: untiled
 ocrs_status detect_words_batch(const ocrs_engine* e, const ocrs_page* const* pages, size_t n_pages, float** rects,
-                               size_t* offsets, bool scored, float** score, uint32_t** pixels) {
+                               size_t* offsets, bool scored, float** score, uint32_t** pixels, int tile_overlap = -1) {
     return guarded_engine(e, [&] {
         if (!e || !pages || !rects || !offsets || (scored && (!score || !pixels))) fail(OCRS_ERR_INVALID_ARGUMENT, "null argument");
         check_pages_on(e, pages, n_pages);
         std::vector<std::vector<RotatedRect>> rr;
         DetScores sc;
-        e->detect(pages, n_pages, &rr, nullptr, scored ? &sc : nullptr);
+        e->detect(pages, n_pages, &rr, nullptr, scored ? &sc : nullptr, tile_overlap);
         std::vector<float> flat, fscore;
         std::vector<uint32_t> fpixels;
         offsets[0] = 0;
@@ -604,6 +604,49 @@ ocrs_status ocrs_engine_detect_text_pixels(const ocrs_engine* e, const ocrs_page
         if (!e || !page || !out_hw) fail(OCRS_ERR_INVALID_ARGUMENT, "null argument");
         check_pages_on(e, &page, 1);
         e->detect(&page, 1, nullptr, out_hw);
+    });
+}
+
+// ---- tiled detection
+ocrs_status ocrs_detection_tile_plan(int page_h, int page_w, int model_h, int model_w, int overlap, size_t* ny, size_t* nx,
+                                     int32_t** origin_y, int32_t** bound_y, int32_t** origin_x, int32_t** bound_x) {
+    return guarded([&] {
+        if (!ny || !nx || !origin_y || !bound_y || !origin_x || !bound_x) fail(OCRS_ERR_INVALID_ARGUMENT, "null argument");
+        if (page_h <= 0 || page_w <= 0 || model_h <= 0 || model_w <= 0)
+            fail(OCRS_ERR_INVALID_ARGUMENT, "tile plan: page %d x %d, model input %d x %d", page_h, page_w, model_h, model_w);
+        const int v = overlap < 0 ? OCRS_TILE_OVERLAP_DEFAULT : overlap;
+        if (v > std::min(model_h, model_w) / 2)
+            fail(OCRS_ERR_INVALID_ARGUMENT, "tile overlap %d: at most half the model input's shorter side (%d)", v, std::min(model_h, model_w) / 2);
+        const TileAxisPlan py = tile_axis_plan(page_h, model_h, v), px = tile_axis_plan(page_w, model_w, v);
+        *ny = py.origin.size();
+        *nx = px.origin.size();
+        *origin_y = dup_buffer(py.origin);
+        *bound_y = dup_buffer(py.bound);
+        *origin_x = dup_buffer(px.origin);
+        *bound_x = dup_buffer(px.bound);
+    });
+}
+
+ocrs_status ocrs_engine_detect_words_batch_tiled(const ocrs_engine* e, const ocrs_page* const* pages, size_t n_pages, int overlap,
+                                                 float** rects, size_t* offsets, float** score, uint32_t** pixels) {
+    if (!score != !pixels) return guarded([&] { fail(OCRS_ERR_INVALID_ARGUMENT, "score and pixels come together"); });
+    return detect_words_batch(e, pages, n_pages, rects, offsets, score != nullptr, score, pixels,
+                              overlap < 0 ? OCRS_TILE_OVERLAP_DEFAULT : overlap);
+}
+
+ocrs_status ocrs_engine_detect_words_tiled(const ocrs_engine* e, const ocrs_page* page, int overlap, float** rects, size_t* n,
+                                           float** score, uint32_t** pixels) {
+    size_t offs[2] = {0, 0};
+    ocrs_status s = ocrs_engine_detect_words_batch_tiled(e, &page, page ? 1 : 0, overlap, rects, offs, score, pixels);
+    if (s == OCRS_OK && n) *n = offs[1];
+    return s;
+}
+
+ocrs_status ocrs_engine_detect_text_pixels_tiled(const ocrs_engine* e, const ocrs_page* page, int overlap, float* out_hw) {
+    return guarded_engine(e, [&] {
+        if (!e || !page || !out_hw) fail(OCRS_ERR_INVALID_ARGUMENT, "null argument");
+        check_pages_on(e, &page, 1);
+        e->detect(&page, 1, nullptr, out_hw, nullptr, overlap < 0 ? OCRS_TILE_OVERLAP_DEFAULT : overlap);
     });
 }
 

@@ -441,6 +441,7 @@ const OptDef kOptDefs[OPT_COUNT] = {
     {"conv12_fuse", "OCRS_CONV12_FUSE", 1},             // first two recognition convs (+ their pools) in one kernel
     {"conv_flat", "OCRS_CONV_FLAT", 1},                 // recognition 3x3 convs: patches tile a width group's whole strip of images (0: every image on its own)
     {"beam_gpu", "OCRS_BEAM_GPU", 1},                   // 1 CTC beam search on the GPU, 0 on the host
+    {"det_tile_batch", "OCRS_DET_TILE_BATCH", 16},      // tiled detection: tiles per model run (bounds a request's activation memory)
     // not options: ocrs_engine_params fields (no name, no environment variable)
     // (ocrs_engine_set_option accepts these names too, except numerics: an engine's numerics are fixed when it is created)
     {"numerics", nullptr, 0},                           // exact
@@ -455,6 +456,7 @@ const OptDef kOptDefs[OPT_COUNT] = {
 struct OptRange { long lo, hi; long also[4]; };
 const OptRange kOptRanges[OPT_COUNT] = {
     {0, 1, {}}, {0, 1, {}}, {0, 1, {}}, {0, 2, {}}, {0, 1, {8, 14, 32}}, {0, 1, {8, 14, 20, 32}}, {0, 1, {}}, {0, 1, {}}, {0, 1, {}}, {0, 1, {}},
+    {1, 1024, {}},
     {0, 2, {}}, {0, 64, {}}, {1, 4096, {}}, {0, 10000000, {}}, {0, 4096, {}}, {0, INT64_MAX, {}},
 };
 bool in_range(int i, long v) {

@@ -11,10 +11,31 @@ using namespace ocrs;
 using namespace ocrs::geom;
 
 // ===========================================================================
+// Tiled detection: the plan
+// ===========================================================================
+TileAxisPlan ocrs::tile_axis_plan(int L, int M, int v) {
+    if (L <= 0 || M <= 0 || v < 0 || v > M / 2) fail(OCRS_ERR_INVALID_ARGUMENT, "tile plan: length %d, model length %d, overlap %d", L, M, v);
+    TileAxisPlan p;
+    if (L <= M) {
+        p.origin = {0};
+        p.bound = {0, L};
+        return p;
+    }
+    const int n = (L - v + (M - v) - 1) / (M - v);   // the fewest tiles whose neighbours overlap by at least v (n >= 2)
+    p.origin.resize(n);
+    p.bound.resize(n + 1);
+    for (int i = 0; i < n; i++) p.origin[i] = (int32_t)(((int64_t)i * (L - M)) / (n - 1));
+    p.bound[0] = 0;
+    p.bound[n] = L;
+    for (int i = 1; i < n; i++) p.bound[i] = (p.origin[i - 1] + M + p.origin[i]) / 2;   // the middle of the overlap of tiles i - 1 and i
+    return p;
+}
+
+// ===========================================================================
 // Detection — detection.rs:104-200
 // ===========================================================================
 void ocrs_engine::detect_now(const ocrs_page* const* pages, size_t n, std::vector<std::vector<RotatedRect>>* rects_out,
-                             float* host_map, DetScores* scores) const {
+                             float* host_map, DetScores* scores, int tile_overlap) const {
     if (!detection) fail(OCRS_ERR_MODEL_NOT_LOADED, "Detection model not loaded");
     if (scores && !rects_out) fail(OCRS_ERR_INVALID_ARGUMENT, "detection scores come with the rects");
     if (n == 0) {
@@ -26,6 +47,11 @@ void ocrs_engine::detect_now(const ocrs_page* const* pages, size_t n, std::vecto
     if (in_h64 <= 0 || in_w64 <= 0) fail(OCRS_ERR_MODEL_DIMS, "failed to get model dims");  // detection.rs:141-144
     const int in_h = (int)in_h64, in_w = (int)in_w64;
     const int N = (int)n;
+    // tiled: the pages are not resized; their model-sized tiles run through the model in chunks and are
+    // stitched into the page-resolution mask / map that the code after resize_threshold works on
+    const bool tiled = tile_overlap >= 0;
+    if (tiled && tile_overlap > std::min(in_h, in_w) / 2)
+        fail(OCRS_ERR_INVALID_ARGUMENT, "tile overlap %d: at most half the model input's shorter side (%d)", tile_overlap, std::min(in_h, in_w) / 2);
     // The reference takes any image per call (detection.rs:131-171) and the model always runs at its own fixed size, so a
     // batch may hold pages of SEVERAL sizes (r6; the coalescer merges whatever waits): the model runs once over all of them,
     // the size-dependent kernels before and after it (resize in; resize back + threshold, components, contours) run once per
@@ -78,11 +104,28 @@ void ocrs_engine::detect_now(const ocrs_page* const* pages, size_t n, std::vecto
     // page pointer table, grouped order
     std::vector<const float*> hp(n);
     for (size_t i = 0; i < n; i++) hp[i] = pages[order[i]]->grey.as<float>();
-    const float** d_ptrs = ws.alloc_n<const float*>(n);
-    ws.upload(d_ptrs, hp.data(), n * sizeof(float*));
+    const float** d_ptrs = tiled ? nullptr : ws.alloc_n<const float*>(n);
+    if (!tiled) ws.upload(d_ptrs, hp.data(), n * sizeof(float*));
 
-    float* d_in = ws.alloc_n<float>((size_t)N * in_h * in_w);
-    {
+    // `trait Model` implemented by the caller: one run per model input, host tensors (detection.rs:184)
+    auto run_callback = [&](const float* d_src, float* d_dst) {
+        const auto* cb = static_cast<const CallbackModel*>(detection);
+        std::vector<float> hin((size_t)in_h * in_w), hout;
+        ws.download(hin.data(), d_src, hin.size() * sizeof(float));
+        ws.sync();
+        const int64_t ishape[4] = {1, 1, in_h, in_w};
+        int64_t oshape[4];
+        int ond = 0;
+        cb->run(hin.data(), ishape, hout, oshape, &ond);
+        if (ond != 4 || oshape[2] != in_h || oshape[3] != in_w || oshape[0] * oshape[1] != 1)
+            fail(OCRS_ERR_WRONG_OUTPUT, "model output had unexpected type or shape: detection output is not [1,1,%d,%d]",
+                 in_h, in_w);
+        OCRS_HIP(hipMemcpyAsync(d_dst, hout.data(), hout.size() * sizeof(float), hipMemcpyHostToDevice, st));
+        ws.sync();
+    };
+
+    float* d_in = tiled ? nullptr : ws.alloc_n<float>((size_t)N * in_h * in_w);
+    if (!tiled) {
         StageScope sc(T, ST_RESIZE_IN, ex, groups.size());
         for (SizeGroup& g : groups) {
             g.pad_bottom = std::max(in_h - g.h, 0);   // detection.rs:155-156
@@ -93,26 +136,14 @@ void ocrs_engine::detect_now(const ocrs_page* const* pages, size_t n, std::vecto
     }
 
     const float* d_prob = nullptr;
-    if (detection->is_callback()) {
-        // `trait Model` implemented by the caller: one run per page, host tensors (detection.rs:184).
-        const auto* cb = static_cast<const CallbackModel*>(detection);
-        std::vector<float> hin((size_t)in_h * in_w), hout;
+    if (tiled) {
+        // the model runs per chunk of tiles, once the pages' masks exist (below)
+    } else if (detection->is_callback()) {
         float* d_out = ws.alloc_n<float>((size_t)N * in_h * in_w);
         for (int oi = 0; oi < N; oi++) {
             int i = 0;
             while (order[i] != oi) i++;      // runs in the CALLER's page order (a caller's model may count its runs)
-            ws.download(hin.data(), d_in + (size_t)i * in_h * in_w, hin.size() * sizeof(float));
-            ws.sync();
-            const int64_t ishape[4] = {1, 1, in_h, in_w};
-            int64_t oshape[4];
-            int ond = 0;
-            cb->run(hin.data(), ishape, hout, oshape, &ond);
-            if (ond != 4 || oshape[2] != in_h || oshape[3] != in_w || oshape[0] * oshape[1] != 1)
-                fail(OCRS_ERR_WRONG_OUTPUT, "model output had unexpected type or shape: detection output is not [1,1,%d,%d]",
-                     in_h, in_w);
-            OCRS_HIP(hipMemcpyAsync(d_out + (size_t)i * in_h * in_w, hout.data(), hout.size() * sizeof(float),
-                                    hipMemcpyHostToDevice, st));
-            ws.sync();
+            run_callback(d_in + (size_t)i * in_h * in_w, d_out + (size_t)i * in_h * in_w);
         }
         d_prob = d_out;
     } else {
@@ -171,7 +202,7 @@ void ocrs_engine::detect_now(const ocrs_page* const* pages, size_t n, std::vecto
     float* d_map = host_map ? ws.alloc_n<float>((size_t)N * groups[0].h * groups[0].w) : nullptr;
     std::vector<char> prepared(groups.size(), 0);
     {
-        StageScope sc(T, ST_RESIZE_THRESH, ex, groups.size());
+        StageScope sc(T, ST_RESIZE_THRESH, ex, tiled ? 0 : groups.size());
         for (size_t gi = 0; gi < groups.size(); gi++) {
             SizeGroup& g = groups[gi];
             g.px = (int64_t)g.h * g.w;
@@ -183,9 +214,61 @@ void ocrs_engine::detect_now(const ocrs_page* const* pages, size_t n, std::vecto
             }
             // a scored request keeps every size's map (host_map: one size, one array)
             g.d_map = d_map ? d_map : scores ? ws.alloc_n<float>((size_t)g.count * g.px) : nullptr;
+            if (tiled) {   // stitch_threshold fills the mask and the map; the component stage takes its unprepared path
+                if (rects_out) OCRS_HIP(hipMemsetAsync(g.b.overflow, 0, g.count * sizeof(int32_t), ex));
+                continue;
+            }
             prepared[gi] = k::resize_threshold(d_prob + (size_t)g.first * in_h * in_w, g.count, in_h, in_w, in_h - g.pad_bottom, in_w - g.pad_right,
                                                text_threshold, g.d_mask, g.d_map, g.h, g.w, ex, g.b.labels, g.b.overflow, g.b.offsets);
             if (rects_out && !prepared[gi]) OCRS_HIP(hipMemsetAsync(g.b.overflow, 0, g.count * sizeof(int32_t), ex));
+        }
+    }
+    if (tiled) {
+        // Tiles of the whole request in the caller's page order, row-major within a page (a caller's model sees them in that
+        // order); gather -> model -> stitch per chunk of at most det_tile_batch tiles, so the activations of a request are
+        // bounded whatever the page size.  Owned rectangles are disjoint: chunks need no ordering among themselves.
+        std::vector<k::TileDesc> tiles;
+        for (int oi = 0; oi < N; oi++) {
+            int i = 0;
+            while (order[i] != oi) i++;
+            const SizeGroup& g = groups[group_of[i]];
+            const TileAxisPlan py = tile_axis_plan(g.h, in_h, tile_overlap), px = tile_axis_plan(g.w, in_w, tile_overlap);
+            const size_t at = (size_t)(i - g.first) * g.px;
+            for (size_t ty = 0; ty < py.origin.size(); ty++)
+                for (size_t tx = 0; tx < px.origin.size(); tx++)
+                    tiles.push_back(k::TileDesc{hp[i], g.d_mask + at, g.d_map ? g.d_map + at : nullptr, g.h, g.w, py.origin[ty], px.origin[tx],
+                                                py.bound[ty], py.bound[ty + 1], px.bound[tx], px.bound[tx + 1]});
+        }
+        k::TileDesc* d_tiles = ws.alloc_n<k::TileDesc>(tiles.size());
+        ws.upload(d_tiles, tiles.data(), tiles.size() * sizeof(k::TileDesc));
+        const size_t chunk = (size_t)std::max(1, option(OPT_DET_TILE_BATCH)), tile_px = (size_t)in_h * in_w;
+        float* d_tin = ws.alloc_n<float>(std::min(chunk, tiles.size()) * tile_px);
+        float* d_tout = detection->is_callback() ? ws.alloc_n<float>(std::min(chunk, tiles.size()) * tile_px) : nullptr;
+        const size_t mark = ws.bufs.size();
+        for (size_t c0 = 0; c0 < tiles.size(); c0 += chunk) {
+            const int nt = (int)std::min(chunk, tiles.size() - c0);
+            {
+                StageScope sc(T, ST_RESIZE_IN, ex);
+                k::gather_tiles(d_tiles + c0, nt, d_tin, in_h, in_w, ex);
+            }
+            const float* d_tp = d_tout;
+            if (d_tout) {
+                for (int t = 0; t < nt; t++) run_callback(d_tin + (size_t)t * tile_px, d_tout + (size_t)t * tile_px);
+            } else {
+                TensorShape os;
+                d_tp = static_cast<const HipModel*>(detection)->run_device(ws, d_tin, nt, in_h, in_w, &os, T, nullptr, nullptr, true, debug, -1, nullptr);
+                if (os.n != nt || os.h != in_h || os.w != in_w || os.c != 1)
+                    fail(OCRS_ERR_WRONG_OUTPUT, "model output had unexpected type or shape: detection output [%d,%d,%d,%d]", os.n,
+                         os.c, os.h, os.w);
+            }
+            {
+                StageScope sc(T, ST_RESIZE_THRESH, ex);
+                k::stitch_threshold(d_tiles + c0, nt, d_tp, in_h, in_w, text_threshold, ex);
+            }
+            if (c0 + chunk < tiles.size()) {   // the next chunk reuses this one's activations: drain, then hand them back
+                ws.sync();
+                while (ws.bufs.size() > mark) ws.bufs.pop_back();
+            }
         }
     }
     if (host_map)   // (one size group: grouped order = the caller's order)
@@ -410,13 +493,14 @@ void ocrs_engine::init_coalescers() {
 }
 
 void ocrs_engine::detect(const ocrs_page* const* pages, size_t n, std::vector<std::vector<RotatedRect>>* rects_out,
-                         float* host_map, DetScores* scores) const {
+                         float* host_map, DetScores* scores, int tile_overlap) const {
     const int max_active = option(OPT_COALESCE);   // (r4: 4 / 6 / 12 detection batches in flight instead of 2: 188-193 pages/s from 12 threads either way)
     const size_t max_pages = (size_t)std::max(1, option(OPT_COALESCE_PAGES));
     // merged only where it cannot be observed: HIP executor (a caller's `trait Model` sees every run), rects only
+    // (a tiled request is a batch of its own tiles already: never merged, never waits)
     if (max_active <= 0 || !det_queue || !rects_out || host_map || n == 0 || 2 * n >= max_pages || !detection ||
-        detection->is_callback() || debug) {
-        detect_now(pages, n, rects_out, host_map, scores);
+        detection->is_callback() || debug || tile_overlap >= 0) {
+        detect_now(pages, n, rects_out, host_map, scores, tile_overlap);
         return;
     }
     DetRequest r;

@@ -62,6 +62,15 @@ struct DetScores {
     std::vector<std::vector<uint32_t>> pixels;  // pixels of that component
 };
 
+// Tiled detection: the plan along one axis of page length L for a model of length M and overlap v,
+// 0 <= v <= M / 2.  L <= M: one tile.  Else n = ceil((L - v) / (M - v)) tiles with origins (i * (L - M)) / (n - 1) — the first at 0,
+// the last ending at L — and ownership bounds in the middle of the neighbours' overlaps: tile i owns [bound[i], bound[i + 1]).
+struct TileAxisPlan {
+    std::vector<int32_t> origin;   // [n]
+    std::vector<int32_t> bound;    // [n + 1], bound[0] = 0, bound[n] = L
+};
+TileAxisPlan tile_axis_plan(int L, int M, int v);
+
 // One caller's detection / recognition request while it waits in the engine's coalescer (coalesce.hpp).
 struct DetRequest : CoalescedBase {
     const ocrs_page* const* pages = nullptr;
@@ -116,10 +125,12 @@ struct ocrs_engine {
     // "coalesce_pages") that only want rects are merged with concurrent ones (coalesce.hpp); results are those of
     // detect_now on the caller's pages alone.
     // scores (optional, with rects): per word the component's score and pixel count; null allocates and launches nothing extra.
+    // tile_overlap >= 0: tiled detection with that overlap — pages are cut into model-sized tiles at their own
+    // resolution instead of being resized; such a request is never merged with others.  < 0: the untiled call.
     void detect(const ocrs_page* const* pages, size_t n, std::vector<std::vector<ocrs::geom::RotatedRect>>* rects,
-                float* host_map /* [n,h,w] or null */, ocrs::DetScores* scores = nullptr) const;
+                float* host_map /* [n,h,w] or null */, ocrs::DetScores* scores = nullptr, int tile_overlap = -1) const;
     void detect_now(const ocrs_page* const* pages, size_t n, std::vector<std::vector<ocrs::geom::RotatedRect>>* rects,
-                    float* host_map, ocrs::DetScores* scores = nullptr) const;
+                    float* host_map, ocrs::DetScores* scores = nullptr, int tile_overlap = -1) const;
 
     // recognition.rs:404-540 over the lines of several pages; small requests are merged likewise.
     void recognize(const ocrs_page* const* pages, size_t n_pages,

@@ -630,13 +630,15 @@ ocrs_status ocrs_group_prepare_input_device_batch(const ocrs_engine_group* g, co
     return guarded([&] { group_prepare(const_cast<ocrs_engine_group*>(g), d_pixels, n, true, type, order, height, width, channels, out); });
 }
 
-// ocrs_group_detect_words_batch[_scored]: score / pixels null for the unscored call, whose payload is unchanged
+// ocrs_group_detect_words_batch[_scored | _tiled]: score / pixels null for the unscored call, whose payload is unchanged;
+// tile_overlap < 0: untiled
 static ocrs_status group_detect_words_batch(ocrs_engine_group* g, const ocrs_page* const* pages, size_t n_pages, float** rects,
-                                            size_t* offsets, bool scored, float** score, uint32_t** pixels) {
+                                            size_t* offsets, bool scored, float** score, uint32_t** pixels, int tile_overlap = -1) {
     return guarded([&] {
         if (!g || !rects || !offsets || (n_pages && !pages) || (scored && (!score || !pixels)))
             fail(OCRS_ERR_INVALID_ARGUMENT, "null argument");
         if (scored && g->replay_mode == 2) fail(OCRS_ERR_INVALID_ARGUMENT, "replay: detection scores are not recorded");
+        if (tile_overlap >= 0 && g->replay_mode != 0) fail(OCRS_ERR_INVALID_ARGUMENT, "replay: tiled detection is not recorded");
         const auto of_member = deal_pages(g, pages, n_pages);
         const size_t G = g->size();
         // member m's payload: for each of its pages (in page order) [u64 word count | count x 6 f32], and in a scored
@@ -658,7 +660,7 @@ static ocrs_status group_detect_words_batch(ocrs_engine_group* g, const ocrs_pag
                 }
                 std::this_thread::sleep_for(std::chrono::duration<double>(g->replay_s[1]));
             } else {
-                g->members[m].engine->detect(mine.data(), mine.size(), &rr, nullptr, scored ? &sc : nullptr);
+                g->members[m].engine->detect(mine.data(), mine.size(), &rr, nullptr, scored ? &sc : nullptr, tile_overlap);
                 if (g->replay_mode == 1) {
                     std::lock_guard<std::mutex> lk(g->replay_mu);
                     for (size_t j = 0; j < mine.size(); j++) g->replay_rects[mine[j]->source] = rr[j];
@@ -719,6 +721,13 @@ ocrs_status ocrs_group_detect_words_batch(ocrs_engine_group* g, const ocrs_page*
 ocrs_status ocrs_group_detect_words_batch_scored(ocrs_engine_group* g, const ocrs_page* const* pages, size_t n_pages, float** rects,
                                                  size_t* offsets, float** score, uint32_t** pixels) {
     return group_detect_words_batch(g, pages, n_pages, rects, offsets, true, score, pixels);
+}
+
+ocrs_status ocrs_group_detect_words_batch_tiled(ocrs_engine_group* g, const ocrs_page* const* pages, size_t n_pages, int overlap,
+                                                float** rects, size_t* offsets, float** score, uint32_t** pixels) {
+    if (!score != !pixels) return guarded([&] { fail(OCRS_ERR_INVALID_ARGUMENT, "score and pixels come together"); });
+    return group_detect_words_batch(g, pages, n_pages, rects, offsets, score != nullptr, score, pixels,
+                                    overlap < 0 ? OCRS_TILE_OVERLAP_DEFAULT : overlap);
 }
 
 ocrs_status ocrs_group_recognize_text_batch(ocrs_engine_group* g, const ocrs_page* const* pages, size_t n_pages,

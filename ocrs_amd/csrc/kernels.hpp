@@ -62,6 +62,20 @@ void contour_rects(const uint8_t* d_mask, int n, int h, int w, const CclBuffers&
 void component_scores(const uint8_t* d_mask, const float* d_map, int n, int h, int w, const CclBuffers& b, int max_comp,
                       hipStream_t s);
 
+// ---- kernels_tile.hip: tiled detection --------------------
+struct TileDesc {          // one model-sized tile of a page, cut at the page's own resolution
+    const float* page;     // [h, w] grey page
+    uint8_t* mask;         // [h, w] the page's text mask
+    float* map;            // [h, w] the page's probability map, or null
+    int32_t h, w;
+    int32_t oy, ox;        // tile origin in the page
+    int32_t y0, y1, x0, x1;   // the page pixels this tile owns: oy <= y0 < y1 <= min(oy + mh, h), likewise x
+};
+// d_dst[t] = the [mh, mw] model input of tile t: page[oy + r, ox + c] inside the page, -0.5 outside; tiles of any mix of pages
+void gather_tiles(const TileDesc* d_tiles, int n_tiles, float* d_dst, int mh, int mw, hipStream_t s);
+// d_prob [n_tiles, mh, mw]: every tile writes the pixels it owns: mask = p > thr (strict) and, where map is set, p
+void stitch_threshold(const TileDesc* d_tiles, int n_tiles, const float* d_prob, int mh, int mw, float thr, hipStream_t s);
+
 // ---- kernels_nn.hip -------------------------------------------------------
 // C[M,N] = act(A[M,K] . B[K,N] + bias[N]) as an exact fp32 MFMA chain, k ascending.
 struct GemmDesc {
