@@ -471,6 +471,48 @@ OCRS_API ocrs_status ocrs_rotated_rect_corners(const float rect6[6], float out8[
 OCRS_API ocrs_status ocrs_engine_prepare_recognition_input(const ocrs_engine* e, const ocrs_page* page, const float* line,
                                                   size_t n_words, float** out, int* height, int* width);
 
+/* ------------------------------------------------------------------------
+ * Rectified line crops (no reference counterpart, opt-in).  The crop of the calls above takes the
+ * axis-aligned bounding box of the line polygon, so a skewed line of width W and height h is cropped from a box of
+ * height h + W |sin theta| and squeezed.  The _rectified calls crop every line along its own axis instead: the axis is the
+ * least-squares line through the word centres (the first word's direction for one word or equal centre columns), the
+ * frame the extent of the words' corners along and across it, and the crop a bilinear gather through an affine map,
+ * masked per column to the rows its words span.  Everything after the crop — width groups, the model, decoding,
+ * scores — is that of the plain calls.  Scope: skew that find_text_lines still groups into lines (a few tens of degrees).
+ *
+ * ocrs_line_frame (host only, no GPU): the frame of one line of n_words rects for a recogniser of input height
+ * rec_height.  axis = (a.x, a.y); extents = (s_min, s_max, t_min, t_max), the corners' projections on a and on the normal
+ * (-a.y, a.x); *resized_width = resized_line_width(ceil(s_max - s_min), ceil(t_max - t_min), rec_height); coef = the
+ * map's (x0, ax, bx, y0, ay, by): output pixel (oy, ox) samples the page at X = (x0 + ax (ox + .5)) + bx (oy + .5), Y
+ * likewise, in float32; ranges (optional, [n_words][4]) = every word's (c0, c1, r0, r1) of the mask, c0 > c1 for a word
+ * that covers nothing.  *empty = 1 for a degenerate line (a value that is not finite, or a frame without width or height):
+ * its crop is all -0.5 at the width the plain crop gives a bounding box with a side of zero, it has no char boxes, and
+ * the other outputs are zero.
+ * ocrs_line_char_boxes (host only): the page boxes of that line's chars from the CTC steps' positions (ascending) of a
+ * model output of ctc_input_len steps: rects_tlbr [n_steps][4], kept [n_steps] (0: the char starts in the padding and is
+ * dropped).  A char's box is the bounding box of its slice of the frame, so TextLine::rotated_rect and the JSON vertices
+ * work from these as they do from the plain call's. */
+OCRS_API ocrs_status ocrs_line_frame(const float* words, size_t n_words, int rec_height, double axis[2], double extents[4],
+                                     uint32_t* resized_width, float coef[6], int32_t* ranges, int* empty);
+OCRS_API ocrs_status ocrs_line_char_boxes(const float* words, size_t n_words, int rec_height, uint32_t ctc_input_len,
+                                          const uint32_t* positions, size_t n_steps, int32_t* rects_tlbr, uint8_t* kept);
+/* ocrs_engine_prepare_recognition_input / ocrs_engine_recognize_text[_batch] with rectified crops.  char_logp and
+ * line_score: the outputs of the _scored calls, or both NULL.  One-page calls of both kinds may be merged into one batch
+ * (option "coalesce"); each caller's lines are cropped its way and its results are those of its call alone. */
+OCRS_API ocrs_status ocrs_engine_prepare_recognition_input_rectified(const ocrs_engine* e, const ocrs_page* page, const float* line,
+                                                                     size_t n_words, float** out, int* height, int* width);
+OCRS_API ocrs_status ocrs_engine_recognize_text_rectified(const ocrs_engine* e, const ocrs_page* page, const float* line_rects,
+                                                          const size_t* line_offsets, size_t n_lines, ocrs_text_char** chars,
+                                                          size_t** char_offsets, float** char_logp, double** line_score);
+OCRS_API ocrs_status ocrs_engine_recognize_text_batch_rectified(const ocrs_engine* e, const ocrs_page* const* pages, size_t n_pages,
+                                                                const size_t* page_line_offsets, const float* line_rects,
+                                                                const size_t* line_offsets, size_t n_lines, ocrs_text_char** chars,
+                                                                size_t** char_offsets, float** char_logp, double** line_score);
+/* ocrs_engine_recognize_tokens over rectified crops: the raw CTC steps the char boxes come from. */
+OCRS_API ocrs_status ocrs_engine_recognize_tokens_rectified(const ocrs_engine* e, const ocrs_page* page, const float* line_rects,
+                                                            const size_t* line_offsets, size_t n_lines, uint32_t** labels,
+                                                            uint32_t** positions, size_t** token_offsets);
+
 /* OcrEngine::get_text (lib.rs:290-300): UTF-8, lines joined by '\n'. */
 OCRS_API ocrs_status ocrs_engine_get_text(const ocrs_engine* e, const ocrs_page* page, char** text);
 
@@ -588,6 +630,11 @@ OCRS_API ocrs_status ocrs_group_recognize_text_batch(ocrs_engine_group* g, const
                                                      const size_t* page_line_offsets, const float* line_rects,
                                                      const size_t* line_offsets, size_t n_lines, ocrs_text_char** chars,
                                                      size_t** char_offsets);
+/* The same with rectified crops (ocrs_engine_recognize_text_batch_rectified); not recorded by the replay mode. */
+OCRS_API ocrs_status ocrs_group_recognize_text_batch_rectified(ocrs_engine_group* g, const ocrs_page* const* pages, size_t n_pages,
+                                                               const size_t* page_line_offsets, const float* line_rects,
+                                                               const size_t* line_offsets, size_t n_lines, ocrs_text_char** chars,
+                                                               size_t** char_offsets);
 /* The per-request gather on its own: payloads[m] / bytes[m] = member m's packed bytes (host memory); *out receives
  * their concatenation in member order through the group's per-request transport, offsets[G + 1] the boundaries. */
 OCRS_API ocrs_status ocrs_group_gather(ocrs_engine_group* g, const void* const* payloads, const size_t* bytes, void** out,

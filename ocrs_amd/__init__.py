@@ -15,7 +15,7 @@ from . import _lib
 from ._lib import OcrsError, check, lib
 
 __all__ = ["OcrEngine", "OcrEngineParams", "ImageSource", "ImageSourceError", "DimOrder", "DecodeMethod", "Model",
-           "OcrInput", "TextLine", "TextWord", "TextChar", "OcrsError", "DEFAULT_ALPHABET", "EngineGroup"]
+           "OcrInput", "TextLine", "TextWord", "TextChar", "OcrsError", "DEFAULT_ALPHABET", "EngineGroup", "line_frame"]
 
 # lib.rs:34 (with the EUR sign the comment at lib.rs:33 asks for)
 DEFAULT_ALPHABET = " 0123456789!\"#$%&'()*+,-./:;<=>?@[\\]^_`{|}~€ABCDEFGHIJKLMNOPQRSTUVWXYZabcdefghijklmnopqrstuvwxyz"
@@ -336,6 +336,39 @@ def tile_plan(page_hw, model_hw, overlap=None):
     return tuple(_take(x, k, np.int32) for x, k in zip(p, (ny.value, ny.value + 1, nx.value, nx.value + 1)))
 
 
+class LineFrame:
+    """ocrs_line_frame's outputs: empty, axis float64 [2], extents float64 [4] (s_min, s_max, t_min,
+    t_max), rw, coef float32 [6] (x0, ax, bx, y0, ay, by), ranges int32 [n, 4] (c0, c1, r0, r1 per word)."""
+    __slots__ = ("empty", "axis", "extents", "rw", "coef", "ranges")
+
+
+def line_frame(words, rec_height=64):
+    """ocrs_line_frame (host only): the frame a rectified crop gives one line of word rects for a recogniser of input
+    height rec_height."""
+    a = _rects_to_array(words)
+    axis, ext, coef = np.zeros(2, np.float64), np.zeros(4, np.float64), np.zeros(6, np.float32)
+    ranges = np.zeros((len(a), 4), np.int32)
+    rw, empty = C.c_uint32(0), C.c_int(0)
+    check(lib().ocrs_line_frame(a.ctypes.data_as(C.POINTER(C.c_float)), C.c_size_t(len(a)), C.c_int(int(rec_height)),
+                                axis.ctypes.data_as(C.POINTER(C.c_double)), ext.ctypes.data_as(C.POINTER(C.c_double)), C.byref(rw),
+                                coef.ctypes.data_as(C.POINTER(C.c_float)), ranges.ctypes.data_as(C.POINTER(C.c_int32)), C.byref(empty)))
+    f = LineFrame()
+    f.empty, f.axis, f.extents, f.rw, f.coef, f.ranges = bool(empty.value), axis, ext, int(rw.value), coef, ranges
+    return f
+
+
+def line_char_boxes(words, ctc_input_len, positions, rec_height=64):
+    """ocrs_line_char_boxes (host only): the page boxes of a rectified line's chars from its CTC steps' positions ->
+    (rects int32 [n, 4] (top, left, bottom, right), kept bool [n])."""
+    a = _rects_to_array(words)
+    pos = np.ascontiguousarray(positions, np.uint32)
+    rects, kept = np.zeros((len(pos), 4), np.int32), np.zeros(len(pos), np.uint8)
+    check(lib().ocrs_line_char_boxes(a.ctypes.data_as(C.POINTER(C.c_float)), C.c_size_t(len(a)), C.c_int(int(rec_height)),
+                                     C.c_uint32(int(ctc_input_len)), pos.ctypes.data_as(C.POINTER(C.c_uint32)), C.c_size_t(len(pos)),
+                                     rects.ctypes.data_as(C.POINTER(C.c_int32)), kept.ctypes.data_as(C.POINTER(C.c_uint8))))
+    return rects, kept.astype(bool)
+
+
 def _detect_words_batch(name, handle, inputs, scores, tiled=False):
     """ocrs_{engine,group}_detect_words_batch[_scored | _tiled] (name without the suffix) -> rects per page [, score per
     page, pixels per page]."""
@@ -561,11 +594,11 @@ class OcrEngine:
             return rects, loffs, poffs, _take(wi, len(allw), np.uintp).astype(np.int64)
         return rects, loffs, poffs
 
-    def recognize_text_batch_raw(self, inputs, rects, line_offsets, page_line_offsets, scores=False):
+    def recognize_text_batch_raw(self, inputs, rects, line_offsets, page_line_offsets, scores=False, rectify=False):
         """Packed form of recognize_text_batch: returns (chars, char_offsets) where chars is a
         structured array (ch, top, left, bottom, right) and line i owns chars[char_offsets[i]:char_offsets[i+1]].
         scores=True: returns (chars, char_offsets, char_logp float32 [len(chars)], line_score float64 [lines]), every
-        line scored, those without text included."""
+        line scored, those without text included.  rectify=True: rectified crops."""
         n = len(inputs)
         pages = (C.c_void_p * n)(*[i._h for i in inputs])
         rects = np.ascontiguousarray(rects, np.float32)
@@ -579,6 +612,10 @@ class OcrEngine:
                 C.byref(chars), C.byref(coffs)]
         if scores:
             clp, lsc = C.POINTER(C.c_float)(), C.POINTER(C.c_double)()
+        if rectify:
+            check(lib().ocrs_engine_recognize_text_batch_rectified(*args, C.byref(clp) if scores else None,
+                                                                   C.byref(lsc) if scores else None))
+        elif scores:
             check(lib().ocrs_engine_recognize_text_batch_scored(*args, C.byref(clp), C.byref(lsc)))
         else:
             check(lib().ocrs_engine_recognize_text_batch(*args))
@@ -601,9 +638,10 @@ class OcrEngine:
         return arr, co, char_logp, line_score
 
     # ---- lib.rs:237-256
-    def recognize_text(self, inp, lines, scores=False):
+    def recognize_text(self, inp, lines, scores=False, rectify=False):
         """OcrEngine::recognize_text (lib.rs:237-256) through the single-page entry point a Rust binding uses.
-        scores=True: through ocrs_engine_recognize_text_scored; every TextChar gets its logp, every TextLine its score."""
+        scores=True: through ocrs_engine_recognize_text_scored; every TextChar gets its logp, every TextLine its score.
+        rectify=True: through ocrs_engine_recognize_text_rectified: every line is cropped along its own axis."""
         rects, offs = _pack_lines(lines)
         chars = C.POINTER(_lib.TextCharC)()
         coffs = C.POINTER(C.c_size_t)()
@@ -612,6 +650,9 @@ class OcrEngine:
         clp = lsc = None
         if scores:
             clp, lsc = C.POINTER(C.c_float)(), C.POINTER(C.c_double)()
+        if rectify:
+            check(lib().ocrs_engine_recognize_text_rectified(*args, C.byref(clp) if scores else None, C.byref(lsc) if scores else None))
+        elif scores:
             check(lib().ocrs_engine_recognize_text_scored(*args, C.byref(clp), C.byref(lsc)))
         else:
             check(lib().ocrs_engine_recognize_text(*args))
@@ -621,7 +662,7 @@ class OcrEngine:
                 lib().ocrs_buffer_free(p)
         return out
 
-    def recognize_text_batch(self, inputs, lines_per_page, scores=False):
+    def recognize_text_batch(self, inputs, lines_per_page, scores=False, rectify=False):
         n = len(inputs)
         pages = (C.c_void_p * n)(*[i._h for i in inputs])
         all_lines = [l for lines in lines_per_page for l in lines]
@@ -638,6 +679,10 @@ class OcrEngine:
         clp = lsc = None
         if scores:
             clp, lsc = C.POINTER(C.c_float)(), C.POINTER(C.c_double)()
+        if rectify:
+            check(lib().ocrs_engine_recognize_text_batch_rectified(*args, C.byref(clp) if scores else None,
+                                                                   C.byref(lsc) if scores else None))
+        elif scores:
             check(lib().ocrs_engine_recognize_text_batch_scored(*args, C.byref(clp), C.byref(lsc)))
         else:
             check(lib().ocrs_engine_recognize_text_batch(*args))
@@ -654,15 +699,16 @@ class OcrEngine:
                 lib().ocrs_buffer_free(p)
         return result
 
-    def recognize_tokens(self, inp, lines):
-        """Raw greedy-CTC output per line: list of (label, pos) — CtcHypothesis::steps()."""
+    def recognize_tokens(self, inp, lines, rectify=False):
+        """Raw greedy-CTC output per line: list of (label, pos) — CtcHypothesis::steps().  rectify=True: over rectified
+        crops."""
         rects, offs = _pack_lines(lines)
         lab = C.POINTER(C.c_uint32)()
         pos = C.POINTER(C.c_uint32)()
         toff = C.POINTER(C.c_size_t)()
-        check(lib().ocrs_engine_recognize_tokens(self._h, inp._h, rects.ctypes.data_as(C.POINTER(C.c_float)),
-                                                 offs.ctypes.data_as(C.POINTER(C.c_size_t)), C.c_size_t(len(lines)),
-                                                 C.byref(lab), C.byref(pos), C.byref(toff)))
+        fn = lib().ocrs_engine_recognize_tokens_rectified if rectify else lib().ocrs_engine_recognize_tokens
+        check(fn(self._h, inp._h, rects.ctypes.data_as(C.POINTER(C.c_float)),
+                 offs.ctypes.data_as(C.POINTER(C.c_size_t)), C.c_size_t(len(lines)), C.byref(lab), C.byref(pos), C.byref(toff)))
         out = []
         for i in range(len(lines)):
             out.append([(int(lab[k]), int(pos[k])) for k in range(toff[i], toff[i + 1])])
@@ -716,12 +762,13 @@ class OcrEngine:
         return res
 
     # ---- lib.rs:268-278
-    def prepare_recognition_input(self, inp, line):
+    def prepare_recognition_input(self, inp, line, rectify=False):
+        """rectify=True: the rectified crop through ocrs_engine_prepare_recognition_input_rectified."""
         a = _rects_to_array(line)
         out = C.POINTER(C.c_float)()
         h, w = C.c_int(0), C.c_int(0)
-        check(lib().ocrs_engine_prepare_recognition_input(self._h, inp._h, a.ctypes.data_as(C.POINTER(C.c_float)),
-                                                          C.c_size_t(len(a)), C.byref(out), C.byref(h), C.byref(w)))
+        fn = lib().ocrs_engine_prepare_recognition_input_rectified if rectify else lib().ocrs_engine_prepare_recognition_input
+        check(fn(self._h, inp._h, a.ctypes.data_as(C.POINTER(C.c_float)), C.c_size_t(len(a)), C.byref(out), C.byref(h), C.byref(w)))
         img = np.ctypeslib.as_array(out, shape=(max(h.value * w.value, 1),))[: h.value * w.value].reshape(h.value, w.value).copy()
         lib().ocrs_buffer_free(out)
         return img
@@ -731,7 +778,11 @@ class OcrEngine:
         return float(lib().ocrs_engine_detection_threshold(self._h))
 
     # ---- lib.rs:290-300
-    def get_text(self, inp):
+    def get_text(self, inp, rectify=False):
+        """rectify=True: the same sequence (detect_words, find_text_lines, recognize_text) with rectified crops."""
+        if rectify:
+            lines = self.find_text_lines(inp, self.detect_words(inp))
+            return "\n".join(str(t) for t in self.recognize_text(inp, lines, rectify=True) if t is not None)
         txt = C.c_char_p()
         check(lib().ocrs_engine_get_text(self._h, inp._h, C.byref(txt)))
         s = txt.value.decode("utf-8")
@@ -895,7 +946,8 @@ class EngineGroup:
     def find_text_lines_batch_raw(self, words_per_page, index=False):
         return self.member(0)[0].find_text_lines_batch_raw(words_per_page, index=index)   # host work: any engine handle serves
 
-    def recognize_text_batch_raw(self, inputs, rects, line_offsets, page_line_offsets):
+    def recognize_text_batch_raw(self, inputs, rects, line_offsets, page_line_offsets, rectify=False):
+        """rectify=True: through ocrs_group_recognize_text_batch_rectified."""
         n = len(inputs)
         pages = (C.c_void_p * n)(*[i._h for i in inputs])
         rects = np.ascontiguousarray(rects, np.float32)
@@ -904,7 +956,8 @@ class EngineGroup:
         nl = len(lo) - 1
         chars = C.POINTER(_lib.TextCharC)()
         coffs = C.POINTER(C.c_size_t)()
-        check(lib().ocrs_group_recognize_text_batch(
+        fn = lib().ocrs_group_recognize_text_batch_rectified if rectify else lib().ocrs_group_recognize_text_batch
+        check(fn(
             self._h, pages, C.c_size_t(n), po.ctypes.data_as(C.POINTER(C.c_size_t)),
             rects.ctypes.data_as(C.POINTER(C.c_float)), lo.ctypes.data_as(C.POINTER(C.c_size_t)), C.c_size_t(nl),
             C.byref(chars), C.byref(coffs)))

@@ -78,6 +78,9 @@ DECLARED_SYMBOLS = [
     "ocrs_engine_find_text_lines_indexed", "ocrs_engine_find_text_lines_batch_indexed",
     "ocrs_detection_tile_plan", "ocrs_engine_detect_words_tiled", "ocrs_engine_detect_words_batch_tiled",
     "ocrs_engine_detect_text_pixels_tiled", "ocrs_group_detect_words_batch_tiled",
+    "ocrs_line_frame", "ocrs_line_char_boxes", "ocrs_engine_prepare_recognition_input_rectified",
+    "ocrs_engine_recognize_text_rectified", "ocrs_engine_recognize_text_batch_rectified",
+    "ocrs_group_recognize_text_batch_rectified", "ocrs_engine_recognize_tokens_rectified",
 ]
 
 ABI_VERSION = 6   # include/ocrs_amd.h OCRS_ABI_VERSION

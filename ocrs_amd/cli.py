@@ -55,6 +55,9 @@ def main(argv=None):
                     help="tiled detection for pages larger than the detector's input: the page is cut into model-sized tiles "
                          "at its own resolution, OVERLAP pixels shared between neighbours (default 100), instead of being "
                          "resized; about one detector run per tile (no reference counterpart: DESIGN.md 7.2)")
+    ap.add_argument("--rectify", action="store_true",
+                    help="crop every text line along its own axis instead of from its axis-aligned bounding box: for skewed "
+                         "scans (no reference counterpart: DESIGN.md 8.4); also applies to --text-line-images")
     ap.add_argument("-o", "--output")
     ap.add_argument("--debug", action="store_true")
     ap.add_argument("--text-map", action="store_true", help="write text-map.png (detect_text_pixels)")
@@ -118,8 +121,8 @@ def main(argv=None):
     if args.text_line_images:  # main.rs:66-86
         os.makedirs("lines", exist_ok=True)
         for i, line in enumerate(lines):
-            write_image("lines/line-%d.png" % i, engine.prepare_recognition_input(inp, line) + np.float32(0.5))
-    texts = engine.recognize_text(inp, lines, scores=args.confidence)
+            write_image("lines/line-%d.png" % i, engine.prepare_recognition_input(inp, line, rectify=args.rectify) + np.float32(0.5))
+    texts = engine.recognize_text(inp, lines, scores=args.confidence, rectify=args.rectify)
     if args.json:
         content = output.format_json_output(args.image, tuple(shape_hw), texts, confidence=args.confidence, word_boxes=word_boxes)
     else:

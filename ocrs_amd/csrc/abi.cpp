@@ -770,7 +770,7 @@ namespace {
 // ocrs_engine_recognize_text[_batch][_scored]: char_logp / line_score null for the unscored calls
 ocrs_status recognize_text_batch(const ocrs_engine* e, const ocrs_page* const* pages, size_t n_pages, const size_t* page_line_offsets,
                                  const float* line_rects, const size_t* line_offsets, size_t n_lines, ocrs_text_char** chars,
-                                 size_t** char_offsets, float** char_logp, double** line_score) {
+                                 size_t** char_offsets, float** char_logp, double** line_score, bool rectify = false) {
     return guarded_engine(e, [&] {
         if (!e || !pages || !page_line_offsets || !line_offsets || !chars || !char_offsets)
             fail(OCRS_ERR_INVALID_ARGUMENT, "null argument");
@@ -784,7 +784,7 @@ ocrs_status recognize_text_batch(const ocrs_engine* e, const ocrs_page* const* p
         std::vector<uint32_t> ctc_len;
         const bool scored = char_logp != nullptr;
         RecScores sc;
-        e->recognize(pages, n_pages, lpp, &steps, &rl, &ctc_len, scored ? &sc : nullptr);
+        e->recognize(pages, n_pages, lpp, &steps, &rl, &ctc_len, scored ? &sc : nullptr, rectify);
         std::vector<ocrs_text_char> flat;
         std::vector<size_t> offs{0};
         std::vector<float> flat_lp, lp;
@@ -838,9 +838,57 @@ ocrs_status ocrs_engine_recognize_text_scored(const ocrs_engine* e, const ocrs_p
                                                    char_logp, line_score);
 }
 
-ocrs_status ocrs_engine_recognize_tokens(const ocrs_engine* e, const ocrs_page* page, const float* line_rects,
-                                         const size_t* line_offsets, size_t n_lines, uint32_t** labels,
-                                         uint32_t** positions, size_t** token_offsets) {
+ocrs_status ocrs_engine_recognize_text_batch_rectified(const ocrs_engine* e, const ocrs_page* const* pages, size_t n_pages,
+                                                       const size_t* page_line_offsets, const float* line_rects,
+                                                       const size_t* line_offsets, size_t n_lines, ocrs_text_char** chars,
+                                                       size_t** char_offsets, float** char_logp, double** line_score) {
+    if (!char_logp != !line_score) return guarded([] { fail(OCRS_ERR_INVALID_ARGUMENT, "char_logp and line_score come together"); });
+    return recognize_text_batch(e, pages, n_pages, page_line_offsets, line_rects, line_offsets, n_lines, chars, char_offsets,
+                                char_logp, line_score, true);
+}
+
+ocrs_status ocrs_engine_recognize_text_rectified(const ocrs_engine* e, const ocrs_page* page, const float* line_rects,
+                                                 const size_t* line_offsets, size_t n_lines, ocrs_text_char** chars,
+                                                 size_t** char_offsets, float** char_logp, double** line_score) {
+    size_t plo[2] = {0, n_lines};
+    return ocrs_engine_recognize_text_batch_rectified(e, &page, 1, plo, line_rects, line_offsets, n_lines, chars, char_offsets,
+                                                      char_logp, line_score);
+}
+
+ocrs_status ocrs_line_frame(const float* words, size_t n_words, int rec_height, double axis[2], double extents[4], uint32_t* resized_width,
+                            float coef[6], int32_t* ranges, int* empty) {
+    return guarded([&] {
+        if (!words || !axis || !extents || !resized_width || !coef || !empty) fail(OCRS_ERR_INVALID_ARGUMENT, "null argument");
+        const LineFrame f = line_frame(words, n_words, rec_height);
+        axis[0] = f.ax; axis[1] = f.ay;
+        extents[0] = f.s_min; extents[1] = f.s_max; extents[2] = f.t_min; extents[3] = f.t_max;
+        *resized_width = f.rw;
+        for (int i = 0; i < 6; i++) coef[i] = f.coef[i];
+        if (ranges) std::copy(f.ranges.begin(), f.ranges.end(), ranges);
+        *empty = f.empty ? 1 : 0;
+    });
+}
+
+ocrs_status ocrs_line_char_boxes(const float* words, size_t n_words, int rec_height, uint32_t ctc_input_len, const uint32_t* positions,
+                                 size_t n_steps, int32_t* rects_tlbr, uint8_t* kept) {
+    return guarded([&] {
+        if (!words || (n_steps && (!positions || !rects_tlbr || !kept))) fail(OCRS_ERR_INVALID_ARGUMENT, "null argument");
+        const LineFrame f = line_frame(words, n_words, rec_height);
+        for (size_t i = 0; i < n_steps; i++) {
+            kept[i] = 0;
+            for (int q = 0; q < 4; q++) rects_tlbr[4 * i + q] = 0;
+        }
+        for (const auto& kv : rectified_char_boxes(f, (f.rw + 49) / 50 * 50, ctc_input_len, positions, n_steps)) {
+            kept[kv.first] = 1;
+            const int32_t r[4] = {kv.second.top, kv.second.left, kv.second.bottom, kv.second.right};
+            std::copy(r, r + 4, rects_tlbr + 4 * kv.first);
+        }
+    });
+}
+
+static ocrs_status recognize_tokens(const ocrs_engine* e, const ocrs_page* page, const float* line_rects,
+                                    const size_t* line_offsets, size_t n_lines, uint32_t** labels,
+                                    uint32_t** positions, size_t** token_offsets, bool rectify) {
     return guarded_engine(e, [&] {
         if (!e || !page || !line_offsets || !labels || !positions || !token_offsets)
             fail(OCRS_ERR_INVALID_ARGUMENT, "null argument");
@@ -850,7 +898,7 @@ ocrs_status ocrs_engine_recognize_tokens(const ocrs_engine* e, const ocrs_page* 
         std::vector<std::vector<CtcStep>> steps;
         std::vector<RecLine> rl;
         std::vector<uint32_t> ctc_len;
-        e->recognize(&page, 1, lpp, &steps, &rl, &ctc_len);
+        e->recognize(&page, 1, lpp, &steps, &rl, &ctc_len, nullptr, rectify);
         std::vector<uint32_t> fl, fp;
         std::vector<size_t> offs{0};
         for (const auto& s : steps) {
@@ -861,6 +909,18 @@ ocrs_status ocrs_engine_recognize_tokens(const ocrs_engine* e, const ocrs_page* 
         *positions = dup_buffer(fp);
         *token_offsets = dup_buffer(offs);
     });
+}
+
+ocrs_status ocrs_engine_recognize_tokens(const ocrs_engine* e, const ocrs_page* page, const float* line_rects,
+                                         const size_t* line_offsets, size_t n_lines, uint32_t** labels,
+                                         uint32_t** positions, size_t** token_offsets) {
+    return recognize_tokens(e, page, line_rects, line_offsets, n_lines, labels, positions, token_offsets, false);
+}
+
+ocrs_status ocrs_engine_recognize_tokens_rectified(const ocrs_engine* e, const ocrs_page* page, const float* line_rects,
+                                                   const size_t* line_offsets, size_t n_lines, uint32_t** labels,
+                                                   uint32_t** positions, size_t** token_offsets) {
+    return recognize_tokens(e, page, line_rects, line_offsets, n_lines, labels, positions, token_offsets, true);
 }
 
 ocrs_status ocrs_engine_recognize_logits(const ocrs_engine* e, const ocrs_page* page, const float* line_rects,
@@ -950,6 +1010,49 @@ ocrs_status ocrs_engine_prepare_recognition_input(const ocrs_engine* e, const oc
             ws.download(host.data(), d_out, host.size() * 4);
         }
         ws.sync();
+        *out = dup_buffer(host);
+        *height = rec_h;
+        *width = rw;
+    });
+}
+
+ocrs_status ocrs_engine_prepare_recognition_input_rectified(const ocrs_engine* e, const ocrs_page* page, const float* line,
+                                                            size_t n_words, float** out, int* height, int* width) {
+    return guarded_engine(e, [&] {
+        if (!e || !page || !line || !out || !height || !width) fail(OCRS_ERR_INVALID_ARGUMENT, "null argument");
+        check_pages_on(e, &page, 1);
+        if (!e->recognition) fail(OCRS_ERR_MODEL_NOT_LOADED, "Recognition model not loaded");
+        std::vector<RotatedRect> words(n_words);
+        for (size_t i = 0; i < n_words; i++) words[i] = RotatedRect::from_array(line + 6 * i);
+        const RecLine ln = e->make_rec_line(words, 0, 0, true);
+        const int rec_h = (int)e->rec_input_height();
+        const int rw = (int)ln.resized_width, gw = (int)ln.group_width;   // cropped at its group's width: the kernel's rows are even
+        std::vector<float> host((size_t)rec_h * rw);
+        if (rw > 0) {
+            Workspace ws;
+            k::RectLineDesc d{};
+            d.page = 0; d.mode = ln.frame.empty ? 1 : 0; d.range_off = 0;
+            d.range_n = ln.frame.empty ? 0 : (int32_t)(ln.frame.ranges.size() / 4);
+            d.resized_w = rw; d.out_w = gw; d.out_off = 0;
+            d.x0 = ln.frame.coef[0]; d.ax = ln.frame.coef[1]; d.bx = ln.frame.coef[2];
+            d.y0 = ln.frame.coef[3]; d.ay = ln.frame.coef[4]; d.by = ln.frame.coef[5];
+            const float* hp = page->grey.as<float>();
+            const int32_t hw[2] = {page->h, page->w};
+            const float** d_pages = ws.alloc_n<const float*>(1);
+            int32_t* d_hw = ws.alloc_n<int32_t>(2);
+            k::RectLineDesc* d_desc = ws.alloc_n<k::RectLineDesc>(1);
+            int32_t* d_ranges = ws.alloc_n<int32_t>(std::max<size_t>(ln.frame.ranges.size(), 4));
+            float* d_out = ws.alloc_n<float>((size_t)rec_h * gw);
+            OCRS_HIP(hipMemcpyAsync(d_pages, &hp, sizeof hp, hipMemcpyHostToDevice, ws.s()));
+            OCRS_HIP(hipMemcpyAsync(d_hw, hw, sizeof hw, hipMemcpyHostToDevice, ws.s()));
+            OCRS_HIP(hipMemcpyAsync(d_desc, &d, sizeof d, hipMemcpyHostToDevice, ws.s()));
+            OCRS_HIP(hipMemcpyAsync(d_ranges, ln.frame.ranges.data(), ln.frame.ranges.size() * 4, hipMemcpyHostToDevice, ws.s()));
+            k::rectify_lines(d_pages, d_hw, d_desc, d_ranges, 1, gw, rec_h, d_out, ws.s());
+            std::vector<float> full((size_t)rec_h * gw);
+            ws.download(full.data(), d_out, full.size() * 4);
+            ws.sync();
+            for (int y = 0; y < rec_h; y++) std::copy_n(&full[(size_t)y * gw], rw, &host[(size_t)y * rw]);
+        }
         *out = dup_buffer(host);
         *height = rec_h;
         *width = rw;

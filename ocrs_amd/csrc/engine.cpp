@@ -449,22 +449,29 @@ void ocrs_engine::init_coalescers() {
                 [&] {
                     if (batch.size() == 1) {
                         RecRequest& r = *batch[0];
-                        recognize_now(r.pages, r.n_pages, *r.lines_per_page, r.steps, r.rec_lines, r.ctc_len, nullptr, r.scores);
+                        const std::vector<char> rp(r.rectify ? r.n_pages : 0, 1);
+                        recognize_now(r.pages, r.n_pages, *r.lines_per_page, r.steps, r.rec_lines, r.ctc_len, nullptr, r.scores,
+                                      r.rectify ? &rp : nullptr);
                         return;
                     }
                     std::vector<const ocrs_page*> pages;
                     std::vector<std::vector<std::vector<RotatedRect>>> lpp;
                     bool any_scores = false;   // scored if any member asked; the steps are the same either way
+                    bool any_rectify = false;  // the kind is per request: a merged batch crops each page's lines its caller's way
+                    std::vector<char> rp;
                     for (RecRequest* r : batch) {
                         pages.insert(pages.end(), r->pages, r->pages + r->n_pages);
                         lpp.insert(lpp.end(), r->lines_per_page->begin(), r->lines_per_page->end());
                         any_scores = any_scores || r->scores;
+                        any_rectify = any_rectify || r->rectify;
+                        rp.insert(rp.end(), r->n_pages, r->rectify ? 1 : 0);
                     }
                     std::vector<std::vector<CtcStep>> steps;
                     std::vector<RecLine> rl;
                     std::vector<uint32_t> cl;
                     RecScores sc;
-                    recognize_now(pages.data(), pages.size(), lpp, &steps, &rl, &cl, nullptr, any_scores ? &sc : nullptr);
+                    recognize_now(pages.data(), pages.size(), lpp, &steps, &rl, &cl, nullptr, any_scores ? &sc : nullptr,
+                                  any_rectify ? &rp : nullptr);
                     size_t line0 = 0, page0 = 0;
                     for (RecRequest* r : batch) {
                         size_t nl = 0;
@@ -486,7 +493,9 @@ void ocrs_engine::init_coalescers() {
                     }
                 },
                 [&](RecRequest& r) {
-                    recognize_now(r.pages, r.n_pages, *r.lines_per_page, r.steps, r.rec_lines, r.ctc_len, nullptr, r.scores);
+                    const std::vector<char> rp(r.rectify ? r.n_pages : 0, 1);
+                    recognize_now(r.pages, r.n_pages, *r.lines_per_page, r.steps, r.rec_lines, r.ctc_len, nullptr, r.scores,
+                                  r.rectify ? &rp : nullptr);
                 });
         },
         [](const RecRequest&, const RecRequest&) { return true; });   // lines of any pages share a ragged batch
@@ -511,16 +520,17 @@ void ocrs_engine::detect(const ocrs_page* const* pages, size_t n, std::vector<st
 void ocrs_engine::recognize(const ocrs_page* const* pages, size_t n_pages,
                             const std::vector<std::vector<std::vector<RotatedRect>>>& lines_per_page,
                             std::vector<std::vector<CtcStep>>* steps_out, std::vector<RecLine>* rec_lines_out,
-                            std::vector<uint32_t>* ctc_len_out, RecScores* scores) const {
+                            std::vector<uint32_t>* ctc_len_out, RecScores* scores, bool rectify) const {
     const int max_active = option(OPT_COALESCE);
     const size_t max_pages = (size_t)std::max(1, option(OPT_COALESCE_PAGES));
     if (max_active <= 0 || !rec_queue || n_pages == 0 || 2 * n_pages >= max_pages || !recognition || recognition->is_callback()) {
-        recognize_now(pages, n_pages, lines_per_page, steps_out, rec_lines_out, ctc_len_out, nullptr, scores);
+        const std::vector<char> rp(rectify ? n_pages : 0, 1);
+        recognize_now(pages, n_pages, lines_per_page, steps_out, rec_lines_out, ctc_len_out, nullptr, scores, rectify ? &rp : nullptr);
         return;
     }
     RecRequest r;
     r.pages = pages; r.n_pages = n_pages; r.lines_per_page = &lines_per_page;
-    r.steps = steps_out; r.rec_lines = rec_lines_out; r.ctc_len = ctc_len_out; r.scores = scores; r.weight = n_pages;
+    r.steps = steps_out; r.rec_lines = rec_lines_out; r.ctc_len = ctc_len_out; r.scores = scores; r.rectify = rectify; r.weight = n_pages;
     rec_queue->submit(r, max_active, max_pages, option_long(OPT_COALESCE_WINDOW_US));
 }
 
@@ -585,8 +595,131 @@ bool polygon_slice_bounding_rect(const std::vector<PointI>& poly, int32_t min_x,
 
 }  // namespace
 
-RecLine ocrs_engine::make_rec_line(const std::vector<RotatedRect>& words, size_t page, size_t index) const {
+// DESIGN.md §8.4 (tests/rectify_ref.py restates it): double from the float32 values, every operation as written, sums in
+// word order, only + - * / sqrt — and no contraction (the tree is built with -ffp-contract=off), so numpy gives the same bits
+LineFrame ocrs::line_frame(const float* w6, size_t n, int32_t H) {
+    if (n == 0 || !w6) fail(OCRS_ERR_INVALID_ARGUMENT, "line has no words");
+    if (H <= 0) fail(OCRS_ERR_INVALID_ARGUMENT, "line frame: recognition height %d", H);
+    LineFrame f;
+    f.ranges.resize(4 * n);
+    for (size_t i = 0; i < n; i++) { f.ranges[4 * i] = 1; f.ranges[4 * i + 1] = 0; f.ranges[4 * i + 2] = 1; f.ranges[4 * i + 3] = 0; }
+    bool finite = true;
+    for (size_t i = 0; i < 6 * n; i++) finite = finite && std::isfinite(w6[i]);
+    if (!finite) {
+        f.rw = resized_line_width(0, 0, H);
+        return f;
+    }
+    auto W = [&](size_t i, int k) { return (double)w6[6 * i + k]; };
+    double sx = 0.0, sy = 0.0;
+    for (size_t i = 0; i < n; i++) { sx = sx + W(i, 0); sy = sy + W(i, 1); }
+    const double mx = sx / (double)n, my = sy / (double)n;
+    double Sxx = 0.0, Sxy = 0.0;
+    for (size_t i = 0; i < n; i++) {
+        Sxx = Sxx + (W(i, 0) - mx) * (W(i, 0) - mx);
+        Sxy = Sxy + (W(i, 0) - mx) * (W(i, 1) - my);
+    }
+    double ax, ay;
+    if (n >= 2 && Sxx > 0.0) {
+        const double m = Sxy / Sxx, L = std::sqrt(1.0 + m * m);
+        ax = 1.0 / L;
+        ay = m / L;
+    } else {
+        ax = -W(0, 3);
+        ay = W(0, 2);
+        if (ax < 0.0 || (ax == 0.0 && ay < 0.0)) { ax = -ax; ay = -ay; }
+    }
+    const double nx = -ay, ny = ax;
+    std::vector<double> ext(4 * n);   // sa, sb, ta, tb per word
+    double s_min = 0.0, s_max = 0.0, t_min = 0.0, t_max = 0.0;
+    for (size_t i = 0; i < n; i++) {
+        const double cx = W(i, 0), cy = W(i, 1), upx = W(i, 2), upy = W(i, 3), w = W(i, 4), h = W(i, 5);
+        const double hx = (w / 2.0) * -upy, hy = (w / 2.0) * upx, vx = (h / 2.0) * upx, vy = (h / 2.0) * upy;
+        double sa = 0.0, sb = 0.0, ta = 0.0, tb = 0.0;
+        bool first = true;
+        for (double sw : {-1.0, 1.0})
+            for (double sh : {-1.0, 1.0}) {
+                const double px = cx + sw * hx + sh * vx, py = cy + sw * hy + sh * vy;
+                const double sv = px * ax + py * ay, tv = px * nx + py * ny;
+                if (first) { sa = sb = sv; ta = tb = tv; first = false; }
+                sa = std::min(sa, sv); sb = std::max(sb, sv);
+                ta = std::min(ta, tv); tb = std::max(tb, tv);
+            }
+        ext[4 * i] = sa; ext[4 * i + 1] = sb; ext[4 * i + 2] = ta; ext[4 * i + 3] = tb;
+        if (i == 0) { s_min = sa; s_max = sb; t_min = ta; t_max = tb; }
+        s_min = std::min(s_min, sa); s_max = std::max(s_max, sb);
+        t_min = std::min(t_min, ta); t_max = std::max(t_max, tb);
+    }
+    const double Wl = s_max - s_min, Hl = t_max - t_min;
+    auto capped_ceil = [](double v) { return (int32_t)std::min(std::ceil(v), 2147483647.0); };
+    const int32_t cw = capped_ceil(Wl), ch = capped_ceil(Hl);
+    if (cw <= 0 || ch <= 0) {   // the plain crop's width for a bounding box with a side of zero
+        f.rw = resized_line_width(std::max(cw, 0), std::max(ch, 0), H);
+        return f;
+    }
+    const uint32_t rw = resized_line_width(cw, ch, H);
+    f.empty = false;
+    f.ax = ax; f.ay = ay;
+    f.s_min = s_min; f.s_max = s_max; f.t_min = t_min; f.t_max = t_max;
+    f.rw = rw;
+    const double drw = (double)rw, dH = (double)H;
+    f.coef[0] = (float)(s_min * ax + t_min * nx - 0.5);
+    f.coef[1] = (float)(ax * Wl / drw);
+    f.coef[2] = (float)(nx * Hl / dH);
+    f.coef[3] = (float)(s_min * ay + t_min * ny - 0.5);
+    f.coef[4] = (float)(ay * Wl / drw);
+    f.coef[5] = (float)(ny * Hl / dH);
+    for (size_t i = 0; i < n; i++) {
+        const double c0 = std::max(std::ceil((ext[4 * i] - s_min) * drw / Wl - 0.5), 0.0);
+        const double c1 = std::min(std::floor((ext[4 * i + 1] - s_min) * drw / Wl - 0.5), drw - 1.0);
+        const double r0 = std::max(std::ceil((ext[4 * i + 2] - t_min) * dH / Hl - 0.5), 0.0);
+        const double r1 = std::min(std::floor((ext[4 * i + 3] - t_min) * dH / Hl - 0.5), dH - 1.0);
+        if (c0 > c1 || r0 > r1) continue;   // covers nothing: (1, 0, 1, 0)
+        f.ranges[4 * i] = (int32_t)c0; f.ranges[4 * i + 1] = (int32_t)c1;
+        f.ranges[4 * i + 2] = (int32_t)r0; f.ranges[4 * i + 3] = (int32_t)r1;
+    }
+    return f;
+}
+
+// the char's slice of the line's frame, mapped to the page in double; a char that starts in the padding is dropped
+std::vector<std::pair<size_t, Rect>> ocrs::rectified_char_boxes(const LineFrame& f, uint32_t group_width, uint32_t ctc_input_len,
+                                                                const uint32_t* pos, size_t n_steps) {
+    std::vector<std::pair<size_t, Rect>> out;
+    if (f.empty || n_steps == 0 || ctc_input_len == 0) return out;
+    const uint32_t ds = (uint32_t)rround((float)group_width / (float)ctc_input_len), rw = f.rw;
+    const double Wl = f.s_max - f.s_min, nx = -f.ay, ny = f.ax, drw = (double)rw;
+    auto to_i32 = [](double v) { return (int32_t)std::min(std::max(v, -2147483648.0), 2147483647.0); };
+    for (size_t i = 0; i < n_steps; i++) {
+        const uint32_t start_x = pos[i] * ds;
+        const uint32_t end_x = i + 1 < n_steps ? pos[i + 1] * ds : rw;
+        if (start_x >= rw) continue;
+        const double sv[2] = {f.s_min + (double)start_x * Wl / drw, f.s_min + (double)end_x * Wl / drw};
+        const double tv[2] = {f.t_min, f.t_max};
+        double x_lo = 0, x_hi = 0, y_lo = 0, y_hi = 0;
+        for (int a = 0; a < 2; a++)
+            for (int b = 0; b < 2; b++) {
+                const double x = sv[a] * f.ax + tv[b] * nx, y = sv[a] * f.ay + tv[b] * ny;
+                if (a == 0 && b == 0) { x_lo = x_hi = x; y_lo = y_hi = y; }
+                x_lo = std::min(x_lo, x); x_hi = std::max(x_hi, x);
+                y_lo = std::min(y_lo, y); y_hi = std::max(y_hi, y);
+            }
+        out.emplace_back(i, Rect{to_i32(std::floor(y_lo)), to_i32(std::floor(x_lo)), to_i32(std::ceil(y_hi)), to_i32(std::ceil(x_hi))});
+    }
+    return out;
+}
+
+RecLine ocrs_engine::make_rec_line(const std::vector<RotatedRect>& words, size_t page, size_t index, bool rectify) const {
     if (words.empty()) fail(OCRS_ERR_INVALID_ARGUMENT, "line has no words");  // recognition.rs:433
+    if (rectify) {   // the line's own frame stands in for polygon and bounds
+        static_assert(sizeof(RotatedRect) == 6 * sizeof(float), "RotatedRect is six packed floats");
+        RecLine l;
+        l.page = page;
+        l.index = index;
+        l.rectified = true;
+        l.frame = line_frame(&words[0].cx, words.size(), (int32_t)rec_input_height());
+        l.resized_width = l.frame.rw;
+        l.group_width = (l.resized_width + 49) / 50 * 50;
+        return l;
+    }
     RectF br = words[0].bounding_rect();
     for (size_t i = 1; i < words.size(); i++) br = br.unite(words[i].bounding_rect());
     const Rect line_rect = br.integral_bounding_rect();
@@ -618,12 +751,13 @@ void ocrs_engine::recognize_now(const ocrs_page* const* pages, size_t n_pages,
                                 const std::vector<std::vector<std::vector<RotatedRect>>>& lines_per_page,
                                 std::vector<std::vector<CtcStep>>* steps_out, std::vector<RecLine>* rec_lines_out,
                                 std::vector<uint32_t>* ctc_len_out, std::vector<std::vector<float>>* logp_out,
-                                RecScores* scores) const {
+                                RecScores* scores, const std::vector<char>* rectify_pages) const {
     if (!recognition) fail(OCRS_ERR_MODEL_NOT_LOADED, "Recognition model not loaded");
     const uint32_t rec_h = rec_input_height();
     std::vector<RecLine> lines;
     for (size_t p = 0; p < n_pages; p++)
-        for (const auto& words : lines_per_page[p]) lines.push_back(make_rec_line(words, p, lines.size()));
+        for (const auto& words : lines_per_page[p])
+            lines.push_back(make_rec_line(words, p, lines.size(), rectify_pages && (*rectify_pages)[p]));
     const size_t L = lines.size();
     const double budget = rec_pixel_budget();
     double total = 0.0;
@@ -863,9 +997,28 @@ void ocrs_engine::recognize_lines(const ocrs_page* const* pages, size_t n_pages,
             fail(OCRS_ERR_CAPACITY, "text line too large for the recognition model (%lld input pixels)", (long long)off);
         std::vector<k::LineDesc> descs;
         std::vector<int32_t> poly;
+        std::vector<k::RectLineDesc> rdescs;   // the rectified lines: a launch of their own into the same tensor
+        std::vector<int32_t> ranges;
+        int rect_max_w = 0;
         for (const Chunk& ch : chunks)
             for (size_t j = 0; j < ch.members.size(); j++) {
                 const RecLine& ln = lines[ch.members[j]];
+                if (ln.rectified) {
+                    k::RectLineDesc d{};
+                    d.page = (int32_t)ln.page;
+                    d.mode = ln.frame.empty ? 1 : 0;
+                    d.range_off = (int32_t)(ranges.size() / 4);
+                    d.range_n = ln.frame.empty ? 0 : (int32_t)(ln.frame.ranges.size() / 4);
+                    d.resized_w = (int32_t)ln.resized_width;
+                    d.out_w = (int32_t)ch.gw;
+                    d.out_off = ch.off + (int64_t)j * rec_h * ch.gw;
+                    d.x0 = ln.frame.coef[0]; d.ax = ln.frame.coef[1]; d.bx = ln.frame.coef[2];
+                    d.y0 = ln.frame.coef[3]; d.ay = ln.frame.coef[4]; d.by = ln.frame.coef[5];
+                    rdescs.push_back(d);
+                    if (!ln.frame.empty) ranges.insert(ranges.end(), ln.frame.ranges.begin(), ln.frame.ranges.end());
+                    rect_max_w = std::max(rect_max_w, (int)ch.gw);
+                    continue;
+                }
                 k::LineDesc d{};
                 d.page = (int32_t)ln.page;
                 d.poly_off = (int32_t)(poly.size() / 2);
@@ -878,16 +1031,27 @@ void ocrs_engine::recognize_lines(const ocrs_page* const* pages, size_t n_pages,
                 descs.push_back(d);
                 for (const PointI& p : ln.polygon) { poly.push_back(p.y); poly.push_back(p.x); }
             }
-        if (descs.empty()) return;
-        k::LineDesc* d_descs = ws.alloc_n<k::LineDesc>(descs.size());
-        int32_t* d_poly = ws.alloc_n<int32_t>(poly.size());
+        if (descs.empty() && rdescs.empty()) return;
+        k::LineDesc* d_descs = descs.empty() ? nullptr : ws.alloc_n<k::LineDesc>(descs.size());
+        int32_t* d_poly = descs.empty() ? nullptr : ws.alloc_n<int32_t>(poly.size());
         // host temporaries travel through the workspace's pinned staging: real asynchronous copies, no host wait here
-        ws.upload(d_descs, descs.data(), descs.size() * sizeof(k::LineDesc));
-        ws.upload(d_poly, poly.data(), poly.size() * sizeof(int32_t));
+        if (!descs.empty()) {
+            ws.upload(d_descs, descs.data(), descs.size() * sizeof(k::LineDesc));
+            ws.upload(d_poly, poly.data(), poly.size() * sizeof(int32_t));
+        }
+        k::RectLineDesc* d_rdescs = nullptr;
+        int32_t* d_ranges = nullptr;
+        if (!rdescs.empty()) {
+            d_rdescs = ws.alloc_n<k::RectLineDesc>(rdescs.size());
+            d_ranges = ws.alloc_n<int32_t>(std::max<size_t>(ranges.size(), 4));
+            ws.upload(d_rdescs, rdescs.data(), rdescs.size() * sizeof(k::RectLineDesc));
+            if (!ranges.empty()) ws.upload(d_ranges, ranges.data(), ranges.size() * sizeof(int32_t));
+        }
         float* d_all = ws.alloc_n<float>((size_t)off);
         {
-            StageScope sc(T, ST_LINE_CROP, st);
+            StageScope sc(T, ST_LINE_CROP, st, (descs.empty() ? 0 : 1) + (rdescs.empty() ? 0 : 1));
             k::crop_lines(d_pages, d_hw, d_descs, d_poly, (int)descs.size(), (int)rec_h, d_all, st);
+            k::rectify_lines(d_pages, d_hw, d_rdescs, d_ranges, (int)rdescs.size(), rect_max_w, (int)rec_h, d_all, st);
         }
         if (callback) ws.sync();   // the callback path reads the crops back right away
         for (Chunk& ch : chunks) ch.ptr = d_all + ch.off;
@@ -1198,6 +1362,16 @@ std::vector<TextChar> ocrs_engine::text_line_from_result(const RecLine& line, ui
     std::vector<TextChar> out;
     if (char_logp) char_logp->clear();
     if (steps.empty() || ctc_input_len == 0) return out;
+    if (line.rectified) {
+        std::vector<uint32_t> pos(steps.size());
+        for (size_t i = 0; i < steps.size(); i++) pos[i] = steps[i].pos;
+        for (const auto& kv : rectified_char_boxes(line.frame, line.group_width, ctc_input_len, pos.data(), pos.size())) {
+            const uint32_t idx = steps[kv.first].label - 1;
+            out.push_back(TextChar{idx < alphabet.size() ? (uint32_t)alphabet[idx] : (uint32_t)'?', kv.second});
+            if (char_logp) char_logp->push_back((*step_logp)[kv.first]);
+        }
+        return out;
+    }
     const Rect line_rect = line.bounds;
     const float x_scale = (float)line_rect.width() / (float)line.resized_width;
     const uint32_t downsample = (uint32_t)rround((float)line.group_width / (float)ctc_input_len);

@@ -47,6 +47,22 @@ struct TextChar {  // text_items.rs:48-54
     geom::Rect rect;
 };
 
+// Rectified line crops: a line's own frame from its word rects (cx, cy, upx, upy, w, h), on the host in
+// double — the axis through the word centres, the extents of the words' corners along it and across it, the output width,
+// the six float32 coefficients of the sampling map and every word's column / row range of the mask.
+struct LineFrame {
+    bool empty = true;                       // degenerate: the crop is all -0.5 and the line has no char boxes
+    double ax = 0.0, ay = 0.0;               // axis a; the normal is (-ay, ax)
+    double s_min = 0.0, s_max = 0.0, t_min = 0.0, t_max = 0.0;
+    uint32_t rw = 0;
+    float coef[6] = {0, 0, 0, 0, 0, 0};      // x0, ax, bx, y0, ay, by
+    std::vector<int32_t> ranges;             // [n][4]: c0, c1, r0, r1 (c0 > c1: the word covers nothing)
+};
+LineFrame line_frame(const float* words6, size_t n_words, int32_t rec_height);
+// the page boxes of a rectified line's chars from its CTC step positions: (step index, box) of every char that is kept
+std::vector<std::pair<size_t, geom::Rect>> rectified_char_boxes(const LineFrame& f, uint32_t group_width, uint32_t ctc_input_len,
+                                                                const uint32_t* pos, size_t n_steps);
+
 struct RecLine {  // TextRecLine (recognition.rs:80-89) + owning page
     size_t page = 0;
     size_t index = 0;                    // line index in the caller's order
@@ -54,6 +70,8 @@ struct RecLine {  // TextRecLine (recognition.rs:80-89) + owning page
     geom::Rect bounds{0, 0, 0, 0};       // Polygon::bounding_rect
     uint32_t resized_width = 0;
     uint32_t group_width = 0;
+    bool rectified = false;              // cropped along its own axis (frame) instead of through polygon / bounds
+    LineFrame frame;
 };
 
 // Detection confidence, indexed [page][word] like the rects of the same call.
@@ -86,6 +104,7 @@ struct RecRequest : CoalescedBase {
     std::vector<RecLine>* rec_lines = nullptr;
     std::vector<uint32_t>* ctc_len = nullptr;
     RecScores* scores = nullptr;   // null: the caller did not ask for confidence
+    bool rectify = false;          // this caller's lines are cropped along their own axes
 };
 
 }  // namespace ocrs
@@ -133,15 +152,17 @@ struct ocrs_engine {
                     float* host_map, ocrs::DetScores* scores = nullptr, int tile_overlap = -1) const;
 
     // recognition.rs:404-540 over the lines of several pages; small requests are merged likewise.
+    // rectify: the request's lines are cropped along their own axes; a merged batch may mix both kinds.
     void recognize(const ocrs_page* const* pages, size_t n_pages,
                    const std::vector<std::vector<std::vector<ocrs::geom::RotatedRect>>>& lines_per_page,
                    std::vector<std::vector<ocrs::CtcStep>>* steps, std::vector<ocrs::RecLine>* rec_lines,
-                   std::vector<uint32_t>* ctc_input_len, ocrs::RecScores* scores = nullptr) const;
+                   std::vector<uint32_t>* ctc_input_len, ocrs::RecScores* scores = nullptr, bool rectify = false) const;
+    // rectify_pages (optional): one flag per page, the kind of that page's lines; null: all plain
     void recognize_now(const ocrs_page* const* pages, size_t n_pages,
                        const std::vector<std::vector<std::vector<ocrs::geom::RotatedRect>>>& lines_per_page,
                        std::vector<std::vector<ocrs::CtcStep>>* steps, std::vector<ocrs::RecLine>* rec_lines,
                        std::vector<uint32_t>* ctc_input_len, std::vector<std::vector<float>>* logp = nullptr,
-                       ocrs::RecScores* scores = nullptr) const;
+                       ocrs::RecScores* scores = nullptr, const std::vector<char>* rectify_pages = nullptr) const;
     void init_coalescers();
     mutable std::unique_ptr<ocrs::Coalescer<ocrs::DetRequest>> det_queue;
     mutable std::unique_ptr<ocrs::Coalescer<ocrs::RecRequest>> rec_queue;
@@ -169,5 +190,6 @@ struct ocrs_engine {
                                                       std::vector<float>* char_logp = nullptr) const;
 
     uint32_t rec_input_height() const;
-    ocrs::RecLine make_rec_line(const std::vector<ocrs::geom::RotatedRect>& words, size_t page, size_t index) const;
+    ocrs::RecLine make_rec_line(const std::vector<ocrs::geom::RotatedRect>& words, size_t page, size_t index,
+                                bool rectify = false) const;
 };

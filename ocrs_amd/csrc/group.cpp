@@ -730,12 +730,13 @@ ocrs_status ocrs_group_detect_words_batch_tiled(ocrs_engine_group* g, const ocrs
                                     overlap < 0 ? OCRS_TILE_OVERLAP_DEFAULT : overlap);
 }
 
-ocrs_status ocrs_group_recognize_text_batch(ocrs_engine_group* g, const ocrs_page* const* pages, size_t n_pages,
-                                            const size_t* page_line_offsets, const float* line_rects, const size_t* line_offsets,
-                                            size_t n_lines, ocrs_text_char** chars, size_t** char_offsets) {
+static ocrs_status group_recognize_text_batch(ocrs_engine_group* g, const ocrs_page* const* pages, size_t n_pages,
+                                              const size_t* page_line_offsets, const float* line_rects, const size_t* line_offsets,
+                                              size_t n_lines, ocrs_text_char** chars, size_t** char_offsets, bool rectify) {
     return guarded([&] {
         if (!g || !page_line_offsets || !line_offsets || !chars || !char_offsets || (n_pages && !pages))
             fail(OCRS_ERR_INVALID_ARGUMENT, "null argument");
+        if (rectify && g->replay_mode != 0) fail(OCRS_ERR_INVALID_ARGUMENT, "replay: rectified recognition is not recorded");
         if (page_line_offsets[0] != 0 || page_line_offsets[n_pages] != n_lines)
             fail(OCRS_ERR_INVALID_ARGUMENT, "page_line_offsets do not cover n_lines");
         for (size_t i = 0; i < n_pages; i++)
@@ -776,7 +777,7 @@ ocrs_status ocrs_group_recognize_text_batch(ocrs_engine_group* g, const ocrs_pag
                 std::vector<std::vector<CtcStep>> steps;
                 std::vector<RecLine> rl;
                 std::vector<uint32_t> ctc_len;
-                e->recognize(mine.data(), mine.size(), lpp, &steps, &rl, &ctc_len);
+                e->recognize(mine.data(), mine.size(), lpp, &steps, &rl, &ctc_len, nullptr, rectify);
                 flatten_chars(e, rl, ctc_len, steps, &flat, &offs);
                 if (g->replay_mode == 1) {
                     std::lock_guard<std::mutex> lk(g->replay_mu);
@@ -817,6 +818,19 @@ ocrs_status ocrs_group_recognize_text_batch(ocrs_engine_group* g, const ocrs_pag
         *chars = dup_buffer(flat);
         *char_offsets = dup_buffer(offs);
     });
+}
+
+ocrs_status ocrs_group_recognize_text_batch(ocrs_engine_group* g, const ocrs_page* const* pages, size_t n_pages,
+                                            const size_t* page_line_offsets, const float* line_rects, const size_t* line_offsets,
+                                            size_t n_lines, ocrs_text_char** chars, size_t** char_offsets) {
+    return group_recognize_text_batch(g, pages, n_pages, page_line_offsets, line_rects, line_offsets, n_lines, chars, char_offsets, false);
+}
+
+ocrs_status ocrs_group_recognize_text_batch_rectified(ocrs_engine_group* g, const ocrs_page* const* pages, size_t n_pages,
+                                                      const size_t* page_line_offsets, const float* line_rects,
+                                                      const size_t* line_offsets, size_t n_lines, ocrs_text_char** chars,
+                                                      size_t** char_offsets) {
+    return group_recognize_text_batch(g, pages, n_pages, page_line_offsets, line_rects, line_offsets, n_lines, chars, char_offsets, true);
 }
 
 static void gather_entry(ocrs_engine_group* g, ocrs_gather_mode mode, const void* const* payloads, const size_t* bytes, void** out,

@@ -288,6 +288,22 @@ struct LineDesc {      // one text line to crop (recognition.rs:91-126)
 void crop_lines(const float* const* d_pages, const int32_t* d_page_hw /*[pages][2]*/, const LineDesc* d_lines,
                 const int32_t* d_poly /*(y,x) pairs*/, int n_lines, int out_h, float* d_out, hipStream_t s);
 
+// ---- kernels_rectify.hip -----------------------------------
+struct RectLineDesc {   // one text line to crop along its own axis: LineDesc's sibling
+    int32_t page;       // index into page pointer table
+    int32_t mode;       // 0: sample through the map; 1: an empty line, all -0.5
+    int32_t range_off;  // first word in the packed range array (4 ints per word: c0, c1, r0, r1; c0 > c1 covers nothing)
+    int32_t range_n;    // word count
+    int32_t resized_w;
+    int32_t out_w;      // padded width of this line's batch (its width group); even
+    int64_t out_off;    // float offset of this line's [out_h, out_w] image in the output buffer; even
+    float x0, ax, bx, y0, ay, by;   // X = (x0 + ax * (ox + 0.5)) + bx * (oy + 0.5), Y likewise
+};
+// Affine gather + bilinear taps + per-column row mask + right-pad with -0.5; every line writes its own [out_h, out_w]
+// image at d_out + out_off, as crop_lines does.  max_out_w: the widest out_w among the lines.  d_ranges: 16-byte aligned.
+void rectify_lines(const float* const* d_pages, const int32_t* d_page_hw /*[pages][2]*/, const RectLineDesc* d_lines,
+                   const int32_t* d_ranges, int n_lines, int max_out_w, int out_h, float* d_out, hipStream_t s);
+
 // kernels_peaks.hip
 void measure_peaks(double* mfma_tflops, double* copy_gbps);
 
