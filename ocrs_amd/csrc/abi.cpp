@@ -779,27 +779,27 @@ ocrs_status recognize_text_batch(const ocrs_engine* e, const ocrs_page* const* p
         std::vector<std::vector<std::vector<RotatedRect>>> lpp(n_pages);
         for (size_t p = 0; p < n_pages; p++)
             lpp[p] = unpack_lines(line_rects, line_offsets, page_line_offsets[p], page_line_offsets[p + 1]);
-        std::vector<std::vector<CtcStep>> steps;
-        std::vector<RecLine> rl;
-        std::vector<uint32_t> ctc_len;
         const bool scored = char_logp != nullptr;
-        RecScores sc;
-        e->recognize(pages, n_pages, lpp, &steps, &rl, &ctc_len, scored ? &sc : nullptr, rectify);
+        std::vector<RecResult> res;
+        e->recognize(pages, n_pages, lpp, &res, scored, rectify);
         std::vector<ocrs_text_char> flat;
         std::vector<size_t> offs{0};
         std::vector<float> flat_lp, lp;
-        for (size_t i = 0; i < rl.size(); i++) {
-            for (const TextChar& c : e->text_line_from_result(rl[i], ctc_len[i], steps[i], scored ? &sc.step_logp[i] : nullptr,
-                                                              scored ? &lp : nullptr))
+        std::vector<double> scores;
+        for (const RecResult& r : res) {
+            for (const TextChar& c : e->text_line_from_result(r, scored ? &lp : nullptr))
                 flat.push_back(ocrs_text_char{c.ch, c.rect.top, c.rect.left, c.rect.bottom, c.rect.right});
-            if (scored) flat_lp.insert(flat_lp.end(), lp.begin(), lp.end());
+            if (scored) {
+                flat_lp.insert(flat_lp.end(), lp.begin(), lp.end());
+                scores.push_back(r.line_score);
+            }
             offs.push_back(flat.size());
         }
         *chars = dup_buffer(flat);
         *char_offsets = dup_buffer(offs);
         if (scored) {
             *char_logp = dup_buffer(flat_lp);
-            *line_score = dup_buffer(sc.line_score);
+            *line_score = dup_buffer(scores);
         }
     });
 }
@@ -895,14 +895,12 @@ static ocrs_status recognize_tokens(const ocrs_engine* e, const ocrs_page* page,
         check_pages_on(e, &page, 1);
         std::vector<std::vector<std::vector<RotatedRect>>> lpp(1);
         lpp[0] = unpack_lines(line_rects, line_offsets, 0, n_lines);
-        std::vector<std::vector<CtcStep>> steps;
-        std::vector<RecLine> rl;
-        std::vector<uint32_t> ctc_len;
-        e->recognize(&page, 1, lpp, &steps, &rl, &ctc_len, nullptr, rectify);
+        std::vector<RecResult> res;
+        e->recognize(&page, 1, lpp, &res, false, rectify);
         std::vector<uint32_t> fl, fp;
         std::vector<size_t> offs{0};
-        for (const auto& s : steps) {
-            for (const CtcStep& c : s) { fl.push_back(c.label); fp.push_back(c.pos); }
+        for (const RecResult& r : res) {
+            for (const CtcStep& c : r.steps) { fl.push_back(c.label); fp.push_back(c.pos); }
             offs.push_back(fl.size());
         }
         *labels = dup_buffer(fl);
@@ -983,33 +981,16 @@ ocrs_status ocrs_engine_prepare_recognition_input(const ocrs_engine* e, const oc
         if (!e->recognition) fail(OCRS_ERR_MODEL_NOT_LOADED, "Recognition model not loaded");
         std::vector<RotatedRect> words(n_words);
         for (size_t i = 0; i < n_words; i++) words[i] = RotatedRect::from_array(line + 6 * i);
-        RecLine ln = e->make_rec_line(words, 0, 0);
+        const RecLine ln = e->make_rec_line(words, 0, 0);
         const int rec_h = (int)e->rec_input_height();
         const int rw = (int)ln.resized_width;
-        Workspace ws;
-        k::LineDesc d{};
-        d.page = 0; d.poly_off = 0; d.poly_n = (int32_t)ln.polygon.size();
-        d.top = ln.bounds.top; d.left = ln.bounds.left; d.bh = ln.bounds.height(); d.bw = ln.bounds.width();
-        d.resized_w = rw; d.out_w = rw; d.out_off = 0;
-        std::vector<int32_t> poly;
-        for (const PointI& p : ln.polygon) { poly.push_back(p.y); poly.push_back(p.x); }
-        const float* hp = page->grey.as<float>();
-        const int32_t hw[2] = {page->h, page->w};
-        const float** d_pages = ws.alloc_n<const float*>(1);
-        int32_t* d_hw = ws.alloc_n<int32_t>(2);
-        k::LineDesc* d_desc = ws.alloc_n<k::LineDesc>(1);
-        int32_t* d_poly = ws.alloc_n<int32_t>(poly.size());
-        float* d_out = ws.alloc_n<float>((size_t)rec_h * std::max(rw, 1));
-        OCRS_HIP(hipMemcpyAsync(d_pages, &hp, sizeof hp, hipMemcpyHostToDevice, ws.s()));
-        OCRS_HIP(hipMemcpyAsync(d_hw, hw, sizeof hw, hipMemcpyHostToDevice, ws.s()));
-        OCRS_HIP(hipMemcpyAsync(d_desc, &d, sizeof d, hipMemcpyHostToDevice, ws.s()));
-        OCRS_HIP(hipMemcpyAsync(d_poly, poly.data(), poly.size() * 4, hipMemcpyHostToDevice, ws.s()));
         std::vector<float> host((size_t)rec_h * rw);
         if (rw > 0) {
-            k::crop_lines(d_pages, d_hw, d_desc, d_poly, 1, rec_h, d_out, ws.s());
+            Workspace ws;
+            const float* d_out = stage_line_crops(ws, nullptr, &page, 1, {CropLine{&ln, (uint32_t)rw, 0}}, rec_h, (int64_t)rec_h * rw);
             ws.download(host.data(), d_out, host.size() * 4);
+            ws.sync();
         }
-        ws.sync();
         *out = dup_buffer(host);
         *height = rec_h;
         *width = rw;
@@ -1030,24 +1011,7 @@ ocrs_status ocrs_engine_prepare_recognition_input_rectified(const ocrs_engine* e
         std::vector<float> host((size_t)rec_h * rw);
         if (rw > 0) {
             Workspace ws;
-            k::RectLineDesc d{};
-            d.page = 0; d.mode = ln.frame.empty ? 1 : 0; d.range_off = 0;
-            d.range_n = ln.frame.empty ? 0 : (int32_t)(ln.frame.ranges.size() / 4);
-            d.resized_w = rw; d.out_w = gw; d.out_off = 0;
-            d.x0 = ln.frame.coef[0]; d.ax = ln.frame.coef[1]; d.bx = ln.frame.coef[2];
-            d.y0 = ln.frame.coef[3]; d.ay = ln.frame.coef[4]; d.by = ln.frame.coef[5];
-            const float* hp = page->grey.as<float>();
-            const int32_t hw[2] = {page->h, page->w};
-            const float** d_pages = ws.alloc_n<const float*>(1);
-            int32_t* d_hw = ws.alloc_n<int32_t>(2);
-            k::RectLineDesc* d_desc = ws.alloc_n<k::RectLineDesc>(1);
-            int32_t* d_ranges = ws.alloc_n<int32_t>(std::max<size_t>(ln.frame.ranges.size(), 4));
-            float* d_out = ws.alloc_n<float>((size_t)rec_h * gw);
-            OCRS_HIP(hipMemcpyAsync(d_pages, &hp, sizeof hp, hipMemcpyHostToDevice, ws.s()));
-            OCRS_HIP(hipMemcpyAsync(d_hw, hw, sizeof hw, hipMemcpyHostToDevice, ws.s()));
-            OCRS_HIP(hipMemcpyAsync(d_desc, &d, sizeof d, hipMemcpyHostToDevice, ws.s()));
-            OCRS_HIP(hipMemcpyAsync(d_ranges, ln.frame.ranges.data(), ln.frame.ranges.size() * 4, hipMemcpyHostToDevice, ws.s()));
-            k::rectify_lines(d_pages, d_hw, d_desc, d_ranges, 1, gw, rec_h, d_out, ws.s());
+            const float* d_out = stage_line_crops(ws, nullptr, &page, 1, {CropLine{&ln, (uint32_t)gw, 0}}, rec_h, (int64_t)rec_h * gw);
             std::vector<float> full((size_t)rec_h * gw);
             ws.download(full.data(), d_out, full.size() * 4);
             ws.sync();
@@ -1067,14 +1031,12 @@ ocrs_status ocrs_engine_get_text(const ocrs_engine* e, const ocrs_page* page, ch
         e->detect(&page, 1, &rr, nullptr);
         std::vector<std::vector<std::vector<RotatedRect>>> lpp(1);
         lpp[0] = find_text_lines(rr[0]);
-        std::vector<std::vector<CtcStep>> steps;
-        std::vector<RecLine> rl;
-        std::vector<uint32_t> ctc_len;
-        e->recognize(&page, 1, lpp, &steps, &rl, &ctc_len);
+        std::vector<RecResult> res;
+        e->recognize(&page, 1, lpp, &res);
         std::string out;
         bool first = true;
-        for (size_t i = 0; i < rl.size(); i++) {
-            auto chars = e->text_line_from_result(rl[i], ctc_len[i], steps[i]);
+        for (const RecResult& r : res) {
+            auto chars = e->text_line_from_result(r);
             if (chars.empty()) continue;
             if (!first) out.push_back('\n');
             first = false;

@@ -117,12 +117,11 @@ std::unique_ptr<ocrs_engine> make_engine(const ocrs_engine_params& params) {
     return e;
 }
 
-void flatten_chars(const ocrs_engine* e, const std::vector<RecLine>& rl, const std::vector<uint32_t>& ctc_len,
-                   const std::vector<std::vector<CtcStep>>& steps, std::vector<ocrs_text_char>* flat, std::vector<size_t>* offs) {
+void flatten_chars(const ocrs_engine* e, const std::vector<RecResult>& res, std::vector<ocrs_text_char>* flat, std::vector<size_t>* offs) {
     flat->clear();
     offs->assign(1, 0);
-    for (size_t i = 0; i < rl.size(); i++) {
-        for (const TextChar& c : e->text_line_from_result(rl[i], ctc_len[i], steps[i]))
+    for (const RecResult& r : res) {
+        for (const TextChar& c : e->text_line_from_result(r))
             flat->push_back(ocrs_text_char{c.ch, c.rect.top, c.rect.left, c.rect.bottom, c.rect.right});
         offs->push_back(flat->size());
     }

@@ -69,8 +69,7 @@ void check_image_args(const void* pixels, int height, int width, int channels);
 // OcrEngine::new (lib.rs:132-180)
 std::unique_ptr<ocrs_engine> make_engine(const ocrs_engine_params& params);
 // flatten per-line characters into the ABI's (chars, char_offsets) form
-void flatten_chars(const ocrs_engine* e, const std::vector<RecLine>& rl, const std::vector<uint32_t>& ctc_len,
-                   const std::vector<std::vector<CtcStep>>& steps, std::vector<ocrs_text_char>* flat, std::vector<size_t>* offs);
+void flatten_chars(const ocrs_engine* e, const std::vector<RecResult>& res, std::vector<ocrs_text_char>* flat, std::vector<size_t>* offs);
 
 }  // namespace abi
 }  // namespace ocrs

@@ -34,6 +34,286 @@ TileAxisPlan ocrs::tile_axis_plan(int L, int M, int v) {
 // ===========================================================================
 // Detection — detection.rs:104-200
 // ===========================================================================
+namespace {
+
+// The reference takes any image per call (detection.rs:131-171) and the model always runs at its own fixed size, so a
+// batch may hold pages of SEVERAL sizes (r6; the coalescer merges whatever waits): the model runs once over all of them,
+// the size-dependent kernels before and after it (resize in; resize back + threshold, components, contours) run once per
+// size, on that size's pages — the same launches with the same arguments as a batch of that size alone, so nobody's bits
+// change.  Internally the pages are ordered by size group (`order`); results go back in the caller's order.
+struct SizeGroup {
+    int h = 0, w = 0, first = 0, count = 0;          // pages [first, first + count) of the grouped order
+    int pad_bottom = 0, pad_right = 0, max_comp = 0;
+    int64_t px = 0, arena = 0;
+    uint8_t* d_mask = nullptr;
+    float* d_map = nullptr;                          // page-resolution probabilities: scored requests (and host_map) only
+    bool prepared = false;                           // resize_threshold wrote the component stage's initial labels too
+    k::CclBuffers b{};
+};
+struct PageGroups {
+    std::vector<SizeGroup> groups;
+    std::vector<int> order;      // grouped position -> the caller's page
+    std::vector<int> pos_of;     // the caller's page -> grouped position (the inverse of `order`)
+    std::vector<int> group_of;   // grouped position -> its size group
+};
+
+PageGroups group_pages_by_size(const ocrs_page* const* pages, size_t n) {
+    PageGroups pg;
+    std::vector<SizeGroup>& groups = pg.groups;
+    pg.order.resize(n); pg.pos_of.resize(n); pg.group_of.resize(n);
+    std::vector<int> gi(n);
+    for (size_t i = 0; i < n; i++) {
+        const int h = pages[i]->h, w = pages[i]->w;
+        if (h <= 0 || w <= 0 || h > 65535 || w > 65535) fail(OCRS_ERR_INVALID_ARGUMENT, "unsupported page size %dx%d", h, w);
+        size_t g = 0;
+        while (g < groups.size() && (groups[g].h != h || groups[g].w != w)) g++;
+        if (g == groups.size()) { groups.emplace_back(); groups[g].h = h; groups[g].w = w; }
+        groups[g].count++;
+        gi[i] = (int)g;
+    }
+    int at = 0;
+    for (SizeGroup& g : groups) { g.first = at; at += g.count; g.count = 0; }
+    for (size_t i = 0; i < n; i++) {
+        SizeGroup& g = groups[gi[i]];
+        pg.order[g.first + g.count] = (int)i;
+        pg.pos_of[i] = g.first + g.count;
+        pg.group_of[g.first + g.count] = gi[i];
+        g.count++;
+    }
+    return pg;
+}
+
+// The detector on `n` model-sized inputs d_in [n, in_h, in_w] (the untiled batch, or one chunk of tiles); returns its
+// probabilities in the same layout.  A callback model runs once per input, input run_order[k] k-th (null: as they lie),
+// and its outputs go to d_cb_out.
+const float* run_detector(const ocrs_engine& e, Workspace& ws, const float* d_in, int n, int in_h, int in_w, float* d_cb_out,
+                          const int* run_order) {
+    if (!e.detection->is_callback()) {
+        TensorShape os;
+        const float* d_prob =
+            static_cast<const HipModel*>(e.detection)->run_device(ws, d_in, n, in_h, in_w, &os, e.tm(), nullptr, nullptr, true, e.debug);
+        if (os.n != n || os.h != in_h || os.w != in_w || os.c != 1)
+            fail(OCRS_ERR_WRONG_OUTPUT, "model output had unexpected type or shape: detection output [%d,%d,%d,%d]", os.n,
+                 os.c, os.h, os.w);
+        return d_prob;
+    }
+    // `trait Model` implemented by the caller: one run per model input, host tensors (detection.rs:184)
+    const auto* cb = static_cast<const CallbackModel*>(e.detection);
+    const size_t px = (size_t)in_h * in_w;
+    for (int k = 0; k < n; k++) {
+        const size_t at = (size_t)(run_order ? run_order[k] : k) * px;
+        std::vector<float> hin(px), hout;
+        ws.download(hin.data(), d_in + at, hin.size() * sizeof(float));
+        ws.sync();
+        const int64_t ishape[4] = {1, 1, in_h, in_w};
+        int64_t oshape[4];
+        int ond = 0;
+        cb->run(hin.data(), ishape, hout, oshape, &ond);
+        if (ond != 4 || oshape[2] != in_h || oshape[3] != in_w || oshape[0] * oshape[1] != 1)
+            fail(OCRS_ERR_WRONG_OUTPUT, "model output had unexpected type or shape: detection output is not [1,1,%d,%d]",
+                 in_h, in_w);
+        OCRS_HIP(hipMemcpyAsync(d_cb_out + at, hout.data(), hout.size() * sizeof(float), hipMemcpyHostToDevice, ws.s()));
+        ws.sync();
+    }
+    return d_cb_out;
+}
+
+// Tiled detection: tiles of the whole request in the caller's page order, row-major within a page (a
+// caller's model sees them in that order); gather -> model -> stitch per chunk of at most det_tile_batch tiles, so the
+// activations of a request are bounded whatever the page size.  Owned rectangles are disjoint: chunks need no ordering
+// among themselves.  stitch_threshold fills every group's mask and map.
+void run_detector_tiled(const ocrs_engine& e, Workspace& ws, const PageGroups& pg, const std::vector<const float*>& page_ptrs,
+                        int in_h, int in_w, int tile_overlap) {
+    StageTimers* T = e.tm();
+    hipStream_t st = ws.s();
+    std::vector<k::TileDesc> tiles;
+    for (int i : pg.pos_of) {
+        const SizeGroup& g = pg.groups[pg.group_of[i]];
+        const TileAxisPlan py = tile_axis_plan(g.h, in_h, tile_overlap), px = tile_axis_plan(g.w, in_w, tile_overlap);
+        const size_t at = (size_t)(i - g.first) * g.px;
+        for (size_t ty = 0; ty < py.origin.size(); ty++)
+            for (size_t tx = 0; tx < px.origin.size(); tx++)
+                tiles.push_back(k::TileDesc{page_ptrs[i], g.d_mask + at, g.d_map ? g.d_map + at : nullptr, g.h, g.w, py.origin[ty], px.origin[tx],
+                                            py.bound[ty], py.bound[ty + 1], px.bound[tx], px.bound[tx + 1]});
+    }
+    k::TileDesc* d_tiles = ws.alloc_n<k::TileDesc>(tiles.size());
+    ws.upload(d_tiles, tiles.data(), tiles.size() * sizeof(k::TileDesc));
+    const size_t chunk = (size_t)std::max(1, option(OPT_DET_TILE_BATCH)), tile_px = (size_t)in_h * in_w;
+    float* d_tin = ws.alloc_n<float>(std::min(chunk, tiles.size()) * tile_px);
+    float* d_tout = e.detection->is_callback() ? ws.alloc_n<float>(std::min(chunk, tiles.size()) * tile_px) : nullptr;
+    const size_t mark = ws.bufs.size();
+    for (size_t c0 = 0; c0 < tiles.size(); c0 += chunk) {
+        const int nt = (int)std::min(chunk, tiles.size() - c0);
+        {
+            StageScope sc(T, ST_RESIZE_IN, st);
+            k::gather_tiles(d_tiles + c0, nt, d_tin, in_h, in_w, st);
+        }
+        const float* d_tp = run_detector(e, ws, d_tin, nt, in_h, in_w, d_tout, nullptr);
+        {
+            StageScope sc(T, ST_RESIZE_THRESH, st);
+            k::stitch_threshold(d_tiles + c0, nt, d_tp, in_h, in_w, e.text_threshold, st);
+        }
+        if (c0 + chunk < tiles.size()) {   // the next chunk reuses this one's activations: drain, then hand them back
+            ws.sync();
+            while (ws.bufs.size() > mark) ws.bufs.pop_back();
+        }
+    }
+}
+
+// connected components -> rects (detection.rs:41-62)
+// Scratch is sized for pages of text: up to 65 536 components and 2 border points per pixel.  The reference
+// takes ANY mask (detection.rs:41-62), so a page that does not fit (salt noise, dense halftone) gets its
+// component stage re-run on its own with buffers for the worst case — rerun_overflow_page.
+k::CclBuffers alloc_ccl(Workspace& ws, int np, int h, int64_t px, int mc, int64_t ar, bool scored, bool zero) {
+    k::CclBuffers b{};
+    b.labels = ws.alloc_n<int32_t>((size_t)np * px);
+    b.row_counts = ws.alloc_n<int32_t>((size_t)np * h);
+    b.row_offsets = ws.alloc_n<int32_t>((size_t)np * h);
+    b.n_roots = ws.alloc_n<int32_t>(np);
+    b.roots = ws.alloc_n<int32_t>((size_t)np * mc);
+    b.lengths = ws.alloc_n<int32_t>((size_t)np * mc);
+    b.offsets = ws.alloc_n<int32_t>((size_t)np * mc);
+    b.overflow = ws.alloc_n<int32_t>(np);
+    b.pts = ws.alloc_n<uint32_t>((size_t)np * ar);
+    b.tmp = ws.alloc_n<uint32_t>((size_t)np * ar * 4);
+    b.keep = ws.alloc_n<uint8_t>((size_t)np * ar);
+    b.rects = ws.alloc_n<float>((size_t)np * mc * 6);
+    b.valid = ws.alloc_n<uint8_t>((size_t)np * mc);
+    if (scored) {
+        b.score_pixels = ws.alloc_n<uint32_t>((size_t)np * mc);
+        b.score_sums = ws.alloc_n<unsigned long long>((size_t)np * mc);
+    }
+    if (zero) OCRS_HIP(hipMemsetAsync(b.overflow, 0, np * sizeof(int32_t), ws.s()));
+    return b;
+}
+
+void run_ccl(const ocrs_engine& e, Workspace& ws, const uint8_t* mask, const float* map, int np, int h, int w, const k::CclBuffers& b,
+             int mc, int64_t ar, bool scored, bool prepared) {
+    StageTimers* T = e.tm();
+    hipStream_t cs = ws.s();
+    {
+        StageScope sc(T, ST_CCL, cs, prepared ? 3 : 4);
+        k::ccl_label(mask, np, h, w, b, mc, cs, prepared);
+    }
+    if (scored) {   // two fills and one kernel, counted with the component stage
+        StageScope sc(T, ST_CCL, cs, 3);
+        k::component_scores(mask, map, np, h, w, b, mc, cs);
+    }
+    {
+        StageScope sc(T, ST_CONTOUR_RECTS, cs, prepared ? 1 : 2);
+        k::contour_rects(mask, np, h, w, b, mc, ar, /*expand*/ 3.0f, e.min_area, /*eps*/ 2.0f, cs, prepared);
+    }
+}
+
+struct PageCandidates {   // one page's candidate components on the host; detect_now compacts them by valid[]
+    int32_t count = 0;
+    std::vector<float> hr;         // [>= count][6] rects
+    std::vector<uint8_t> hv;       // valid
+    std::vector<uint32_t> hpx;     // scored: the candidates' pixel counts and fixed-point sums
+    std::vector<uint64_t> hsum;
+};
+
+// queues the download of the `count` candidates of page slot `slot` of `b`, whose slots hold `stride` candidates each
+void fetch_candidates(Workspace& ws, const k::CclBuffers& b, size_t slot, size_t stride, int32_t count, bool scored, PageCandidates* pc) {
+    const size_t at = slot * stride;
+    pc->count = count;
+    pc->hr.resize((size_t)count * 6);
+    pc->hv.resize(count);
+    ws.download(pc->hr.data(), b.rects + at * 6, pc->hr.size() * sizeof(float));
+    ws.download(pc->hv.data(), b.valid + at, count);
+    if (scored) {
+        pc->hpx.resize(count);
+        pc->hsum.resize(count);
+        ws.download(pc->hpx.data(), b.score_pixels + at, (size_t)count * sizeof(uint32_t));
+        ws.download(pc->hsum.data(), b.score_sums + at, (size_t)count * sizeof(uint64_t));
+    }
+}
+
+// the component stage of page j of `g` (the caller's page `page_no`) again, alone, with buffers for the worst case
+void rerun_overflow_page(const ocrs_engine& e, Workspace& ws, const SizeGroup& g, int j, int page_no, bool scored, PageCandidates* pc) {
+    // Worst case of an h x w mask: no more than px / 4 + O(h + w) 8-connected components can be pairwise
+    // separated, and a border walk enters a pixel at most once per direction (8 px points in total).
+    const int64_t mc64 = g.px / 4 + (int64_t)g.h + g.w + 16, ar_big = 8 * g.px + 64;
+    if (ar_big >= (int64_t)0x7fffffff)
+        fail(OCRS_ERR_CAPACITY, "text mask of page %d: %lld pixels exceed the 32-bit contour arena", page_no, (long long)g.px);
+    const int mc = (int)mc64;
+    const k::CclBuffers bb = alloc_ccl(ws, 1, g.h, g.px, mc, ar_big, scored, true);
+    run_ccl(e, ws, g.d_mask + (size_t)j * g.px, g.d_map ? g.d_map + (size_t)j * g.px : nullptr, 1, g.h, g.w, bb, mc, ar_big, scored, false);
+    int32_t cnt = 0, o = 0;
+    ws.download(&cnt, bb.n_roots, sizeof cnt);
+    ws.download(&o, bb.overflow, sizeof o);
+    ws.sync();
+    if (o || cnt > mc)
+        fail(OCRS_ERR_DEVICE, "internal: component stage of page %d overflowed its worst-case buffers (%d components)", page_no, cnt);
+    fetch_candidates(ws, bb, 0, (size_t)mc, cnt, scored, pc);
+    ws.sync();
+}
+
+// The component stage of every size group and its results on the host, per page in grouped order.
+// One round trip in the common case: the counts travel together with the first kSpec candidate rects of every
+// page (a page of text has a few hundred to ~1 500 components); only a page with more needs a second one.
+std::vector<PageCandidates> component_candidates(const ocrs_engine& e, Workspace& ws, const PageGroups& pg, bool scored) {
+    constexpr int kSpec = 2048;
+    struct Prefix {   // one size group's counts and speculative candidates
+        std::vector<int32_t> counts, ovf;
+        PageCandidates all;   // [count pages][spec]
+    };
+    std::vector<Prefix> prefix(pg.groups.size());
+    for (size_t gi = 0; gi < pg.groups.size(); gi++) {
+        const SizeGroup& g = pg.groups[gi];
+        Prefix& p = prefix[gi];
+        run_ccl(e, ws, g.d_mask, g.d_map, g.count, g.h, g.w, g.b, g.max_comp, g.arena, scored, g.prepared);
+        const size_t spec = (size_t)std::min(g.max_comp, kSpec);
+        p.counts.resize(g.count); p.ovf.resize(g.count);
+        p.all.hr.resize(g.count * spec * 6); p.all.hv.resize(g.count * spec);
+        ws.download(p.counts.data(), g.b.n_roots, g.count * sizeof(int32_t));
+        ws.download(p.ovf.data(), g.b.overflow, g.count * sizeof(int32_t));
+        // the first `spec` candidates of every page in ONE strided copy per array (r2: two copies per page — each a blit
+        // kernel that waits for CU slots like any other)
+        ws.download_2d(p.all.hr.data(), g.b.rects, (size_t)g.max_comp * 6 * sizeof(float), spec * 6 * sizeof(float), g.count);
+        ws.download_2d(p.all.hv.data(), g.b.valid, (size_t)g.max_comp, spec, g.count);
+        if (scored) {
+            p.all.hpx.resize(g.count * spec); p.all.hsum.resize(g.count * spec);
+            ws.download_2d(p.all.hpx.data(), g.b.score_pixels, (size_t)g.max_comp * sizeof(uint32_t), spec * sizeof(uint32_t), g.count);
+            ws.download_2d(p.all.hsum.data(), g.b.score_sums, (size_t)g.max_comp * sizeof(uint64_t), spec * sizeof(uint64_t), g.count);
+        }
+    }
+    ws.sync();   // one wait for all sizes
+    std::vector<PageCandidates> cand(pg.order.size());
+    bool more = false;
+    std::vector<int> big;   // pages (grouped order) whose component stage did not fit
+    for (size_t gi = 0; gi < pg.groups.size(); gi++) {
+        const SizeGroup& g = pg.groups[gi];
+        const Prefix& p = prefix[gi];
+        const size_t spec = (size_t)std::min(g.max_comp, kSpec);
+        for (int j = 0; j < g.count; j++) {
+            PageCandidates& pc = cand[g.first + j];
+            const int32_t cnt = p.counts[j];
+            if (p.ovf[j] || cnt > g.max_comp) { big.push_back(g.first + j); continue; }
+            if ((size_t)cnt > spec) {   // the second trip
+                more = true;
+                fetch_candidates(ws, g.b, (size_t)j, (size_t)g.max_comp, cnt, scored, &pc);
+                continue;
+            }
+            pc.count = cnt;
+            pc.hr.assign(p.all.hr.begin() + j * spec * 6, p.all.hr.begin() + (j + 1) * spec * 6);
+            pc.hv.assign(p.all.hv.begin() + j * spec, p.all.hv.begin() + (j + 1) * spec);
+            if (scored) {
+                pc.hpx.assign(p.all.hpx.begin() + j * spec, p.all.hpx.begin() + (j + 1) * spec);
+                pc.hsum.assign(p.all.hsum.begin() + j * spec, p.all.hsum.begin() + (j + 1) * spec);
+            }
+        }
+    }
+    if (more) ws.sync();
+    for (int i : big) {
+        const SizeGroup& g = pg.groups[pg.group_of[i]];
+        rerun_overflow_page(e, ws, g, i - g.first, pg.order[i], scored, &cand[i]);
+    }
+    return cand;
+}
+
+}  // namespace
+
 void ocrs_engine::detect_now(const ocrs_page* const* pages, size_t n, std::vector<std::vector<RotatedRect>>* rects_out,
                              float* host_map, DetScores* scores, int tile_overlap) const {
     if (!detection) fail(OCRS_ERR_MODEL_NOT_LOADED, "Detection model not loaded");
@@ -52,225 +332,61 @@ void ocrs_engine::detect_now(const ocrs_page* const* pages, size_t n, std::vecto
     const bool tiled = tile_overlap >= 0;
     if (tiled && tile_overlap > std::min(in_h, in_w) / 2)
         fail(OCRS_ERR_INVALID_ARGUMENT, "tile overlap %d: at most half the model input's shorter side (%d)", tile_overlap, std::min(in_h, in_w) / 2);
-    // The reference takes any image per call (detection.rs:131-171) and the model always runs at its own fixed size, so a
-    // batch may hold pages of SEVERAL sizes (r6; the coalescer merges whatever waits): the model runs once over all of them,
-    // the size-dependent kernels before and after it (resize in; resize back + threshold, components, contours) run once per
-    // size, on that size's pages — the same launches with the same arguments as a batch of that size alone, so nobody's bits
-    // change.  Internally the pages are ordered by size group (`order`); results go back in the caller's order.
-    struct SizeGroup {
-        int h = 0, w = 0, first = 0, count = 0;          // pages [first, first + count) of the grouped order
-        int pad_bottom = 0, pad_right = 0, max_comp = 0;
-        int64_t px = 0, arena = 0;
-        uint8_t* d_mask = nullptr;
-        float* d_map = nullptr;                          // page-resolution probabilities: scored requests (and host_map) only
-        k::CclBuffers b{};
-        std::vector<int32_t> counts, ovf;
-        std::vector<float> hr_all;
-        std::vector<uint8_t> hv_all;
-        std::vector<uint32_t> hp_all;                    // scored: the candidates' pixel counts and fixed-point sums
-        std::vector<uint64_t> hs_all;
-    };
-    std::vector<SizeGroup> groups;
-    std::vector<int> order(n), group_of(n);
-    {
-        std::vector<int> gi(n);
-        for (size_t i = 0; i < n; i++) {
-            const int h = pages[i]->h, w = pages[i]->w;
-            if (h <= 0 || w <= 0 || h > 65535 || w > 65535) fail(OCRS_ERR_INVALID_ARGUMENT, "unsupported page size %dx%d", h, w);
-            size_t g = 0;
-            while (g < groups.size() && (groups[g].h != h || groups[g].w != w)) g++;
-            if (g == groups.size()) { groups.emplace_back(); groups[g].h = h; groups[g].w = w; }
-            groups[g].count++;
-            gi[i] = (int)g;
-        }
-        if (host_map && groups.size() > 1)
-            fail(OCRS_ERR_INVALID_ARGUMENT, "pages whose probability maps are returned in one [n, h, w] array must share a size");
-        int at = 0;
-        for (SizeGroup& g : groups) { g.first = at; at += g.count; g.count = 0; }
-        for (size_t i = 0; i < n; i++) {
-            SizeGroup& g = groups[gi[i]];
-            order[g.first + g.count] = (int)i;
-            group_of[g.first + g.count] = gi[i];
-            g.count++;
-        }
-    }
+    PageGroups pg = group_pages_by_size(pages, n);
+    std::vector<SizeGroup>& groups = pg.groups;
+    if (host_map && groups.size() > 1)
+        fail(OCRS_ERR_INVALID_ARGUMENT, "pages whose probability maps are returned in one [n, h, w] array must share a size");
 
     Workspace ws;
     hipStream_t st = ws.s();
     StageTimers* T = tm();
-    hipStream_t ex = st;   // (round 3 could route a small request's kernels through the device's conv-stack stream — option det_heavy,
-                           // off since round 4: 180 vs 194 pages/s for one-page calls from 12 threads — removed in round 5)
 
     // page pointer table, grouped order
     std::vector<const float*> hp(n);
-    for (size_t i = 0; i < n; i++) hp[i] = pages[order[i]]->grey.as<float>();
-    const float** d_ptrs = tiled ? nullptr : ws.alloc_n<const float*>(n);
-    if (!tiled) ws.upload(d_ptrs, hp.data(), n * sizeof(float*));
+    for (size_t i = 0; i < n; i++) hp[i] = pages[pg.order[i]]->grey.as<float>();
 
-    // `trait Model` implemented by the caller: one run per model input, host tensors (detection.rs:184)
-    auto run_callback = [&](const float* d_src, float* d_dst) {
-        const auto* cb = static_cast<const CallbackModel*>(detection);
-        std::vector<float> hin((size_t)in_h * in_w), hout;
-        ws.download(hin.data(), d_src, hin.size() * sizeof(float));
-        ws.sync();
-        const int64_t ishape[4] = {1, 1, in_h, in_w};
-        int64_t oshape[4];
-        int ond = 0;
-        cb->run(hin.data(), ishape, hout, oshape, &ond);
-        if (ond != 4 || oshape[2] != in_h || oshape[3] != in_w || oshape[0] * oshape[1] != 1)
-            fail(OCRS_ERR_WRONG_OUTPUT, "model output had unexpected type or shape: detection output is not [1,1,%d,%d]",
-                 in_h, in_w);
-        OCRS_HIP(hipMemcpyAsync(d_dst, hout.data(), hout.size() * sizeof(float), hipMemcpyHostToDevice, st));
-        ws.sync();
-    };
-
-    float* d_in = tiled ? nullptr : ws.alloc_n<float>((size_t)N * in_h * in_w);
+    const float* d_prob = nullptr;   // tiled: the model runs per chunk of tiles, once the pages' masks exist (below)
     if (!tiled) {
-        StageScope sc(T, ST_RESIZE_IN, ex, groups.size());
-        for (SizeGroup& g : groups) {
-            g.pad_bottom = std::max(in_h - g.h, 0);   // detection.rs:155-156
-            g.pad_right = std::max(in_w - g.w, 0);
-            k::resize_pages_to_model(d_ptrs + g.first, g.count, g.h, g.w, g.h + g.pad_bottom, g.w + g.pad_right,
-                                     d_in + (size_t)g.first * in_h * in_w, in_h, in_w, ex);
-        }
-    }
-
-    const float* d_prob = nullptr;
-    if (tiled) {
-        // the model runs per chunk of tiles, once the pages' masks exist (below)
-    } else if (detection->is_callback()) {
-        float* d_out = ws.alloc_n<float>((size_t)N * in_h * in_w);
-        for (int oi = 0; oi < N; oi++) {
-            int i = 0;
-            while (order[i] != oi) i++;      // runs in the CALLER's page order (a caller's model may count its runs)
-            run_callback(d_in + (size_t)i * in_h * in_w, d_out + (size_t)i * in_h * in_w);
-        }
-        d_prob = d_out;
-    } else {
-        const auto* hm = static_cast<const HipModel*>(detection);
-        TensorShape os;
-        d_prob = hm->run_device(ws, d_in, N, in_h, in_w, &os, T, nullptr, nullptr, true, debug, -1, nullptr);
-        if (os.n != N || os.h != in_h || os.w != in_w || os.c != 1)
-            fail(OCRS_ERR_WRONG_OUTPUT, "model output had unexpected type or shape: detection output [%d,%d,%d,%d]", os.n,
-                 os.c, os.h, os.w);
-    }
-
-    // connected components -> rects (detection.rs:41-62)
-    // Scratch is sized for pages of text: up to 65 536 components and 2 border points per pixel.  The reference
-    // takes ANY mask (detection.rs:41-62), so a page that does not fit (salt noise, dense halftone) gets its
-    // component stage re-run on its own with buffers for the worst case — below.
-    auto alloc_ccl = [&](int np, int h, int64_t px, int mc, int64_t ar, hipStream_t cs, bool zero) {
-        k::CclBuffers b{};
-        b.labels = ws.alloc_n<int32_t>((size_t)np * px);
-        b.row_counts = ws.alloc_n<int32_t>((size_t)np * h);
-        b.row_offsets = ws.alloc_n<int32_t>((size_t)np * h);
-        b.n_roots = ws.alloc_n<int32_t>(np);
-        b.roots = ws.alloc_n<int32_t>((size_t)np * mc);
-        b.lengths = ws.alloc_n<int32_t>((size_t)np * mc);
-        b.offsets = ws.alloc_n<int32_t>((size_t)np * mc);
-        b.overflow = ws.alloc_n<int32_t>(np);
-        b.pts = ws.alloc_n<uint32_t>((size_t)np * ar);
-        b.tmp = ws.alloc_n<uint32_t>((size_t)np * ar * 4);
-        b.keep = ws.alloc_n<uint8_t>((size_t)np * ar);
-        b.rects = ws.alloc_n<float>((size_t)np * mc * 6);
-        b.valid = ws.alloc_n<uint8_t>((size_t)np * mc);
-        if (scores) {
-            b.score_pixels = ws.alloc_n<uint32_t>((size_t)np * mc);
-            b.score_sums = ws.alloc_n<unsigned long long>((size_t)np * mc);
-        }
-        if (zero) OCRS_HIP(hipMemsetAsync(b.overflow, 0, np * sizeof(int32_t), cs));
-        return b;
-    };
-    auto run_ccl = [&](const uint8_t* mask, const float* map, int np, int h, int w, const k::CclBuffers& b, int mc, int64_t ar,
-                       hipStream_t cs, bool prepared) {
+        const float** d_ptrs = ws.alloc_n<const float*>(n);
+        ws.upload(d_ptrs, hp.data(), n * sizeof(float*));
+        float* d_in = ws.alloc_n<float>((size_t)N * in_h * in_w);
         {
-            StageScope sc(T, ST_CCL, cs, prepared ? 3 : 4);
-            k::ccl_label(mask, np, h, w, b, mc, cs, prepared);
+            StageScope sc(T, ST_RESIZE_IN, st, groups.size());
+            for (SizeGroup& g : groups) {
+                g.pad_bottom = std::max(in_h - g.h, 0);   // detection.rs:155-156
+                g.pad_right = std::max(in_w - g.w, 0);
+                k::resize_pages_to_model(d_ptrs + g.first, g.count, g.h, g.w, g.h + g.pad_bottom, g.w + g.pad_right,
+                                         d_in + (size_t)g.first * in_h * in_w, in_h, in_w, st);
+            }
         }
-        if (scores) {   // two fills and one kernel, counted with the component stage
-            StageScope sc(T, ST_CCL, cs, 3);
-            k::component_scores(mask, map, np, h, w, b, mc, cs);
-        }
-        {
-            StageScope sc(T, ST_CONTOUR_RECTS, cs, prepared ? 1 : 2);
-            k::contour_rects(mask, np, h, w, b, mc, ar, /*expand*/ 3.0f, min_area, /*eps*/ 2.0f, cs, prepared);
-        }
-    };
+        // a callback model runs in the CALLER's page order (a caller's model may count its runs)
+        float* d_out = detection->is_callback() ? ws.alloc_n<float>((size_t)N * in_h * in_w) : nullptr;
+        d_prob = run_detector(*this, ws, d_in, N, in_h, in_w, d_out, pg.pos_of.data());
+    }
 
     // slice off the padded region, resize back, threshold (detection.rs:187-194,110); r6: where the page width allows, the same
     // launch writes the component stage's initial labels and zeroes its counters (one launch and two fills fewer per size)
     float* d_map = host_map ? ws.alloc_n<float>((size_t)N * groups[0].h * groups[0].w) : nullptr;
-    std::vector<char> prepared(groups.size(), 0);
     {
-        StageScope sc(T, ST_RESIZE_THRESH, ex, tiled ? 0 : groups.size());
-        for (size_t gi = 0; gi < groups.size(); gi++) {
-            SizeGroup& g = groups[gi];
+        StageScope sc(T, ST_RESIZE_THRESH, st, tiled ? 0 : groups.size());
+        for (SizeGroup& g : groups) {
             g.px = (int64_t)g.h * g.w;
             g.d_mask = ws.alloc_n<uint8_t>((size_t)g.count * g.px);
             if (rects_out) {
                 g.max_comp = (int)std::min<int64_t>(65536, g.px / 2 + 16);
                 g.arena = 2 * g.px + 64;
-                g.b = alloc_ccl(g.count, g.h, g.px, g.max_comp, g.arena, ex, false);
+                g.b = alloc_ccl(ws, g.count, g.h, g.px, g.max_comp, g.arena, scores != nullptr, false);
             }
             // a scored request keeps every size's map (host_map: one size, one array)
             g.d_map = d_map ? d_map : scores ? ws.alloc_n<float>((size_t)g.count * g.px) : nullptr;
-            if (tiled) {   // stitch_threshold fills the mask and the map; the component stage takes its unprepared path
-                if (rects_out) OCRS_HIP(hipMemsetAsync(g.b.overflow, 0, g.count * sizeof(int32_t), ex));
-                continue;
-            }
-            prepared[gi] = k::resize_threshold(d_prob + (size_t)g.first * in_h * in_w, g.count, in_h, in_w, in_h - g.pad_bottom, in_w - g.pad_right,
-                                               text_threshold, g.d_mask, g.d_map, g.h, g.w, ex, g.b.labels, g.b.overflow, g.b.offsets);
-            if (rects_out && !prepared[gi]) OCRS_HIP(hipMemsetAsync(g.b.overflow, 0, g.count * sizeof(int32_t), ex));
+            // tiled: stitch_threshold fills the mask and the map; the component stage takes its unprepared path
+            if (!tiled)
+                g.prepared = k::resize_threshold(d_prob + (size_t)g.first * in_h * in_w, g.count, in_h, in_w, in_h - g.pad_bottom, in_w - g.pad_right,
+                                                 text_threshold, g.d_mask, g.d_map, g.h, g.w, st, g.b.labels, g.b.overflow, g.b.offsets);
+            if (rects_out && !g.prepared) OCRS_HIP(hipMemsetAsync(g.b.overflow, 0, g.count * sizeof(int32_t), st));
         }
     }
-    if (tiled) {
-        // Tiles of the whole request in the caller's page order, row-major within a page (a caller's model sees them in that
-        // order); gather -> model -> stitch per chunk of at most det_tile_batch tiles, so the activations of a request are
-        // bounded whatever the page size.  Owned rectangles are disjoint: chunks need no ordering among themselves.
-        std::vector<k::TileDesc> tiles;
-        for (int oi = 0; oi < N; oi++) {
-            int i = 0;
-            while (order[i] != oi) i++;
-            const SizeGroup& g = groups[group_of[i]];
-            const TileAxisPlan py = tile_axis_plan(g.h, in_h, tile_overlap), px = tile_axis_plan(g.w, in_w, tile_overlap);
-            const size_t at = (size_t)(i - g.first) * g.px;
-            for (size_t ty = 0; ty < py.origin.size(); ty++)
-                for (size_t tx = 0; tx < px.origin.size(); tx++)
-                    tiles.push_back(k::TileDesc{hp[i], g.d_mask + at, g.d_map ? g.d_map + at : nullptr, g.h, g.w, py.origin[ty], px.origin[tx],
-                                                py.bound[ty], py.bound[ty + 1], px.bound[tx], px.bound[tx + 1]});
-        }
-        k::TileDesc* d_tiles = ws.alloc_n<k::TileDesc>(tiles.size());
-        ws.upload(d_tiles, tiles.data(), tiles.size() * sizeof(k::TileDesc));
-        const size_t chunk = (size_t)std::max(1, option(OPT_DET_TILE_BATCH)), tile_px = (size_t)in_h * in_w;
-        float* d_tin = ws.alloc_n<float>(std::min(chunk, tiles.size()) * tile_px);
-        float* d_tout = detection->is_callback() ? ws.alloc_n<float>(std::min(chunk, tiles.size()) * tile_px) : nullptr;
-        const size_t mark = ws.bufs.size();
-        for (size_t c0 = 0; c0 < tiles.size(); c0 += chunk) {
-            const int nt = (int)std::min(chunk, tiles.size() - c0);
-            {
-                StageScope sc(T, ST_RESIZE_IN, ex);
-                k::gather_tiles(d_tiles + c0, nt, d_tin, in_h, in_w, ex);
-            }
-            const float* d_tp = d_tout;
-            if (d_tout) {
-                for (int t = 0; t < nt; t++) run_callback(d_tin + (size_t)t * tile_px, d_tout + (size_t)t * tile_px);
-            } else {
-                TensorShape os;
-                d_tp = static_cast<const HipModel*>(detection)->run_device(ws, d_tin, nt, in_h, in_w, &os, T, nullptr, nullptr, true, debug, -1, nullptr);
-                if (os.n != nt || os.h != in_h || os.w != in_w || os.c != 1)
-                    fail(OCRS_ERR_WRONG_OUTPUT, "model output had unexpected type or shape: detection output [%d,%d,%d,%d]", os.n,
-                         os.c, os.h, os.w);
-            }
-            {
-                StageScope sc(T, ST_RESIZE_THRESH, ex);
-                k::stitch_threshold(d_tiles + c0, nt, d_tp, in_h, in_w, text_threshold, ex);
-            }
-            if (c0 + chunk < tiles.size()) {   // the next chunk reuses this one's activations: drain, then hand them back
-                ws.sync();
-                while (ws.bufs.size() > mark) ws.bufs.pop_back();
-            }
-        }
-    }
+    if (tiled) run_detector_tiled(*this, ws, pg, hp, in_h, in_w, tile_overlap);
     if (host_map)   // (one size group: grouped order = the caller's order)
         ws.download(host_map, d_map, (size_t)N * groups[0].px * sizeof(float));
     if (!rects_out) {
@@ -279,105 +395,19 @@ void ocrs_engine::detect_now(const ocrs_page* const* pages, size_t n, std::vecto
         return;
     }
 
-    // One round trip in the common case: the counts travel together with the first kSpec candidate rects of every
-    // page (a page of text has a few hundred to ~1 500 components); only a page with more needs a second one.
-    constexpr int kSpec = 2048;
-    for (size_t gi = 0; gi < groups.size(); gi++) {
-        SizeGroup& g = groups[gi];
-        run_ccl(g.d_mask, g.d_map, g.count, g.h, g.w, g.b, g.max_comp, g.arena, ex, prepared[gi] != 0);
-        const int spec = std::min(g.max_comp, kSpec);
-        g.counts.resize(g.count); g.ovf.resize(g.count);
-        g.hr_all.resize((size_t)g.count * spec * 6); g.hv_all.resize((size_t)g.count * spec);
-        ws.download(g.counts.data(), g.b.n_roots, g.count * sizeof(int32_t));
-        ws.download(g.ovf.data(), g.b.overflow, g.count * sizeof(int32_t));
-        // the first `spec` candidates of every page in ONE strided copy per array (r2: two copies per page — each a blit
-        // kernel that waits for CU slots like any other)
-        ws.download_2d(g.hr_all.data(), g.b.rects, (size_t)g.max_comp * 6 * sizeof(float), (size_t)spec * 6 * sizeof(float), g.count);
-        ws.download_2d(g.hv_all.data(), g.b.valid, (size_t)g.max_comp, (size_t)spec, g.count);
-        if (scores) {
-            g.hp_all.resize((size_t)g.count * spec); g.hs_all.resize((size_t)g.count * spec);
-            ws.download_2d(g.hp_all.data(), g.b.score_pixels, (size_t)g.max_comp * sizeof(uint32_t), (size_t)spec * sizeof(uint32_t), g.count);
-            ws.download_2d(g.hs_all.data(), g.b.score_sums, (size_t)g.max_comp * sizeof(uint64_t), (size_t)spec * sizeof(uint64_t), g.count);
-        }
-    }
-    ws.sync();   // one wait for all sizes
-    std::vector<int32_t> counts(N);
-    std::vector<std::vector<float>> hr(N);
-    std::vector<std::vector<uint8_t>> hv(N);
-    std::vector<std::vector<uint32_t>> hpx(scores ? N : 0);
-    std::vector<std::vector<uint64_t>> hsum(scores ? N : 0);
+    const std::vector<PageCandidates> cand = component_candidates(*this, ws, pg, scores != nullptr);
     rects_out->assign(n, {});
-    bool more = false;
-    std::vector<int> big;   // pages (grouped order) whose component stage did not fit
-    for (const SizeGroup& g : groups) {
-        const int spec = std::min(g.max_comp, kSpec);
-        for (int j = 0; j < g.count; j++) {
-            const int i = g.first + j, cnt = g.counts[j];
-            counts[i] = cnt;
-            if (g.ovf[j] || cnt > g.max_comp) { big.push_back(i); continue; }
-            if (cnt <= spec) {
-                hr[i].assign(g.hr_all.begin() + (size_t)j * spec * 6, g.hr_all.begin() + (size_t)(j + 1) * spec * 6);
-                hv[i].assign(g.hv_all.begin() + (size_t)j * spec, g.hv_all.begin() + (size_t)(j + 1) * spec);
-                if (scores) {
-                    hpx[i].assign(g.hp_all.begin() + (size_t)j * spec, g.hp_all.begin() + (size_t)(j + 1) * spec);
-                    hsum[i].assign(g.hs_all.begin() + (size_t)j * spec, g.hs_all.begin() + (size_t)(j + 1) * spec);
-                }
-                continue;
-            }
-            more = true;
-            hr[i].resize((size_t)cnt * 6);
-            hv[i].resize(cnt);
-            ws.download(hr[i].data(), g.b.rects + (size_t)j * g.max_comp * 6, hr[i].size() * sizeof(float));
-            ws.download(hv[i].data(), g.b.valid + (size_t)j * g.max_comp, cnt);
-            if (scores) {
-                hpx[i].resize(cnt);
-                hsum[i].resize(cnt);
-                ws.download(hpx[i].data(), g.b.score_pixels + (size_t)j * g.max_comp, (size_t)cnt * sizeof(uint32_t));
-                ws.download(hsum[i].data(), g.b.score_sums + (size_t)j * g.max_comp, (size_t)cnt * sizeof(uint64_t));
-            }
-        }
-    }
-    if (more) ws.sync();
-    for (int i : big) {
-        const SizeGroup& g = groups[group_of[i]];
-        // Worst case of an h x w mask: no more than px / 4 + O(h + w) 8-connected components can be pairwise
-        // separated, and a border walk enters a pixel at most once per direction (8 px points in total).
-        const int64_t mc64 = g.px / 4 + (int64_t)g.h + g.w + 16, ar_big = 8 * g.px + 64;
-        if (ar_big >= (int64_t)0x7fffffff)
-            fail(OCRS_ERR_CAPACITY, "text mask of page %d: %lld pixels exceed the 32-bit contour arena", order[i], (long long)g.px);
-        const int mc = (int)mc64;
-        const k::CclBuffers bb = alloc_ccl(1, g.h, g.px, mc, ar_big, st, true);
-        run_ccl(g.d_mask + (size_t)(i - g.first) * g.px, g.d_map ? g.d_map + (size_t)(i - g.first) * g.px : nullptr, 1, g.h, g.w, bb, mc,
-                ar_big, st, false);
-        int32_t cnt = 0, o = 0;
-        ws.download(&cnt, bb.n_roots, sizeof cnt);
-        ws.download(&o, bb.overflow, sizeof o);
-        ws.sync();
-        if (o || cnt > mc)
-            fail(OCRS_ERR_DEVICE, "internal: component stage of page %d overflowed its worst-case buffers (%d components)", order[i], cnt);
-        counts[i] = cnt;
-        hr[i].resize((size_t)cnt * 6);
-        hv[i].resize(cnt);
-        ws.download(hr[i].data(), bb.rects, hr[i].size() * sizeof(float));
-        ws.download(hv[i].data(), bb.valid, cnt);
-        if (scores) {
-            hpx[i].resize(cnt);
-            hsum[i].resize(cnt);
-            ws.download(hpx[i].data(), bb.score_pixels, (size_t)cnt * sizeof(uint32_t));
-            ws.download(hsum[i].data(), bb.score_sums, (size_t)cnt * sizeof(uint64_t));
-        }
-        ws.sync();
-    }
     if (scores) { scores->score.assign(n, {}); scores->pixels.assign(n, {}); }
     for (int i = 0; i < N; i++) {
-        auto& out = (*rects_out)[order[i]];
-        for (int c = 0; c < counts[i]; c++) {
-            if (!hv[i][c]) continue;
-            out.push_back(RotatedRect::from_array(&hr[i][(size_t)c * 6]));
+        const PageCandidates& pc = cand[i];
+        auto& out = (*rects_out)[pg.order[i]];
+        for (int c = 0; c < pc.count; c++) {
+            if (!pc.hv[c]) continue;
+            out.push_back(RotatedRect::from_array(&pc.hr[(size_t)c * 6]));
             if (scores) {   // the compaction by valid[] that compacts the rects
-                const uint32_t px = hpx[i][c];
-                scores->pixels[order[i]].push_back(px);
-                scores->score[order[i]].push_back(px ? (float)((double)hsum[i][c] / ((double)px * 16777216.0)) : 0.0f);
+                const uint32_t px = pc.hpx[c];
+                scores->pixels[pg.order[i]].push_back(px);
+                scores->score[pg.order[i]].push_back(px ? (float)((double)pc.hsum[c] / ((double)px * 16777216.0)) : 0.0f);
             }
         }
     }
@@ -450,8 +480,7 @@ void ocrs_engine::init_coalescers() {
                     if (batch.size() == 1) {
                         RecRequest& r = *batch[0];
                         const std::vector<char> rp(r.rectify ? r.n_pages : 0, 1);
-                        recognize_now(r.pages, r.n_pages, *r.lines_per_page, r.steps, r.rec_lines, r.ctc_len, nullptr, r.scores,
-                                      r.rectify ? &rp : nullptr);
+                        recognize_now(r.pages, r.n_pages, *r.lines_per_page, r.results, r.scored, false, r.rectify ? &rp : nullptr);
                         return;
                     }
                     std::vector<const ocrs_page*> pages;
@@ -462,31 +491,20 @@ void ocrs_engine::init_coalescers() {
                     for (RecRequest* r : batch) {
                         pages.insert(pages.end(), r->pages, r->pages + r->n_pages);
                         lpp.insert(lpp.end(), r->lines_per_page->begin(), r->lines_per_page->end());
-                        any_scores = any_scores || r->scores;
+                        any_scores = any_scores || r->scored;
                         any_rectify = any_rectify || r->rectify;
                         rp.insert(rp.end(), r->n_pages, r->rectify ? 1 : 0);
                     }
-                    std::vector<std::vector<CtcStep>> steps;
-                    std::vector<RecLine> rl;
-                    std::vector<uint32_t> cl;
-                    RecScores sc;
-                    recognize_now(pages.data(), pages.size(), lpp, &steps, &rl, &cl, nullptr, any_scores ? &sc : nullptr,
-                                  any_rectify ? &rp : nullptr);
+                    std::vector<RecResult> res;
+                    recognize_now(pages.data(), pages.size(), lpp, &res, any_scores, false, any_rectify ? &rp : nullptr);
                     size_t line0 = 0, page0 = 0;
                     for (RecRequest* r : batch) {
                         size_t nl = 0;
                         for (const auto& pg : *r->lines_per_page) nl += pg.size();
-                        r->steps->assign(std::make_move_iterator(steps.begin() + line0), std::make_move_iterator(steps.begin() + line0 + nl));
-                        r->ctc_len->assign(cl.begin() + line0, cl.begin() + line0 + nl);
-                        if (r->scores) {
-                            r->scores->step_logp.assign(std::make_move_iterator(sc.step_logp.begin() + line0),
-                                                        std::make_move_iterator(sc.step_logp.begin() + line0 + nl));
-                            r->scores->line_score.assign(sc.line_score.begin() + line0, sc.line_score.begin() + line0 + nl);
-                        }
-                        r->rec_lines->assign(std::make_move_iterator(rl.begin() + line0), std::make_move_iterator(rl.begin() + line0 + nl));
-                        for (RecLine& l : *r->rec_lines) {   // back to the caller's numbering
-                            l.page -= page0;
-                            l.index -= line0;
+                        r->results->assign(std::make_move_iterator(res.begin() + line0), std::make_move_iterator(res.begin() + line0 + nl));
+                        for (RecResult& l : *r->results) {   // back to the caller's numbering
+                            l.line.page -= page0;
+                            l.line.index -= line0;
                         }
                         line0 += nl;
                         page0 += r->n_pages;
@@ -494,8 +512,7 @@ void ocrs_engine::init_coalescers() {
                 },
                 [&](RecRequest& r) {
                     const std::vector<char> rp(r.rectify ? r.n_pages : 0, 1);
-                    recognize_now(r.pages, r.n_pages, *r.lines_per_page, r.steps, r.rec_lines, r.ctc_len, nullptr, r.scores,
-                                  r.rectify ? &rp : nullptr);
+                    recognize_now(r.pages, r.n_pages, *r.lines_per_page, r.results, r.scored, false, r.rectify ? &rp : nullptr);
                 });
         },
         [](const RecRequest&, const RecRequest&) { return true; });   // lines of any pages share a ragged batch
@@ -518,19 +535,18 @@ void ocrs_engine::detect(const ocrs_page* const* pages, size_t n, std::vector<st
 }
 
 void ocrs_engine::recognize(const ocrs_page* const* pages, size_t n_pages,
-                            const std::vector<std::vector<std::vector<RotatedRect>>>& lines_per_page,
-                            std::vector<std::vector<CtcStep>>* steps_out, std::vector<RecLine>* rec_lines_out,
-                            std::vector<uint32_t>* ctc_len_out, RecScores* scores, bool rectify) const {
+                            const std::vector<std::vector<std::vector<RotatedRect>>>& lines_per_page, std::vector<RecResult>* results,
+                            bool scored, bool rectify) const {
     const int max_active = option(OPT_COALESCE);
     const size_t max_pages = (size_t)std::max(1, option(OPT_COALESCE_PAGES));
     if (max_active <= 0 || !rec_queue || n_pages == 0 || 2 * n_pages >= max_pages || !recognition || recognition->is_callback()) {
         const std::vector<char> rp(rectify ? n_pages : 0, 1);
-        recognize_now(pages, n_pages, lines_per_page, steps_out, rec_lines_out, ctc_len_out, nullptr, scores, rectify ? &rp : nullptr);
+        recognize_now(pages, n_pages, lines_per_page, results, scored, false, rectify ? &rp : nullptr);
         return;
     }
     RecRequest r;
     r.pages = pages; r.n_pages = n_pages; r.lines_per_page = &lines_per_page;
-    r.steps = steps_out; r.rec_lines = rec_lines_out; r.ctc_len = ctc_len_out; r.scores = scores; r.rectify = rectify; r.weight = n_pages;
+    r.results = results; r.scored = scored; r.rectify = rectify; r.weight = n_pages;
     rec_queue->submit(r, max_active, max_pages, option_long(OPT_COALESCE_WINDOW_US));
 }
 
@@ -738,6 +754,81 @@ RecLine ocrs_engine::make_rec_line(const std::vector<RotatedRect>& words, size_t
     return l;
 }
 
+// ---- crop + resize + pad every line into its place in one tensor (recognition.rs:135-158): one launch for all plain
+// lines and one for all rectified ones, whatever their widths
+float* ocrs::stage_line_crops(Workspace& ws, StageTimers* T, const ocrs_page* const* pages, size_t n_pages,
+                              const std::vector<CropLine>& crops, int rec_h, int64_t total) {
+    hipStream_t st = ws.s();
+    std::vector<const float*> hp(n_pages);
+    std::vector<int32_t> hhw(2 * n_pages);
+    for (size_t i = 0; i < n_pages; i++) {
+        hp[i] = pages[i]->grey.as<float>();
+        hhw[2 * i] = pages[i]->h;
+        hhw[2 * i + 1] = pages[i]->w;
+    }
+    const float** d_pages = ws.alloc_n<const float*>(n_pages);
+    int32_t* d_hw = ws.alloc_n<int32_t>(2 * n_pages);
+    ws.upload(d_pages, hp.data(), n_pages * sizeof(float*));
+    ws.upload(d_hw, hhw.data(), hhw.size() * sizeof(int32_t));
+
+    std::vector<k::LineDesc> descs;
+    std::vector<int32_t> poly;
+    std::vector<k::RectLineDesc> rdescs;   // the rectified lines: a launch of their own into the same tensor
+    std::vector<int32_t> ranges;
+    int rect_max_w = 0;
+    for (const CropLine& c : crops) {
+        const RecLine& ln = *c.line;
+        if (ln.rectified) {
+            k::RectLineDesc d{};
+            d.page = (int32_t)ln.page;
+            d.mode = ln.frame.empty ? 1 : 0;
+            d.range_off = (int32_t)(ranges.size() / 4);
+            d.range_n = ln.frame.empty ? 0 : (int32_t)(ln.frame.ranges.size() / 4);
+            d.resized_w = (int32_t)ln.resized_width;
+            d.out_w = (int32_t)c.out_w;
+            d.out_off = c.out_off;
+            d.x0 = ln.frame.coef[0]; d.ax = ln.frame.coef[1]; d.bx = ln.frame.coef[2];
+            d.y0 = ln.frame.coef[3]; d.ay = ln.frame.coef[4]; d.by = ln.frame.coef[5];
+            rdescs.push_back(d);
+            if (!ln.frame.empty) ranges.insert(ranges.end(), ln.frame.ranges.begin(), ln.frame.ranges.end());
+            rect_max_w = std::max(rect_max_w, (int)c.out_w);
+            continue;
+        }
+        k::LineDesc d{};
+        d.page = (int32_t)ln.page;
+        d.poly_off = (int32_t)(poly.size() / 2);
+        d.poly_n = (int32_t)ln.polygon.size();
+        d.top = ln.bounds.top; d.left = ln.bounds.left;
+        d.bh = ln.bounds.height(); d.bw = ln.bounds.width();
+        d.resized_w = (int32_t)ln.resized_width;
+        d.out_w = (int32_t)c.out_w;
+        d.out_off = c.out_off;
+        descs.push_back(d);
+        for (const PointI& p : ln.polygon) { poly.push_back(p.y); poly.push_back(p.x); }
+    }
+    if (descs.empty() && rdescs.empty()) return nullptr;
+    k::LineDesc* d_descs = descs.empty() ? nullptr : ws.alloc_n<k::LineDesc>(descs.size());
+    int32_t* d_poly = descs.empty() ? nullptr : ws.alloc_n<int32_t>(poly.size());
+    // host temporaries travel through the workspace's pinned staging: real asynchronous copies, no host wait here
+    if (!descs.empty()) {
+        ws.upload(d_descs, descs.data(), descs.size() * sizeof(k::LineDesc));
+        ws.upload(d_poly, poly.data(), poly.size() * sizeof(int32_t));
+    }
+    k::RectLineDesc* d_rdescs = nullptr;
+    int32_t* d_ranges = nullptr;
+    if (!rdescs.empty()) {
+        d_rdescs = ws.alloc_n<k::RectLineDesc>(rdescs.size());
+        d_ranges = ws.alloc_n<int32_t>(std::max<size_t>(ranges.size(), 4));
+        ws.upload(d_rdescs, rdescs.data(), rdescs.size() * sizeof(k::RectLineDesc));
+        if (!ranges.empty()) ws.upload(d_ranges, ranges.data(), ranges.size() * sizeof(int32_t));
+    }
+    float* d_all = ws.alloc_n<float>((size_t)total);
+    StageScope sc(T, ST_LINE_CROP, st, (descs.empty() ? 0 : 1) + (rdescs.empty() ? 0 : 1));
+    k::crop_lines(d_pages, d_hw, d_descs, d_poly, (int)descs.size(), rec_h, d_all, st);
+    k::rectify_lines(d_pages, d_hw, d_rdescs, d_ranges, (int)rdescs.size(), rect_max_w, rec_h, d_all, st);
+    return d_all;
+}
+
 // Activations of the recognition conv stack scale with the input (~100 B per input pixel of the padded line
 // batch).  A request beyond the budget is run as consecutive sub-requests over contiguous runs of its lines
 // (lines are independent: recognition.rs:448-503 itself works in chunks of 20), so the caller never has to
@@ -749,63 +840,39 @@ static double rec_pixel_budget() {
 
 void ocrs_engine::recognize_now(const ocrs_page* const* pages, size_t n_pages,
                                 const std::vector<std::vector<std::vector<RotatedRect>>>& lines_per_page,
-                                std::vector<std::vector<CtcStep>>* steps_out, std::vector<RecLine>* rec_lines_out,
-                                std::vector<uint32_t>* ctc_len_out, std::vector<std::vector<float>>* logp_out,
-                                RecScores* scores, const std::vector<char>* rectify_pages) const {
+                                std::vector<RecResult>* out, bool scored, bool want_logp,
+                                const std::vector<char>* rectify_pages) const {
     if (!recognition) fail(OCRS_ERR_MODEL_NOT_LOADED, "Recognition model not loaded");
     const uint32_t rec_h = rec_input_height();
-    std::vector<RecLine> lines;
+    size_t L = 0;
+    for (size_t p = 0; p < n_pages; p++) L += lines_per_page[p].size();
+    std::vector<RecResult>& res = *out;
+    res.clear();
+    res.resize(L);
+    L = 0;
     for (size_t p = 0; p < n_pages; p++)
-        for (const auto& words : lines_per_page[p])
-            lines.push_back(make_rec_line(words, p, lines.size(), rectify_pages && (*rectify_pages)[p]));
-    const size_t L = lines.size();
+        for (const auto& words : lines_per_page[p]) {
+            res[L].line = make_rec_line(words, p, L, rectify_pages && (*rectify_pages)[p]);
+            L++;
+        }
     const double budget = rec_pixel_budget();
-    double total = 0.0;
-    for (const RecLine& l : lines) total += (double)rec_h * l.group_width;
-    if (total <= budget) {
-        recognize_lines(pages, n_pages, lines, steps_out, ctc_len_out, logp_out, scores);
-        *rec_lines_out = std::move(lines);
-        return;
-    }
-    steps_out->assign(L, {});
-    ctc_len_out->assign(L, 0);
-    if (logp_out) logp_out->assign(L, {});
-    if (scores) {
-        scores->step_logp.assign(L, {});
-        scores->line_score.assign(L, 0.0);
-    }
-    for (size_t b = 0; b < L;) {
+    for (size_t b = 0; b < L;) {   // sub-requests within the budget, each of at least one line
         size_t e = b;
         double px = 0.0;
-        while (e < L && (e == b || px + (double)rec_h * lines[e].group_width <= budget)) px += (double)rec_h * lines[e++].group_width;
-        std::vector<RecLine> part(lines.begin() + b, lines.begin() + e);
-        std::vector<std::vector<CtcStep>> st;
-        std::vector<uint32_t> cl;
-        std::vector<std::vector<float>> lp;
-        RecScores sc;
-        recognize_lines(pages, n_pages, part, &st, &cl, logp_out ? &lp : nullptr, scores ? &sc : nullptr);
-        for (size_t i = b; i < e; i++) {
-            (*steps_out)[i] = std::move(st[i - b]);
-            (*ctc_len_out)[i] = cl[i - b];
-            if (logp_out) (*logp_out)[i] = std::move(lp[i - b]);
-            if (scores) {
-                scores->step_logp[i] = std::move(sc.step_logp[i - b]);
-                scores->line_score[i] = sc.line_score[i - b];
-            }
-        }
+        while (e < L && (e == b || px + (double)rec_h * res[e].line.group_width <= budget)) px += (double)rec_h * res[e++].line.group_width;
+        recognize_lines(pages, n_pages, res.data() + b, e - b, scored, want_logp);
         b = e;
     }
-    *rec_lines_out = std::move(lines);
 }
 
 void ocrs_engine::recognize_logits(const ocrs_page* page, const std::vector<std::vector<RotatedRect>>& lines_in,
                                    std::vector<std::vector<float>>* logp, int* classes) const {
     if (!recognition) fail(OCRS_ERR_MODEL_NOT_LOADED, "Recognition model not loaded");
     if (recognition->is_callback()) fail(OCRS_ERR_INVALID_ARGUMENT, "recognize_logits needs a model of the fixed-graph executor");
-    std::vector<std::vector<CtcStep>> steps;
-    std::vector<RecLine> lines;
-    std::vector<uint32_t> ctc_len;
-    recognize_now(&page, 1, {lines_in}, &steps, &lines, &ctc_len, logp);
+    std::vector<RecResult> res;
+    recognize_now(&page, 1, {lines_in}, &res, false, true);
+    logp->clear();
+    for (RecResult& r : res) logp->push_back(std::move(r.logp));
     *classes = (int)alphabet.size() + 1;
 }
 
@@ -931,434 +998,343 @@ void ocrs_engine::run_recognition_ops(const int32_t* widths, size_t n, int first
     }
 }
 
-void ocrs_engine::recognize_lines(const ocrs_page* const* pages, size_t n_pages, const std::vector<RecLine>& lines,
-                                  std::vector<std::vector<CtcStep>>* steps_out, std::vector<uint32_t>* ctc_len_out,
-                                  std::vector<std::vector<float>>* logp_out, RecScores* scores) const {
-    const bool beam = decode_method == OCRS_DECODE_BEAM_SEARCH;
-    if (logp_out) logp_out->assign(lines.size(), {});
-    if (scores) {   // lines without rows keep these: no steps, score 0
-        scores->step_logp.assign(lines.size(), {});
-        scores->line_score.assign(lines.size(), 0.0);
-    }
-    const uint32_t rec_h = rec_input_height();
-    const size_t alphabet_len = alphabet.size();
+namespace {
 
-    const size_t L = lines.size();
-    steps_out->assign(L, {});
-    ctc_len_out->assign(L, 0);
+struct Chunk { uint32_t gw; std::vector<size_t> members; int64_t off; float* ptr = nullptr; };
+
+// the model output is [T, lines, alphabet + blank] (recognition.rs:487-493)
+void check_rec_output(int ndim, int64_t batch, size_t lines, int classes, size_t alphabet_len) {
+    if (ndim != 3)
+        fail(OCRS_ERR_WRONG_OUTPUT,
+             "model output had unexpected type or shape: expected recognition output to have 3 dims but it has %d", ndim);
+    if ((size_t)batch != lines)
+        fail(OCRS_ERR_WRONG_OUTPUT, "model output had unexpected type or shape: batch size %lld != %zu", (long long)batch, lines);
+    if (alphabet_len + 1 != (size_t)classes)
+        fail(OCRS_ERR_WRONG_OUTPUT,
+             "model output had unexpected type or shape: output column count (%d) does not match alphabet size (%zu)",
+             classes, alphabet_len + 1);
+}
+
+// The decoded steps of M lines as the CTC kernels leave them: `stride` entries per line, counts[m] of them used.
+struct DecodedSteps {
+    int stride = 0;
+    std::vector<uint32_t> hl, hp;    // labels, positions
+    std::vector<int32_t> hc;         // counts
+    std::vector<float> hlp;          // scored on the GPU: step log-probs
+    std::vector<double> hscore;      // scored on the GPU: [M] line scores
+};
+
+// queues their download on `st` through `w` (d_slp / d_score null: not scored on the GPU)
+void download_steps(Workspace& w, hipStream_t st, size_t M, int stride, const uint32_t* d_ol, const uint32_t* d_op, const int32_t* d_cnt,
+                    const float* d_slp, const double* d_score, DecodedSteps* d) {
+    d->stride = stride;
+    d->hl.resize(M * stride);
+    d->hp.resize(M * stride);
+    d->hc.resize(M);
+    w.download(d->hl.data(), d_ol, d->hl.size() * 4, st);
+    w.download(d->hp.data(), d_op, d->hp.size() * 4, st);
+    w.download(d->hc.data(), d_cnt, M * 4, st);
+    if (d_slp) {
+        d->hlp.resize(M * stride);
+        d->hscore.resize(M);
+        w.download(d->hlp.data(), d_slp, d->hlp.size() * sizeof(float), st);
+        w.download(d->hscore.data(), d_score, M * sizeof(double), st);
+    }
+}
+
+// line m's slice of them, as the result's steps (and scores, if they came from the GPU)
+void take_steps(const DecodedSteps& d, size_t m, uint32_t ctc_len, RecResult* r) {
+    const size_t at = m * d.stride;
+    r->steps.resize(d.hc[m]);
+    for (int q = 0; q < d.hc[m]; q++) r->steps[q] = CtcStep{d.hl[at + q], d.hp[at + q]};
+    r->ctc_len = ctc_len;
+    if (!d.hscore.empty()) {
+        r->step_logp.assign(d.hlp.data() + at, d.hlp.data() + at + d.hc[m]);
+        r->line_score = d.hscore[m];
+    }
+}
+
+// rten decode_beam (recognition.rs:512-514) on the host for one line of T rows, row(t) its t-th row of C log-probs:
+// masked as recognition.rs:547-561 does.  seq: scratch.
+template <class Row>
+void beam_decode_line(const ocrs_engine& e, int T, int C, Row row, std::vector<float>& seq, bool scored, RecResult* r) {
+    seq.resize((size_t)T * C);
+    for (int t = 0; t < T; t++) {
+        const float* src = row(t);
+        for (int c = 0; c < C; c++)
+            seq[(size_t)t * C + c] = (e.has_excluded && e.excluded[c]) ? -std::numeric_limits<float>::infinity() : src[c];
+    }
+    double bs = 0.0;
+    r->steps = ctc_beam_search(seq.data(), T, C, C, e.beam_width, scored ? &bs : nullptr);
+    r->ctc_len = (uint32_t)T;
+    if (scored) score_line(seq.data(), T, C, C, nullptr, r->steps, &bs, &r->step_logp, &r->line_score);
+}
+
+// ---- `trait Model` implemented by the caller: one run per <=20-line chunk (recognition.rs:485)
+void recognize_callback(const ocrs_engine& e, Workspace& ws, const std::vector<Chunk>& chunks, RecResult* res, bool scored) {
+    const auto* cb = static_cast<const CallbackModel*>(e.recognition);
+    const bool beam = e.decode_method == OCRS_DECODE_BEAM_SEARCH;
+    const uint32_t rec_h = e.rec_input_height();
+    const uint8_t* d_excl = e.has_excluded ? e.d_excluded.as<uint8_t>() : nullptr;
+    hipStream_t st = ws.s();
+    std::vector<float> seq;
+    for (const Chunk& ch : chunks) {
+        const size_t nb = ch.members.size();
+        const uint32_t gw = ch.gw;
+        std::vector<float> hin(nb * rec_h * gw), hout;
+        ws.download(hin.data(), ch.ptr, hin.size() * sizeof(float));
+        ws.sync();
+        const int64_t ishape[4] = {(int64_t)nb, 1, rec_h, gw};
+        int64_t oshape[4] = {0, 0, 0, 0};
+        int ond = 0;
+        cb->run(hin.data(), ishape, hout, oshape, &ond);
+        check_rec_output(ond, oshape[1], nb, (int)oshape[2], e.alphabet.size());
+        const int Tn = (int)oshape[0], C = (int)oshape[2];
+        if (beam) {  // decode_beam on the model output: line j's row t is hout[(t * nb + j) * C]
+            for (size_t j = 0; j < nb; j++)
+                beam_decode_line(e, Tn, C, [&](int t) { return &hout[((size_t)t * nb + j) * C]; }, seq, scored, &res[ch.members[j]]);
+            continue;
+        }
+        float* d_logp = ws.alloc_n<float>(hout.size());
+        OCRS_HIP(hipMemcpyAsync(d_logp, hout.data(), hout.size() * sizeof(float), hipMemcpyHostToDevice, st));
+        int32_t* d_labels = ws.alloc_n<int32_t>((size_t)Tn * nb);
+        uint32_t* d_ol = ws.alloc_n<uint32_t>((size_t)nb * Tn);
+        uint32_t* d_op = ws.alloc_n<uint32_t>((size_t)nb * Tn);
+        int32_t* d_cnt = ws.alloc_n<int32_t>(nb);
+        {
+            StageScope sc(e.tm(), ST_CTC, st, 2);
+            k::argmax_rows(d_logp, (int64_t)Tn * nb, C, d_excl, d_labels, st);
+            k::ctc_collapse(d_labels, Tn, (int)nb, d_ol, d_op, d_cnt, st);  // recognition.rs:511
+        }
+        DecodedSteps dec;
+        download_steps(ws, st, nb, Tn, d_ol, d_op, d_cnt, nullptr, nullptr, &dec);
+        ws.sync();
+        for (size_t j = 0; j < nb; j++) {
+            RecResult& r = res[ch.members[j]];
+            take_steps(dec, j, (uint32_t)Tn, &r);
+            if (scored)   // the model output is on the host already: line j's row t is hout[(t * nb + j) * C]
+                score_line(&hout[j * C], Tn, C, nb * (size_t)C, e.has_excluded ? e.excluded.data() : nullptr, r.steps, nullptr,
+                           &r.step_logp, &r.line_score);
+        }
+    }
+}
+
+// ---- fixed-graph HIP executor: all width groups in ONE ragged batch.  Each line keeps the
+// padded width (hence sequence length) the reference gives it (recognition.rs:437), lines are
+// sorted by length so that step t of the recurrence works on a dense prefix of rows.
+struct Slot { int T; size_t line; };
+struct Sub {   // one ragged batch of a request: what its launches leave for the host
+    std::vector<Slot> slots;
+    DecodedSteps dec;              // greedy, or beam search done on the GPU
+    uint32_t gru_status[8] = {0};  // time-out words of the persistent GRU kernels (0 = fine)
+    bool gpu_beam = false;         // beam search already done on the GPU: dec holds its steps
+    std::vector<float> logp;       // beam search on the host / logits wanted: packed [R][C]
+    std::vector<int32_t> off;      // with logp
+};
+struct PackedRequest {   // what the sub-batches of one request share
+    const ocrs_engine& e;
+    const HipModel* hm;
+    const std::vector<Chunk>& chunks;
+    std::vector<int> chunk_T;   // each chunk's sequence length
+    int C;                      // classes
+    bool scored, want_logp;
+    RecResult* res;
+};
+
+// launches chunks [c0, c1) as one ragged batch on `w` and queues the downloads of what unpack_packed needs
+void launch_packed(const PackedRequest& rq, size_t c0, size_t c1, Workspace& w, Sub& sub) {
+    const ocrs_engine& e = rq.e;
+    const bool beam = e.decode_method == OCRS_DECODE_BEAM_SEARCH;
+    const uint8_t* d_excl = e.has_excluded ? e.d_excluded.as<uint8_t>() : nullptr;
+    StageTimers* T = e.tm();
+    const int C = rq.C;
+    hipStream_t sst = w.s();
+    std::vector<int32_t> lineT;                      // the lines of chunks c0 .. c1 in chunk order
+    std::vector<size_t> line_of;                     // and which line of the request each is
+    std::vector<size_t> pos_at(c1 - c0);             // index of each chunk's first line
+    for (size_t c = c0; c < c1; c++) {
+        pos_at[c - c0] = lineT.size();
+        for (size_t li : rq.chunks[c].members) {
+            lineT.push_back(rq.chunk_T[c]);
+            line_of.push_back(li);
+        }
+    }
+    HipModel::PackedPlan plan;
+    plan.h_status = sub.gru_status;
+    std::vector<size_t> order;
+    const int32_t* d_pos = HipModel::make_packed_plan(w, lineT, &plan, &order);
+    if (!d_pos) return;
+    for (size_t i : order) sub.slots.push_back(Slot{lineT[i], line_of[i]});
+    const int M = plan.M, Tmax = plan.Tmax;
+    std::vector<HipModel::PackedGroup> pg;
+    for (size_t c = c0; c < c1; c++)
+        if (rq.chunk_T[c] > 0)
+            pg.push_back(HipModel::PackedGroup{rq.chunks[c].ptr, (int)rq.chunks[c].members.size(), (int)rq.chunks[c].gw,
+                                               d_pos + pos_at[c - c0]});
+    int32_t* d_labels = w.alloc_n<int32_t>((size_t)plan.R);
+    float* d_logp = nullptr;
+    float* d_maxlp = (rq.scored && !beam) ? w.alloc_n<float>((size_t)plan.R) : nullptr;
+    rq.hm->run_recognition_packed(w, pg, plan, (int)e.rec_input_height(), T, d_excl, d_labels, (beam || rq.want_logp) ? &d_logp : nullptr,
+                                  d_maxlp);
+    sub.gpu_beam = beam && option(OPT_BEAM_GPU) && k::ctc_beam_supported(C, (int)e.beam_width);
+    if (rq.want_logp || (beam && !sub.gpu_beam)) {   // the host needs the log-probs: the caller, or its beam search
+        sub.logp.resize((size_t)plan.R * C);
+        sub.off = plan.h_off;
+        w.download(sub.logp.data(), d_logp, sub.logp.size() * sizeof(float), sst);
+    }
+    if (beam && !sub.gpu_beam) return;
+    // where the steps land: [M][Tmax] labels and positions, [M] counts; scored: step log-probs and line scores as well
+    int2* d_nodes = nullptr;
+    int2* d_posn = nullptr;
+    if (sub.gpu_beam) {
+        const size_t arena = k::ctc_beam_arena_entries(Tmax, (int)e.beam_width);
+        d_nodes = w.alloc_n<int2>((size_t)M * arena);
+        d_posn = w.alloc_n<int2>((size_t)M * arena);
+    }
+    uint32_t* d_ol = w.alloc_n<uint32_t>((size_t)M * Tmax);
+    uint32_t* d_op = w.alloc_n<uint32_t>((size_t)M * Tmax);
+    int32_t* d_cnt = w.alloc_n<int32_t>(M);
+    float* d_slp = rq.scored ? w.alloc_n<float>((size_t)M * Tmax) : nullptr;
+    double* d_score = rq.scored ? w.alloc_n<double>(M) : nullptr;
+    {
+        StageScope sc(T, ST_CTC, sst);
+        if (sub.gpu_beam)   // rten decode_beam (recognition.rs:512-514) on the GPU, one workgroup per line (kernels_beam.hip)
+            k::ctc_beam_packed(d_logp, plan.d_Tm, plan.d_off, M, Tmax, C, (int)e.beam_width, d_excl, d_nodes, d_posn, d_ol, d_op, d_cnt,
+                               sst, d_score, d_slp);
+        else if (rq.scored)   // greedy CTC with each step's log-prob and the greedy path's score, in one pass
+            k::ctc_collapse_scored_packed(d_labels, d_maxlp, plan.d_Tm, plan.d_off, M, Tmax, d_ol, d_op, d_slp, d_cnt, d_score, sst);
+        else   // greedy CTC (recognition.rs:511)
+            k::ctc_collapse_packed(d_labels, plan.d_Tm, plan.d_off, M, Tmax, d_ol, d_op, d_cnt, sst);
+    }
+    download_steps(w, sst, (size_t)M, Tmax, d_ol, d_op, d_cnt, d_slp, d_score, &sub.dec);
+}
+
+// after the sync: the request's results from what launch_packed downloaded
+void unpack_packed(const PackedRequest& rq, const Sub& sub) {
+    const ocrs_engine& e = rq.e;
+    const int C = rq.C;
+    const size_t M = sub.slots.size();
+    for (uint32_t st8 : sub.gru_status)
+        if (st8) fail(OCRS_ERR_DEVICE, "GRU recurrence kernel timed out waiting for a peer workgroup (status 0x%x)", st8);
+    auto row = [&](size_t m, int t) { return &sub.logp[((size_t)sub.off[t] + m) * C]; };
+    if (rq.want_logp)
+        for (size_t m = 0; m < M; m++) {
+            auto& dst = rq.res[sub.slots[m].line].logp;
+            dst.resize((size_t)sub.slots[m].T * C);
+            for (int t = 0; t < sub.slots[m].T; t++) memcpy(&dst[(size_t)t * C], row(m, t), (size_t)C * sizeof(float));
+        }
+    if (e.decode_method == OCRS_DECODE_BEAM_SEARCH && !sub.gpu_beam) {  // host side, one thread per slice of lines
+        const unsigned nth = (unsigned)std::max<size_t>(1, std::min<size_t>({(size_t)std::thread::hardware_concurrency(), (size_t)32, M}));
+        std::vector<std::thread> th;
+        for (unsigned w0 = 0; w0 < nth; w0++)
+            th.emplace_back([&, w0] {
+                std::vector<float> seq;
+                for (size_t m = w0; m < M; m += nth)
+                    beam_decode_line(e, sub.slots[m].T, C, [&](int t) { return row(m, t); }, seq, rq.scored, &rq.res[sub.slots[m].line]);
+            });
+        for (auto& t : th) t.join();
+        return;
+    }
+    for (size_t m = 0; m < M; m++) take_steps(sub.dec, m, (uint32_t)sub.slots[m].T, &rq.res[sub.slots[m].line]);
+}
+
+void recognize_packed(const ocrs_engine& e, Workspace& ws, const std::vector<Chunk>& chunks, RecResult* res, bool scored, bool want_logp) {
+    const auto* hm = static_cast<const HipModel*>(e.recognition);
+    PackedRequest rq{e, hm, chunks, std::vector<int>(chunks.size()), 0, scored, want_logp, res};
+    int ndim = hm->packed_split() < 0 ? 4 : 3;
+    for (size_t c = 0; c < chunks.size() && ndim == 3; c++) {
+        TensorShape os = hm->infer(1, (int)e.rec_input_height(), (int)chunks[c].gw);
+        if (!os.seq) ndim = 4;
+        rq.chunk_T[c] = os.n;
+        rq.C = os.c;
+    }
+    check_rec_output(ndim, 0, 0, rq.C, e.alphabet.size());
+    // Two ragged batches when the request mixes long and short lines: the recurrence is a chain
+    // of up to 600 dependent, latency-bound steps whose tail only involves the few longest lines.
+    // The long groups run first on a high-priority stream; their recurrence then overlaps the
+    // conv stack of the short groups (the bulk of the FLOPs) on this call's main stream.
+    const int T_SPLIT = 160;
+    size_t first_long = chunks.size();
+    for (size_t c = 0; c < chunks.size(); c++)
+        if (rq.chunk_T[c] > T_SPLIT) { first_long = c; break; }
+    size_t n_long_lines = 0, n_short_lines = 0;
+    for (size_t c = 0; c < chunks.size(); c++) (c >= first_long ? n_long_lines : n_short_lines) += chunks[c].members.size();
+    const bool split = n_long_lines > 0 && n_short_lines >= 64;
+    Workspace ws_long(true);  // high-priority stream (idle if unused)
+    Sub sub_long, sub_short;
+    if (split) {
+        {   // the crops were produced on ws's stream: the long lines' stream starts after them
+            hipEvent_t crops = ws.make_event();
+            OCRS_HIP(hipEventRecord(crops, ws.s()));
+            OCRS_HIP(hipStreamWaitEvent(ws_long.s(), crops, 0));
+        }
+        launch_packed(rq, first_long, chunks.size(), ws_long, sub_long);
+        launch_packed(rq, 0, first_long, ws, sub_short);
+        ws_long.sync();
+        ws.sync();
+        unpack_packed(rq, sub_long);
+        unpack_packed(rq, sub_short);
+    } else {
+        launch_packed(rq, 0, chunks.size(), ws, sub_short);
+        ws.sync();
+        unpack_packed(rq, sub_short);
+    }
+}
+
+}  // namespace
+
+void ocrs_engine::recognize_lines(const ocrs_page* const* pages, size_t n_pages, RecResult* res, size_t L, bool scored,
+                                  bool want_logp) const {
     if (L == 0) return;
+    const uint32_t rec_h = rec_input_height();
+    const bool callback = recognition->is_callback();
 
     // group by padded width (recognition.rs:430-446); std::map gives a deterministic order
     std::map<uint32_t, std::vector<size_t>> groups;
-    for (size_t i = 0; i < L; i++) groups[lines[i].group_width].push_back(i);
+    for (size_t i = 0; i < L; i++) groups[res[i].line.group_width].push_back(i);
 
     Workspace ws;
-    hipStream_t st = ws.s();
-    StageTimers* T = tm();
-
-    std::vector<const float*> hp(n_pages);
-    std::vector<int32_t> hhw(2 * n_pages);
-    for (size_t i = 0; i < n_pages; i++) {
-        hp[i] = pages[i]->grey.as<float>();
-        hhw[2 * i] = pages[i]->h;
-        hhw[2 * i + 1] = pages[i]->w;
-    }
-    const float** d_pages = ws.alloc_n<const float*>(n_pages);
-    int32_t* d_hw = ws.alloc_n<int32_t>(2 * n_pages);
-    ws.upload(d_pages, hp.data(), n_pages * sizeof(float*));
-    ws.upload(d_hw, hhw.data(), hhw.size() * sizeof(int32_t));
-
-    const bool callback = recognition->is_callback();
-    const uint8_t* d_excl = has_excluded ? d_excluded.as<uint8_t>() : nullptr;
-
-    // ---- crop + resize + pad every line into its width group's batch (recognition.rs:135-158),
-    // one launch for all lines of all groups
-    struct Chunk { uint32_t gw; std::vector<size_t> members; int64_t off; float* ptr = nullptr; };
     std::vector<Chunk> chunks;
-    {
-        int64_t off = 0;
-        for (auto& kv : groups) {
-            const uint32_t gw = kv.first;
-            if (gw == 0) continue;  // zero-width lines produce no input and no text
-            // reference: chunks of 20 (recognition.rs:450); rows are independent, so the HIP
-            // executor takes bigger chunks, bounded by activation memory (~8 KB per input pixel column).
-            const size_t max_chunk = callback ? 20 : std::max<size_t>(1, 2457600 / gw);
-            for (size_t c0 = 0; c0 < kv.second.size(); c0 += max_chunk) {
-                Chunk ch;
-                ch.gw = gw;
-                ch.members.assign(kv.second.begin() + c0, kv.second.begin() + std::min(kv.second.size(), c0 + max_chunk));
-                ch.off = off;
-                off += (int64_t)ch.members.size() * rec_h * gw;
-                chunks.push_back(std::move(ch));
+    std::vector<CropLine> crops;
+    int64_t off = 0;
+    for (auto& kv : groups) {
+        const uint32_t gw = kv.first;
+        if (gw == 0) continue;  // zero-width lines produce no input and no text
+        // reference: chunks of 20 (recognition.rs:450); rows are independent, so the HIP
+        // executor takes bigger chunks, bounded by activation memory (~8 KB per input pixel column).
+        const size_t max_chunk = callback ? 20 : std::max<size_t>(1, 2457600 / gw);
+        for (size_t c0 = 0; c0 < kv.second.size(); c0 += max_chunk) {
+            Chunk ch;
+            ch.gw = gw;
+            ch.members.assign(kv.second.begin() + c0, kv.second.begin() + std::min(kv.second.size(), c0 + max_chunk));
+            ch.off = off;
+            for (size_t li : ch.members) {
+                crops.push_back(CropLine{&res[li].line, gw, off});
+                off += (int64_t)rec_h * gw;
             }
+            chunks.push_back(std::move(ch));
         }
-        // (ocrs_engine::recognize keeps a request within the activation budget; a single line beyond it is refused)
-        if ((double)off > std::max(rec_pixel_budget(), 2.0e9))
-            fail(OCRS_ERR_CAPACITY, "text line too large for the recognition model (%lld input pixels)", (long long)off);
-        std::vector<k::LineDesc> descs;
-        std::vector<int32_t> poly;
-        std::vector<k::RectLineDesc> rdescs;   // the rectified lines: a launch of their own into the same tensor
-        std::vector<int32_t> ranges;
-        int rect_max_w = 0;
-        for (const Chunk& ch : chunks)
-            for (size_t j = 0; j < ch.members.size(); j++) {
-                const RecLine& ln = lines[ch.members[j]];
-                if (ln.rectified) {
-                    k::RectLineDesc d{};
-                    d.page = (int32_t)ln.page;
-                    d.mode = ln.frame.empty ? 1 : 0;
-                    d.range_off = (int32_t)(ranges.size() / 4);
-                    d.range_n = ln.frame.empty ? 0 : (int32_t)(ln.frame.ranges.size() / 4);
-                    d.resized_w = (int32_t)ln.resized_width;
-                    d.out_w = (int32_t)ch.gw;
-                    d.out_off = ch.off + (int64_t)j * rec_h * ch.gw;
-                    d.x0 = ln.frame.coef[0]; d.ax = ln.frame.coef[1]; d.bx = ln.frame.coef[2];
-                    d.y0 = ln.frame.coef[3]; d.ay = ln.frame.coef[4]; d.by = ln.frame.coef[5];
-                    rdescs.push_back(d);
-                    if (!ln.frame.empty) ranges.insert(ranges.end(), ln.frame.ranges.begin(), ln.frame.ranges.end());
-                    rect_max_w = std::max(rect_max_w, (int)ch.gw);
-                    continue;
-                }
-                k::LineDesc d{};
-                d.page = (int32_t)ln.page;
-                d.poly_off = (int32_t)(poly.size() / 2);
-                d.poly_n = (int32_t)ln.polygon.size();
-                d.top = ln.bounds.top; d.left = ln.bounds.left;
-                d.bh = ln.bounds.height(); d.bw = ln.bounds.width();
-                d.resized_w = (int32_t)ln.resized_width;
-                d.out_w = (int32_t)ch.gw;
-                d.out_off = ch.off + (int64_t)j * rec_h * ch.gw;
-                descs.push_back(d);
-                for (const PointI& p : ln.polygon) { poly.push_back(p.y); poly.push_back(p.x); }
-            }
-        if (descs.empty() && rdescs.empty()) return;
-        k::LineDesc* d_descs = descs.empty() ? nullptr : ws.alloc_n<k::LineDesc>(descs.size());
-        int32_t* d_poly = descs.empty() ? nullptr : ws.alloc_n<int32_t>(poly.size());
-        // host temporaries travel through the workspace's pinned staging: real asynchronous copies, no host wait here
-        if (!descs.empty()) {
-            ws.upload(d_descs, descs.data(), descs.size() * sizeof(k::LineDesc));
-            ws.upload(d_poly, poly.data(), poly.size() * sizeof(int32_t));
-        }
-        k::RectLineDesc* d_rdescs = nullptr;
-        int32_t* d_ranges = nullptr;
-        if (!rdescs.empty()) {
-            d_rdescs = ws.alloc_n<k::RectLineDesc>(rdescs.size());
-            d_ranges = ws.alloc_n<int32_t>(std::max<size_t>(ranges.size(), 4));
-            ws.upload(d_rdescs, rdescs.data(), rdescs.size() * sizeof(k::RectLineDesc));
-            if (!ranges.empty()) ws.upload(d_ranges, ranges.data(), ranges.size() * sizeof(int32_t));
-        }
-        float* d_all = ws.alloc_n<float>((size_t)off);
-        {
-            StageScope sc(T, ST_LINE_CROP, st, (descs.empty() ? 0 : 1) + (rdescs.empty() ? 0 : 1));
-            k::crop_lines(d_pages, d_hw, d_descs, d_poly, (int)descs.size(), (int)rec_h, d_all, st);
-            k::rectify_lines(d_pages, d_hw, d_rdescs, d_ranges, (int)rdescs.size(), rect_max_w, (int)rec_h, d_all, st);
-        }
-        if (callback) ws.sync();   // the callback path reads the crops back right away
-        for (Chunk& ch : chunks) ch.ptr = d_all + ch.off;
     }
-    auto chunk_ptr = [](const Chunk& ch) { return ch.ptr; };
-
+    // (ocrs_engine::recognize_now keeps a request within the activation budget; a single line beyond it is refused)
+    if ((double)off > std::max(rec_pixel_budget(), 2.0e9))
+        fail(OCRS_ERR_CAPACITY, "text line too large for the recognition model (%lld input pixels)", (long long)off);
+    float* d_all = stage_line_crops(ws, tm(), pages, n_pages, crops, (int)rec_h, off);
+    if (!d_all) return;
+    for (Chunk& ch : chunks) ch.ptr = d_all + ch.off;
     if (callback) {
-        // ---- `trait Model` implemented by the caller: one run per <=20-line chunk (recognition.rs:485)
-        const auto* cb = static_cast<const CallbackModel*>(recognition);
-        for (const Chunk& ch : chunks) {
-            const size_t nb = ch.members.size();
-            const uint32_t gw = ch.gw;
-            std::vector<float> hin(nb * rec_h * gw), hout;
-            ws.download(hin.data(), chunk_ptr(ch), hin.size() * sizeof(float));
-            ws.sync();
-            const int64_t ishape[4] = {(int64_t)nb, 1, rec_h, gw};
-            int64_t oshape[4];
-            int ond = 0;
-            cb->run(hin.data(), ishape, hout, oshape, &ond);
-            if (ond != 3)
-                fail(OCRS_ERR_WRONG_OUTPUT,
-                     "model output had unexpected type or shape: expected recognition output to have 3 dims but it has %d", ond);
-            if ((size_t)oshape[1] != nb)
-                fail(OCRS_ERR_WRONG_OUTPUT, "model output had unexpected type or shape: batch size %lld != %zu",
-                     (long long)oshape[1], nb);
-            const int Tn = (int)oshape[0], C = (int)oshape[2];
-            if (alphabet_len + 1 != (size_t)C)
-                fail(OCRS_ERR_WRONG_OUTPUT,
-                     "model output had unexpected type or shape: output column count (%d) does not match alphabet size (%zu)",
-                     C, alphabet_len + 1);
-            if (beam) {  // decode_beam on the model output, masked as recognition.rs:547-561 does
-                std::vector<float> seq((size_t)Tn * C);
-                for (size_t j = 0; j < nb; j++) {
-                    for (int t = 0; t < Tn; t++)
-                        for (int c = 0; c < C; c++) {
-                            float v = hout[((size_t)t * nb + j) * C + c];
-                            if (has_excluded && excluded[c]) v = -std::numeric_limits<float>::infinity();
-                            seq[(size_t)t * C + c] = v;
-                        }
-                    const size_t li = ch.members[j];
-                    double bs = 0.0;
-                    (*steps_out)[li] = ctc_beam_search(seq.data(), Tn, C, C, beam_width, scores ? &bs : nullptr);
-                    (*ctc_len_out)[li] = (uint32_t)Tn;
-                    if (scores)
-                        score_line(seq.data(), Tn, C, C, nullptr, (*steps_out)[li], &bs, &scores->step_logp[li],
-                                   &scores->line_score[li]);
-                }
-                continue;
-            }
-            float* d_logp = ws.alloc_n<float>(hout.size());
-            OCRS_HIP(hipMemcpyAsync(d_logp, hout.data(), hout.size() * sizeof(float), hipMemcpyHostToDevice, st));
-            int32_t* d_labels = ws.alloc_n<int32_t>((size_t)Tn * nb);
-            uint32_t* d_ol = ws.alloc_n<uint32_t>((size_t)nb * Tn);
-            uint32_t* d_op = ws.alloc_n<uint32_t>((size_t)nb * Tn);
-            int32_t* d_cnt = ws.alloc_n<int32_t>(nb);
-            {
-                StageScope sc(T, ST_CTC, st, 2);
-                k::argmax_rows(d_logp, (int64_t)Tn * nb, C, d_excl, d_labels, st);
-                k::ctc_collapse(d_labels, Tn, (int)nb, d_ol, d_op, d_cnt, st);  // recognition.rs:511
-            }
-            std::vector<uint32_t> hl((size_t)nb * Tn), hpz((size_t)nb * Tn);
-            std::vector<int32_t> hc(nb);
-            ws.download(hl.data(), d_ol, hl.size() * 4);
-            ws.download(hpz.data(), d_op, hpz.size() * 4);
-            ws.download(hc.data(), d_cnt, nb * 4);
-            ws.sync();
-            for (size_t j = 0; j < nb; j++) {
-                const size_t li = ch.members[j];
-                auto& sv = (*steps_out)[li];
-                sv.resize(hc[j]);
-                for (int q = 0; q < hc[j]; q++) sv[q] = CtcStep{hl[j * Tn + q], hpz[j * Tn + q]};
-                (*ctc_len_out)[li] = (uint32_t)Tn;
-                if (scores)   // the model output is on the host already: line j's row t is hout[(t * nb + j) * C]
-                    score_line(&hout[j * C], Tn, C, nb * (size_t)C, has_excluded ? excluded.data() : nullptr, sv, nullptr,
-                               &scores->step_logp[li], &scores->line_score[li]);
-            }
-        }
+        ws.sync();   // the callback path reads the crops back right away
+        recognize_callback(*this, ws, chunks, res, scored);
     } else {
-        // ---- fixed-graph HIP executor: all width groups in ONE ragged batch.  Each line keeps the
-        // padded width (hence sequence length) the reference gives it (recognition.rs:437), lines are
-        // sorted by length so that step t of the recurrence works on a dense prefix of rows.
-        const auto* hm = static_cast<const HipModel*>(recognition);
-        if (hm->packed_split() < 0)
-            fail(OCRS_ERR_WRONG_OUTPUT,
-                 "model output had unexpected type or shape: expected recognition output to have 3 dims but it has 4");
-        std::vector<int> chunk_T(chunks.size());
-        int C = 0;
-        for (size_t c = 0; c < chunks.size(); c++) {
-            TensorShape os = hm->infer(1, (int)rec_h, (int)chunks[c].gw);
-            if (!os.seq)
-                fail(OCRS_ERR_WRONG_OUTPUT,
-                     "model output had unexpected type or shape: expected recognition output to have 3 dims but it has 4");
-            chunk_T[c] = os.n;
-            C = os.c;
-        }
-        if (alphabet_len + 1 != (size_t)C)  // recognition.rs:487-493
-            fail(OCRS_ERR_WRONG_OUTPUT,
-                 "model output had unexpected type or shape: output column count (%d) does not match alphabet size (%zu)", C,
-                 alphabet_len + 1);
-        // Two ragged batches when the request mixes long and short lines: the recurrence is a chain
-        // of up to 600 dependent, latency-bound steps whose tail only involves the few longest lines.
-        // The long groups run first on a high-priority stream; their recurrence then overlaps the
-        // conv stack of the short groups (the bulk of the FLOPs) on this call's main stream.
-        struct Slot { int T; size_t line; size_t chunk, j; };
-        struct Sub {
-            std::vector<Slot> slots;
-            std::vector<uint32_t> hl, hp;
-            std::vector<int32_t> hc;
-            std::vector<float> hlp;        // scored, on the GPU: [M][Tmax] step log-probs
-            std::vector<double> hscore;    // scored, on the GPU: [M] line scores
-            int Tmax = 0;
-            uint32_t gru_status[8] = {0};  // time-out words of the persistent GRU kernels (0 = fine)
-            bool gpu_beam = false;         // beam search already done on the GPU: hl/hp/hc hold its steps
-            std::vector<float> logp;      // beam search on the host / logits wanted: packed [R][C]
-            std::vector<int32_t> off;     // with logp
-        };
-        const int T_SPLIT = 160;
-        size_t first_long = chunks.size();
-        for (size_t c = 0; c < chunks.size(); c++)
-            if (chunk_T[c] > T_SPLIT) { first_long = c; break; }
-        size_t n_long_lines = 0, n_short_lines = 0;
-        for (size_t c = 0; c < chunks.size(); c++) (c >= first_long ? n_long_lines : n_short_lines) += chunks[c].members.size();
-        const bool split = n_long_lines > 0 && n_short_lines >= 64;
-        Workspace ws_long(true);  // high-priority stream (idle if unused)
-
-        auto launch = [&](size_t c0, size_t c1, Workspace& w, Sub& sub) {
-            hipStream_t sst = w.s();
-            std::vector<int32_t> lineT;                      // the lines of chunks c0 .. c1 in chunk order
-            std::vector<std::pair<size_t, size_t>> at;       // (chunk, member)
-            std::vector<size_t> pos_at(c1 - c0);             // index of each chunk's first line
-            for (size_t c = c0; c < c1; c++) {
-                pos_at[c - c0] = lineT.size();
-                for (size_t j = 0; j < chunks[c].members.size(); j++) {
-                    lineT.push_back(chunk_T[c]);
-                    at.emplace_back(c, j);
-                }
-            }
-            HipModel::PackedPlan plan;
-            plan.h_status = sub.gru_status;
-            std::vector<size_t> order;
-            const int32_t* d_pos = HipModel::make_packed_plan(w, lineT, &plan, &order);
-            if (!d_pos) return;
-            for (size_t i : order)
-                sub.slots.push_back(Slot{lineT[i], chunks[at[i].first].members[at[i].second], at[i].first, at[i].second});
-            const int M = plan.M;
-            std::vector<HipModel::PackedGroup> pg;
-            for (size_t c = c0; c < c1; c++)
-                if (chunk_T[c] > 0)
-                    pg.push_back(HipModel::PackedGroup{chunk_ptr(chunks[c]), (int)chunks[c].members.size(), (int)chunks[c].gw,
-                                                       d_pos + pos_at[c - c0]});
-            int32_t* d_labels = w.alloc_n<int32_t>((size_t)plan.R);
-            float* d_logp = nullptr;
-            float* d_maxlp = (scores && !beam) ? w.alloc_n<float>((size_t)plan.R) : nullptr;
-            hm->run_recognition_packed(w, pg, plan, (int)rec_h, T, d_excl, d_labels, (beam || logp_out) ? &d_logp : nullptr,
-                                       d_maxlp);
-            if (logp_out) {
-                sub.logp.resize((size_t)plan.R * C);
-                sub.off = plan.h_off;
-                w.download(sub.logp.data(), d_logp, sub.logp.size() * sizeof(float), sst);
-            }
-            if (beam && option(OPT_BEAM_GPU) && k::ctc_beam_supported(C, (int)beam_width)) {
-                // rten decode_beam (recognition.rs:512-514) on the GPU, one workgroup per line (kernels_beam.hip)
-                const int Tmax = plan.Tmax;
-                sub.Tmax = Tmax;
-                sub.gpu_beam = true;
-                const size_t arena = k::ctc_beam_arena_entries(Tmax, (int)beam_width);
-                int2* d_nodes = w.alloc_n<int2>((size_t)M * arena);
-                int2* d_posn = w.alloc_n<int2>((size_t)M * arena);
-                uint32_t* d_ol = w.alloc_n<uint32_t>((size_t)M * Tmax);
-                uint32_t* d_op = w.alloc_n<uint32_t>((size_t)M * Tmax);
-                int32_t* d_cnt = w.alloc_n<int32_t>(M);
-                double* d_score = scores ? w.alloc_n<double>(M) : nullptr;
-                float* d_slp = scores ? w.alloc_n<float>((size_t)M * Tmax) : nullptr;
-                {
-                    StageScope sc(T, ST_CTC, sst);
-                    k::ctc_beam_packed(d_logp, plan.d_Tm, plan.d_off, M, Tmax, C, (int)beam_width, d_excl, d_nodes, d_posn, d_ol,
-                                       d_op, d_cnt, sst, d_score, d_slp);
-                }
-                sub.hl.resize((size_t)M * Tmax);
-                sub.hp.resize((size_t)M * Tmax);
-                sub.hc.resize(M);
-                w.download(sub.hl.data(), d_ol, sub.hl.size() * 4, sst);
-                w.download(sub.hp.data(), d_op, sub.hp.size() * 4, sst);
-                w.download(sub.hc.data(), d_cnt, (size_t)M * 4, sst);
-                if (scores) {
-                    sub.hlp.resize((size_t)M * Tmax);
-                    sub.hscore.resize(M);
-                    w.download(sub.hlp.data(), d_slp, sub.hlp.size() * sizeof(float), sst);
-                    w.download(sub.hscore.data(), d_score, (size_t)M * sizeof(double), sst);
-                }
-                return;
-            }
-            if (beam) {
-                sub.Tmax = plan.Tmax;
-                if (!logp_out) {
-                    sub.logp.resize((size_t)plan.R * C);
-                    sub.off = plan.h_off;
-                    w.download(sub.logp.data(), d_logp, sub.logp.size() * sizeof(float), sst);
-                }
-                return;
-            }
-            // greedy CTC (recognition.rs:511)
-            const int Tmax = plan.Tmax;
-            sub.Tmax = Tmax;
-            uint32_t* d_ol = w.alloc_n<uint32_t>((size_t)M * Tmax);
-            uint32_t* d_op = w.alloc_n<uint32_t>((size_t)M * Tmax);
-            int32_t* d_cnt = w.alloc_n<int32_t>(M);
-            if (scores) {   // the same collapse, with each step's log-prob and the greedy path's score, in one pass
-                float* d_slp = w.alloc_n<float>((size_t)M * Tmax);
-                double* d_score = w.alloc_n<double>(M);
-                {
-                    StageScope sc(T, ST_CTC, sst);
-                    k::ctc_collapse_scored_packed(d_labels, d_maxlp, plan.d_Tm, plan.d_off, M, Tmax, d_ol, d_op, d_slp, d_cnt,
-                                                  d_score, sst);
-                }
-                sub.hlp.resize((size_t)M * Tmax);
-                sub.hscore.resize(M);
-                w.download(sub.hlp.data(), d_slp, sub.hlp.size() * sizeof(float), sst);
-                w.download(sub.hscore.data(), d_score, (size_t)M * sizeof(double), sst);
-            } else {
-                StageScope sc(T, ST_CTC, sst);
-                k::ctc_collapse_packed(d_labels, plan.d_Tm, plan.d_off, M, Tmax, d_ol, d_op, d_cnt, sst);
-            }
-            sub.hl.resize((size_t)M * Tmax);
-            sub.hp.resize((size_t)M * Tmax);
-            sub.hc.resize(M);
-            w.download(sub.hl.data(), d_ol, sub.hl.size() * 4, sst);
-            w.download(sub.hp.data(), d_op, sub.hp.size() * 4, sst);
-            w.download(sub.hc.data(), d_cnt, (size_t)M * 4, sst);
-        };
-        auto unpack = [&](const Sub& sub) {
-            for (uint32_t st8 : sub.gru_status)
-                if (st8) fail(OCRS_ERR_DEVICE, "GRU recurrence kernel timed out waiting for a peer workgroup (status 0x%x)", st8);
-            if (logp_out)
-                for (size_t m = 0; m < sub.slots.size(); m++) {
-                    auto& dst = (*logp_out)[sub.slots[m].line];
-                    dst.resize((size_t)sub.slots[m].T * C);
-                    for (int t = 0; t < sub.slots[m].T; t++)
-                        memcpy(&dst[(size_t)t * C], &sub.logp[((size_t)sub.off[t] + m) * C], (size_t)C * sizeof(float));
-                }
-            if (beam && !sub.gpu_beam) {  // rten decode_beam (recognition.rs:512-514), host side, one thread per slice of lines
-                const size_t M = sub.slots.size();
-                const unsigned nth = (unsigned)std::max<size_t>(1, std::min<size_t>({(size_t)std::thread::hardware_concurrency(), (size_t)32, M}));
-                std::vector<std::thread> th;
-                for (unsigned w0 = 0; w0 < nth; w0++)
-                    th.emplace_back([&, w0] {
-                        std::vector<float> seq;
-                        for (size_t m = w0; m < M; m += nth) {
-                            const int Tm = sub.slots[m].T;
-                            seq.resize((size_t)Tm * C);
-                            for (int t = 0; t < Tm; t++) {
-                                const float* src = &sub.logp[((size_t)sub.off[t] + m) * C];
-                                for (int c = 0; c < C; c++)
-                                    seq[(size_t)t * C + c] = (has_excluded && excluded[c]) ? -std::numeric_limits<float>::infinity() : src[c];
-                            }
-                            const size_t li = sub.slots[m].line;
-                            double bs = 0.0;
-                            (*steps_out)[li] = ctc_beam_search(seq.data(), Tm, C, C, beam_width, scores ? &bs : nullptr);
-                            (*ctc_len_out)[li] = (uint32_t)Tm;
-                            if (scores)
-                                score_line(seq.data(), Tm, C, C, nullptr, (*steps_out)[li], &bs, &scores->step_logp[li],
-                                           &scores->line_score[li]);
-                        }
-                    });
-                for (auto& t : th) t.join();
-                return;
-            }
-            for (size_t m = 0; m < sub.slots.size(); m++) {
-                const size_t li = sub.slots[m].line;
-                auto& sv = (*steps_out)[li];
-                sv.resize(sub.hc[m]);
-                for (int q = 0; q < sub.hc[m]; q++)
-                    sv[q] = CtcStep{sub.hl[m * sub.Tmax + q], sub.hp[m * sub.Tmax + q]};
-                (*ctc_len_out)[li] = (uint32_t)sub.slots[m].T;
-                if (scores) {
-                    const float* lp = &sub.hlp[m * sub.Tmax];
-                    scores->step_logp[li].assign(lp, lp + sub.hc[m]);
-                    scores->line_score[li] = sub.hscore[m];
-                }
-            }
-        };
-        Sub sub_long, sub_short;
-        if (split) {
-            {   // the crops were produced on `st`: the long lines' stream starts after them
-                hipEvent_t crops = ws.make_event();
-                OCRS_HIP(hipEventRecord(crops, st));
-                OCRS_HIP(hipStreamWaitEvent(ws_long.s(), crops, 0));
-            }
-            launch(first_long, chunks.size(), ws_long, sub_long);
-            launch(0, first_long, ws, sub_short);
-            ws_long.sync();
-            ws.sync();
-            unpack(sub_long);
-            unpack(sub_short);
-        } else {
-            launch(0, chunks.size(), ws, sub_short);
-            ws.sync();
-            unpack(sub_short);
-        }
+        recognize_packed(*this, ws, chunks, res, scored, want_logp);
     }
-    if (T) T->collect();
+    if (StageTimers* T = tm()) T->collect();
 }
 
 // recognition.rs:241-311 for one line
-std::vector<TextChar> ocrs_engine::text_line_from_result(const RecLine& line, uint32_t ctc_input_len,
-                                                         const std::vector<CtcStep>& steps, const std::vector<float>* step_logp,
-                                                         std::vector<float>* char_logp) const {
+std::vector<TextChar> ocrs_engine::text_line_from_result(const RecResult& res, std::vector<float>* char_logp) const {
+    const RecLine& line = res.line;
+    const uint32_t ctc_input_len = res.ctc_len;
+    const std::vector<CtcStep>& steps = res.steps;
     std::vector<TextChar> out;
     if (char_logp) char_logp->clear();
     if (steps.empty() || ctc_input_len == 0) return out;
@@ -1368,7 +1344,7 @@ std::vector<TextChar> ocrs_engine::text_line_from_result(const RecLine& line, ui
         for (const auto& kv : rectified_char_boxes(line.frame, line.group_width, ctc_input_len, pos.data(), pos.size())) {
             const uint32_t idx = steps[kv.first].label - 1;
             out.push_back(TextChar{idx < alphabet.size() ? (uint32_t)alphabet[idx] : (uint32_t)'?', kv.second});
-            if (char_logp) char_logp->push_back((*step_logp)[kv.first]);
+            if (char_logp) char_logp->push_back(res.step_logp[kv.first]);
         }
         return out;
     }
@@ -1387,7 +1363,7 @@ std::vector<TextChar> ocrs_engine::text_line_from_result(const RecLine& line, ui
         if (!polygon_slice_bounding_rect(line.polygon, sx, ex, &r))
             fail(OCRS_ERR_RUN_FAILED, "invalid X coords");  // recognition.rs:299
         out.push_back(TextChar{ch, r});
-        if (char_logp) char_logp->push_back((*step_logp)[i]);   // padding steps are skipped with their chars
+        if (char_logp) char_logp->push_back(res.step_logp[i]);   // padding steps are skipped with their chars
     }
     return out;
 }

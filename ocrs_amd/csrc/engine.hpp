@@ -29,16 +29,9 @@ std::vector<CtcStep> ctc_beam_search(const float* logp, int T, int C, int row_st
 std::vector<CtcStep> ctc_beam_search_reference(const float* logp, int T, int C, int row_stride, uint32_t width,
                                                double* score = nullptr);
 
-// Recognition confidence (DESIGN.md "Recognition confidence"), per line and indexed like the steps: each step's
-// log-prob L[pos][label] and the line score (greedy: the float64 sum of the masked row maxima in ascending t; beam:
-// the best beam's lse(pb, pnb)).  A line without rows has no steps and score 0.
-struct RecScores {
-    std::vector<std::vector<float>> step_logp;
-    std::vector<double> line_score;
-};
-// The host form of the above for one line whose log-probs are on the host: row t at logp + t * row_stride, labels
-// flagged in `excluded` ([C] or null) read as -inf.  beam_score given: the line score is that value (beam search);
-// null: the greedy path's.  The GPU kernels compute the same bits (ctc_collapse_scored_packed, ctc_beam_packed).
+// The host form of recognition confidence (RecResult below) for one line whose log-probs are on the host: row t at
+// logp + t * row_stride, labels flagged in `excluded` ([C] or null) read as -inf.  beam_score given: the line score is that
+// value (beam search); null: the greedy path's.  The GPU kernels compute the same bits (ctc_collapse_scored_packed, ctc_beam_packed).
 void score_line(const float* logp, int T, int C, size_t row_stride, const uint8_t* excluded, const std::vector<CtcStep>& steps,
                 const double* beam_score, std::vector<float>* step_logp, double* line_score);
 
@@ -74,6 +67,32 @@ struct RecLine {  // TextRecLine (recognition.rs:80-89) + owning page
     LineFrame frame;
 };
 
+// One recognised line.  The optional fields are filled only when the request asks for them: nothing extra is launched or
+// allocated otherwise.
+struct RecResult {
+    RecLine line;
+    uint32_t ctc_len = 0;            // the model's sequence length for the line (ctc_input_len); 0: the line gave no input
+    std::vector<CtcStep> steps;
+    // Recognition confidence (DESIGN.md "Recognition confidence"), scored requests: each step's log-prob L[pos][label],
+    // indexed like the steps, and the line score (greedy: the float64 sum of the masked row maxima in ascending t; beam:
+    // the best beam's lse(pb, pnb)).  A line without rows has no steps and score 0.
+    std::vector<float> step_logp;
+    double line_score = 0.0;
+    // when asked: the model's log-probabilities [ctc_len][C] (TextRecognizer::run, recognition.rs:341-360), unmasked
+    std::vector<float> logp;
+};
+
+// One line to crop into a tensor of recognition inputs: rows of `out_w` floats, the first at float offset `out_off`.
+struct CropLine {
+    const RecLine* line;
+    uint32_t out_w;
+    int64_t out_off;
+};
+// Builds the crop descriptors of `crops`, uploads them through `ws` and launches the crops (plain and rectified lines: one
+// launch each) into a new tensor of `total` floats, which it returns; null when there is nothing to crop.
+float* stage_line_crops(Workspace& ws, StageTimers* timers, const ocrs_page* const* pages, size_t n_pages,
+                        const std::vector<CropLine>& crops, int rec_h, int64_t total);
+
 // Detection confidence, indexed [page][word] like the rects of the same call.
 struct DetScores {
     std::vector<std::vector<float>> score;      // mean text probability of the word's component, from the fixed-point sum
@@ -100,10 +119,8 @@ struct RecRequest : CoalescedBase {
     const ocrs_page* const* pages = nullptr;
     size_t n_pages = 0;
     const std::vector<std::vector<std::vector<geom::RotatedRect>>>* lines_per_page = nullptr;
-    std::vector<std::vector<CtcStep>>* steps = nullptr;
-    std::vector<RecLine>* rec_lines = nullptr;
-    std::vector<uint32_t>* ctc_len = nullptr;
-    RecScores* scores = nullptr;   // null: the caller did not ask for confidence
+    std::vector<RecResult>* results = nullptr;
+    bool scored = false;           // the caller asked for confidence
     bool rectify = false;          // this caller's lines are cropped along their own axes
 };
 
@@ -155,23 +172,19 @@ struct ocrs_engine {
     // rectify: the request's lines are cropped along their own axes; a merged batch may mix both kinds.
     void recognize(const ocrs_page* const* pages, size_t n_pages,
                    const std::vector<std::vector<std::vector<ocrs::geom::RotatedRect>>>& lines_per_page,
-                   std::vector<std::vector<ocrs::CtcStep>>* steps, std::vector<ocrs::RecLine>* rec_lines,
-                   std::vector<uint32_t>* ctc_input_len, ocrs::RecScores* scores = nullptr, bool rectify = false) const;
-    // rectify_pages (optional): one flag per page, the kind of that page's lines; null: all plain
+                   std::vector<ocrs::RecResult>* results, bool scored = false, bool rectify = false) const;
+    // want_logp: every line's model output too.  rectify_pages (optional): one flag per page, the kind of that page's
+    // lines; null: all plain.  Lines beyond the activation budget run as consecutive sub-requests.
     void recognize_now(const ocrs_page* const* pages, size_t n_pages,
                        const std::vector<std::vector<std::vector<ocrs::geom::RotatedRect>>>& lines_per_page,
-                       std::vector<std::vector<ocrs::CtcStep>>* steps, std::vector<ocrs::RecLine>* rec_lines,
-                       std::vector<uint32_t>* ctc_input_len, std::vector<std::vector<float>>* logp = nullptr,
-                       ocrs::RecScores* scores = nullptr, const std::vector<char>* rectify_pages = nullptr) const;
+                       std::vector<ocrs::RecResult>* results, bool scored = false, bool want_logp = false,
+                       const std::vector<char>* rectify_pages = nullptr) const;
     void init_coalescers();
     mutable std::unique_ptr<ocrs::Coalescer<ocrs::DetRequest>> det_queue;
     mutable std::unique_ptr<ocrs::Coalescer<ocrs::RecRequest>> rec_queue;
-    // one sub-request of `recognize` (within the activation budget); outputs indexed like `lines`
-    // logp (optional): per line the model's log-probabilities [T][C] (TextRecognizer::run, recognition.rs:341-360), unmasked
-    // scores (optional): per line the step log-probs and line score; null launches nothing extra
-    void recognize_lines(const ocrs_page* const* pages, size_t n_pages, const std::vector<ocrs::RecLine>& lines,
-                         std::vector<std::vector<ocrs::CtcStep>>* steps, std::vector<uint32_t>* ctc_input_len,
-                         std::vector<std::vector<float>>* logp = nullptr, ocrs::RecScores* scores = nullptr) const;
+    // one sub-request of `recognize_now` (within the activation budget): fills the `n` fresh results at `res`, whose `line`s are set
+    void recognize_lines(const ocrs_page* const* pages, size_t n_pages, ocrs::RecResult* res, size_t n, bool scored,
+                         bool want_logp) const;
     // the recognition model's output for the lines of one page, no coalescing (parity / tolerance checks); split into
     // sub-requests within the activation budget as `recognize` is
     void recognize_logits(const ocrs_page* page, const std::vector<std::vector<ocrs::geom::RotatedRect>>& lines,
@@ -183,11 +196,8 @@ struct ocrs_engine {
     void run_recognition_ops(const int32_t* widths, size_t n, int first_op, int last_op, bool gx_only, const float* in,
                              size_t in_len, std::vector<float>* out, std::vector<int32_t>* shapes) const;
 
-    // step_logp (optional, indexed like steps): char_logp receives the log-prob of every char's step, aligned with the result
-    std::vector<ocrs::TextChar> text_line_from_result(const ocrs::RecLine& line, uint32_t ctc_input_len,
-                                                      const std::vector<ocrs::CtcStep>& steps,
-                                                      const std::vector<float>* step_logp = nullptr,
-                                                      std::vector<float>* char_logp = nullptr) const;
+    // char_logp (optional, scored results): receives the log-prob of every char's step, aligned with the result
+    std::vector<ocrs::TextChar> text_line_from_result(const ocrs::RecResult& res, std::vector<float>* char_logp = nullptr) const;
 
     uint32_t rec_input_height() const;
     ocrs::RecLine make_rec_line(const std::vector<ocrs::geom::RotatedRect>& words, size_t page, size_t index,

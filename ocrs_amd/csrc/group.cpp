@@ -774,11 +774,9 @@ static ocrs_status group_recognize_text_batch(ocrs_engine_group* g, const ocrs_p
                 }
                 std::this_thread::sleep_for(std::chrono::duration<double>(g->replay_s[2]));
             } else {
-                std::vector<std::vector<CtcStep>> steps;
-                std::vector<RecLine> rl;
-                std::vector<uint32_t> ctc_len;
-                e->recognize(mine.data(), mine.size(), lpp, &steps, &rl, &ctc_len, nullptr, rectify);
-                flatten_chars(e, rl, ctc_len, steps, &flat, &offs);
+                std::vector<RecResult> res;
+                e->recognize(mine.data(), mine.size(), lpp, &res, false, rectify);
+                flatten_chars(e, res, &flat, &offs);
                 if (g->replay_mode == 1) {
                     std::lock_guard<std::mutex> lk(g->replay_mu);
                     size_t l = 0;

@@ -234,6 +234,67 @@ def test_crafted_salt_noise_takes_the_overflow_rerun(w):
     assert got[2].tolist() == [14 * 16] * 6
 
 
+def second_trip_pages(w):
+    """Two 128 x w maps.  A: six kept blobs with a speck beside each.  B: the same below salt on the stride-2 lattice
+    over rows 0..63 — more components than the 2 048 that travel with the counts, fewer than the first pass has room
+    for: the page is fetched in a second round trip, and its kept words come after all the salt in component order."""
+    h = 128
+    A = np.zeros((h, w), np.float32)
+    for k in range(6):
+        A[90:104, 20 + 60 * k:20 + 60 * k + 16] = 0.3 + k / 16.0
+        A[92:94, 50 + 60 * k:52 + 60 * k] = 0.9
+    B = A.copy()
+    rng = np.random.default_rng(w)
+    ys, xs = np.meshgrid(np.arange(0, 64, 2), np.arange(0, w, 2), indexing="ij")
+    B[ys, xs] = rng.uniform(0.25, 2.0, ys.shape).astype(np.float32)
+    return A, B
+
+
+@pytest.mark.parametrize("w", [704, 702], ids=["quad", "byte"])
+def test_second_round_trip_page_in_a_batch_with_a_prefix_page(w):
+    A, B = second_trip_pages(w)
+    h = A.shape[0]
+    refA = DR.reference(A, 0.2, MIN_AREA, count=True)
+    refB = DR.reference(B, 0.2, MIN_AREA, count=True)
+    capacity = min(65536, h * w // 2 + 16)
+    print("w = %d: A %d components, %d kept; B %d components, %d kept, capacity %d"
+          % (w, refA[3], len(refA[0]), refB[3], len(refB[0]), capacity))
+    assert refA[3] == 12 and refA[3] <= 2048, "A travels with the counts"
+    assert refB[3] == 32 * (w // 2) + 12 and 2048 < refB[3] <= capacity, "B needs the second trip and no re-run"
+    assert len(refA[0]) == len(refB[0]) == 6 and refB[2].tolist() == [14 * 16] * 6
+    maps = {"A": A, "B": B}
+    ref = {"A": refA[:3], "B": refB[:3]}
+    queue = []
+
+    def model(x):   # its k-th map on its k-th call
+        assert x.shape == (1, 1, h, w)
+        return queue.pop(0).reshape(1, 1, h, w)
+
+    eng = OcrEngine(detection_model=Model.from_callable([1, 1, h, w], model))
+    inp = eng.prepare_input(ImageSource.from_tensor(np.zeros((h, w, 1), np.uint8), DimOrder.Hwc))
+
+    def run(names, scores):
+        queue[:] = [maps[n] for n in names]
+        out = eng.detect_words_batch([inp] * len(names), scores=scores) if len(names) > 1 else \
+            [[x] for x in eng.detect_words(inp, scores=True)] if scores else [eng.detect_words(inp)]
+        assert not queue, "one run per page, in the caller's order"
+        return out
+
+    single = {n: run([n], True) for n in "AB"}
+    for n in "AB":
+        assert_same("w = %d, page %s alone" % (w, n), tuple(x[0] for x in single[n]), ref[n])
+        assert run([n], False)[0].tobytes() == single[n][0][0].tobytes(), "page %s alone, unscored" % n
+    for names in ("AB", "BA"):
+        words, score, pixels = run(names, True)
+        plain = run(names, False)
+        for i, n in enumerate(names):
+            what = "w = %d, batch %s, page %s" % (w, names, n)
+            assert_same(what, (words[i], score[i], pixels[i]), ref[n])
+            assert_same(what + " against its single-page call", (words[i], score[i], pixels[i]), tuple(x[0] for x in single[n]))
+            assert plain[i].tobytes() == words[i].tobytes(), what + ": unscored rects"
+            assert plain[i].tobytes() == run([n], False)[0].tobytes(), what + ": unscored against its single-page call"
+
+
 # ------------------------------------------------------------------ 3. scoring changes nobody's rects or launches
 DET_STAGES = ("resize_to_model", "detection_cnn", "resize_threshold", "ccl", "contour_rects")
 
