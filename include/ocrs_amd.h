@@ -310,6 +310,9 @@ OCRS_API void ocrs_page_free(ocrs_page* p);
 OCRS_API ocrs_status ocrs_page_dims(const ocrs_page* p, int* height, int* width);
 /* Copy the prepared grey page [H,W] f32 to host (OcrInput.image, lib.rs:127). */
 OCRS_API ocrs_status ocrs_page_image(const ocrs_page* p, float* out_hw);
+/* The inverse of ocrs_page_image: a page on the engine's device from an already prepared grey image [H,W] f32 (host
+ * memory), copied bit for bit; nothing is converted or checked.  For a caller that keeps prepared pages on the host. */
+OCRS_API ocrs_status ocrs_engine_page_from_grey(const ocrs_engine* e, const float* grey_hw, int height, int width, ocrs_page** out);
 
 /* OcrEngine::detect_words (lib.rs:193-199 -> detection.rs:104-122).
  * *rects receives n x 6 floats in contour discovery order. */
@@ -512,6 +515,51 @@ OCRS_API ocrs_status ocrs_engine_recognize_text_batch_rectified(const ocrs_engin
 OCRS_API ocrs_status ocrs_engine_recognize_tokens_rectified(const ocrs_engine* e, const ocrs_page* page, const float* line_rects,
                                                             const size_t* line_offsets, size_t n_lines, uint32_t** labels,
                                                             uint32_t** positions, size_t** token_offsets);
+
+/* ------------------------------------------------------------------------
+ * Quarter turns and auto-orientation (no reference counterpart, opt-in).  find_text_lines groups words
+ * along x, so a page that went through the feeder sideways or upside down reads as nothing.  These calls turn a resident
+ * page by multiples of 90 degrees on the device, decide which turn makes it read, and map the results of the turned page
+ * back to the frame of the page as given.  A turned page is an ordinary ocrs_page: every other call takes it.
+ *
+ * ocrs_engine_rotate_page[s]: *out = np.rot90(page, k), counter-clockwise: k = 1: out[i][j] = in[j][W-1-i] (shape
+ * [W, H]), k = 2: out[i][j] = in[H-1-i][W-1-j], k = 3: out[i][j] = in[H-1-j][i] (shape [W, H]), k = 0: a copy.  Any
+ * integer k, reduced to ((k % 4) + 4) % 4.  Pure data movement: every bit pattern survives.  out is a new page on the
+ * page's device, independent of the source (also for k = 0); release both with ocrs_page_free in any order.  The batch
+ * form turns n pages of any sizes by their own quarter_turns[i] in one launch; out[n] receives the pages.
+ *
+ * ocrs_unrotate_rects / ocrs_unrotate_chars (host only, in place): results found on rot90(page, k) mapped back to the
+ * page_h x page_w page.  Coordinates are points of the pixel-index frame: k = 1: x = (W-1) - y', y = x', up = (-uy', ux');
+ * k = 2: x = (W-1) - x', y = (H-1) - y', up = (-ux', -uy'); k = 3: x = y', y = (H-1) - x', up = (uy', -ux').  Widths and
+ * heights are untouched.  Rects: float32, one subtraction from (float)(W-1) or (float)(H-1).  Char boxes: integers, the
+ * four bounds mapped and swapped so that left <= right and top <= bottom stay true (k = 1: left = W-1-bottom',
+ * right = W-1-top', top = left', bottom = right').
+ *
+ * ocrs_orientation_vote (host only): the word-shape vote over n word rects.  Per word, in order: its four corners as
+ * ocrs_rotated_rect_corners gives them (float32), bw = max x - min x, bh = max y - min y; a word with a value, a corner or
+ * an extent that is not finite is skipped; bw >= bh adds bw to out[0], else bh to out[1] (float64 sums).  The page reads
+ * horizontally iff out[0] >= out[1] (also with no words).
+ *
+ * ocrs_engine_detect_orientation: which of the four quarter turns makes the page read.
+ *   (a) detect_words on the page as given, then the vote: the candidates are {0, 2} if it reads horizontally, else {1, 3};
+ *   (b) the candidates other than 0 are turned in one launch and detected as one batch (k = 0 keeps the words of (a));
+ *   (c) find_text_lines per candidate; of each candidate up to max_lines lines (0 = all): those of the most words, ties to
+ *       the lower line index, kept in line order;
+ *   (d) one scored recognition batch over both candidates' lines (plain crops, the engine's decode method);
+ *   (e) score[k] = (sum of the char log-probs, float64, in line order then char order) / n_chars[k]; -inf without chars;
+ *       the two turns that are not candidates get NaN and n_chars 0;
+ *   (f) *quarter_turns = the candidate of the larger score; a tie, and -inf twice, go to the smaller k.
+ * Turn the page by *quarter_turns (ocrs_engine_rotate_page) to read it.  vote, score and n_chars may be NULL.  The
+ * detection and recognition requests inside go the way of the public batch calls and may be merged with concurrent
+ * one-page calls (option "coalesce").  The scores are the recognition confidence above: uncalibrated. */
+OCRS_API ocrs_status ocrs_engine_rotate_page(const ocrs_engine* e, const ocrs_page* page, int quarter_turns, ocrs_page** out);
+OCRS_API ocrs_status ocrs_engine_rotate_pages(const ocrs_engine* e, const ocrs_page* const* pages, size_t n, const int* quarter_turns,
+                                              ocrs_page** out);
+OCRS_API ocrs_status ocrs_unrotate_rects(float* rects6, size_t n, int page_h, int page_w, int k);
+OCRS_API ocrs_status ocrs_unrotate_chars(ocrs_text_char* chars, size_t n, int page_h, int page_w, int k);
+OCRS_API ocrs_status ocrs_orientation_vote(const float* rects6, size_t n, double out[2]);
+OCRS_API ocrs_status ocrs_engine_detect_orientation(const ocrs_engine* e, const ocrs_page* page, size_t max_lines, int* quarter_turns,
+                                                    double vote[2], double score[4], uint32_t n_chars[4]);
 
 /* OcrEngine::get_text (lib.rs:290-300): UTF-8, lines joined by '\n'. */
 OCRS_API ocrs_status ocrs_engine_get_text(const ocrs_engine* e, const ocrs_page* page, char** text);

@@ -15,7 +15,8 @@ from . import _lib
 from ._lib import OcrsError, check, lib
 
 __all__ = ["OcrEngine", "OcrEngineParams", "ImageSource", "ImageSourceError", "DimOrder", "DecodeMethod", "Model",
-           "OcrInput", "TextLine", "TextWord", "TextChar", "OcrsError", "DEFAULT_ALPHABET", "EngineGroup", "line_frame"]
+           "OcrInput", "TextLine", "TextWord", "TextChar", "OcrsError", "DEFAULT_ALPHABET", "EngineGroup", "line_frame",
+           "Orientation", "orientation_vote", "unrotate_rects", "unrotate_lines"]
 
 # lib.rs:34 (with the EUR sign the comment at lib.rs:33 asks for)
 DEFAULT_ALPHABET = " 0123456789!\"#$%&'()*+,-./:;<=>?@[\\]^_`{|}~€ABCDEFGHIJKLMNOPQRSTUVWXYZabcdefghijklmnopqrstuvwxyz"
@@ -369,6 +370,59 @@ def line_char_boxes(words, ctc_input_len, positions, rec_height=64):
     return rects, kept.astype(bool)
 
 
+class Orientation:
+    """ocrs_engine_detect_orientation's outputs: quarter_turns (the counter-clockwise quarter turns that
+    make the page read), vote float64 [2] (horizontal, vertical), scores float64 [4] (mean char log-prob per turn; NaN for
+    the two turns that were not candidates, -inf for a candidate without chars), n_chars uint32 [4]."""
+    __slots__ = ("quarter_turns", "vote", "scores", "n_chars")
+
+    def __repr__(self):
+        return "Orientation(quarter_turns=%d, vote=%s, scores=%s, n_chars=%s)" % (
+            self.quarter_turns, self.vote.tolist(), self.scores.tolist(), self.n_chars.tolist())
+
+
+def orientation_vote(rects):
+    """ocrs_orientation_vote (host only): the word-shape vote over word rects -> float64 [2]: the summed widths of the
+    words wider than tall, the summed heights of the others.  The page reads horizontally iff vote[0] >= vote[1]."""
+    a = _rects_to_array(rects)
+    out = np.zeros(2, np.float64)
+    check(lib().ocrs_orientation_vote(a.ctypes.data_as(C.POINTER(C.c_float)), C.c_size_t(len(a)),
+                                      out.ctypes.data_as(C.POINTER(C.c_double))))
+    return out
+
+
+def unrotate_rects(rects, page_hw, k):
+    """ocrs_unrotate_rects (host only): word rects found on np.rot90(page, k) -> the same rects in the frame of the
+    page_hw = (height, width) page itself, float32 [n, 6] (a copy)."""
+    a = _rects_to_array(rects).copy()
+    check(lib().ocrs_unrotate_rects(a.ctypes.data_as(C.POINTER(C.c_float)), C.c_size_t(len(a)), C.c_int(int(page_hw[0])),
+                                    C.c_int(int(page_hw[1])), C.c_int(int(k))))
+    return a
+
+
+def unrotate_boxes(boxes, page_hw, k):
+    """ocrs_unrotate_chars on bare boxes: int32 [n, 4] (top, left, bottom, right) on np.rot90(page, k) -> in the page's frame."""
+    b = np.asarray(boxes, np.int32).reshape(-1, 4)
+    arr = (_lib.TextCharC * max(len(b), 1))()
+    for i, (t, l, bo, r) in enumerate(b.tolist()):
+        arr[i] = _lib.TextCharC(0, t, l, bo, r)
+    check(lib().ocrs_unrotate_chars(arr, C.c_size_t(len(b)), C.c_int(int(page_hw[0])), C.c_int(int(page_hw[1])), C.c_int(int(k))))
+    return np.array([[arr[i].top, arr[i].left, arr[i].bottom, arr[i].right] for i in range(len(b))], np.int32).reshape(-1, 4)
+
+
+def unrotate_lines(text_lines, page_hw, k):
+    """recognize_text's output on np.rot90(page, k) -> new TextLines (None stays None) whose char boxes are in the frame of
+    the page_hw = (height, width) page itself (ocrs_unrotate_chars); text, log-probs and scores are kept."""
+    out = []
+    for t in text_lines:
+        if t is None:
+            out.append(None)
+            continue
+        boxes = unrotate_boxes([c.rect for c in t.chars()], page_hw, k)
+        out.append(TextLine([TextChar(c.char, tuple(int(v) for v in b), c.logp) for c, b in zip(t.chars(), boxes)], t.score))
+    return out
+
+
 def _detect_words_batch(name, handle, inputs, scores, tiled=False):
     """ocrs_{engine,group}_detect_words_batch[_scored | _tiled] (name without the suffix) -> rects per page [, score per
     page, pixels per page]."""
@@ -475,6 +529,15 @@ class OcrEngine:
                                               image.order, h, w, c, C.byref(h_out)))
         return OcrInput(h_out)
 
+    def input_from_grey(self, grey):
+        """ocrs_engine_page_from_grey: a page from an already prepared grey image ([H, W] or [1, H, W] float32, what
+        OcrInput.image() returns), copied bit for bit."""
+        a = np.ascontiguousarray(grey, np.float32)
+        a = a.reshape(a.shape[-2], a.shape[-1])
+        h_out = C.c_void_p()
+        check(lib().ocrs_engine_page_from_grey(self._h, a.ctypes.data_as(C.POINTER(C.c_float)), a.shape[0], a.shape[1], C.byref(h_out)))
+        return OcrInput(h_out)
+
     def prepare_input_batch_raw(self, host_ptrs, dtype, order, h, w, c):
         """n equally sized host images given as raw pointers (e.g. pinned buffers from ocrs_host_malloc): one call,
         one wait."""
@@ -501,6 +564,35 @@ class OcrEngine:
         buf = C.create_string_buffer(bytes(data), len(data))
         check(lib().ocrs_engine_prepare_input_jpeg(self._h, buf, C.c_size_t(len(data)), C.byref(h_out), C.byref(cb)))
         return OcrInput(h_out), cb.value
+
+    # ---- quarter turns and auto-orientation
+    def rotate(self, inp, k):
+        """ocrs_engine_rotate_page: np.rot90(page, k) (counter-clockwise, any integer k) as a new resident page."""
+        return self.rotate_batch([inp], [k])[0]
+
+    def rotate_batch(self, inputs, ks):
+        """ocrs_engine_rotate_pages: pages of any sizes, each by its own k, in one launch."""
+        n = len(inputs)
+        if len(ks) != n:
+            raise ValueError("rotate_batch: one k per page")
+        pages = (C.c_void_p * n)(*[i._h for i in inputs])
+        turns = (C.c_int * n)(*[int(k) for k in ks])
+        out = (C.c_void_p * n)()
+        check(lib().ocrs_engine_rotate_pages(self._h, pages, C.c_size_t(n), turns, out))
+        return [OcrInput(C.c_void_p(out[i])) for i in range(n)]
+
+    def detect_orientation(self, inp, max_lines=8):
+        """ocrs_engine_detect_orientation -> Orientation: which quarter turn makes the page read (rotate(inp,
+        result.quarter_turns) is the upright page).  max_lines: lines recognised per candidate turn (0 = all)."""
+        o = Orientation()
+        k = C.c_int(0)
+        o.vote, o.scores, o.n_chars = np.zeros(2, np.float64), np.zeros(4, np.float64), np.zeros(4, np.uint32)
+        check(lib().ocrs_engine_detect_orientation(self._h, inp._h, C.c_size_t(int(max_lines)), C.byref(k),
+                                                   o.vote.ctypes.data_as(C.POINTER(C.c_double)),
+                                                   o.scores.ctypes.data_as(C.POINTER(C.c_double)),
+                                                   o.n_chars.ctypes.data_as(C.POINTER(C.c_uint32))))
+        o.quarter_turns = k.value
+        return o
 
     # ---- lib.rs:193-199
     def detect_words(self, inp, scores=False, tiled=False):
@@ -778,8 +870,13 @@ class OcrEngine:
         return float(lib().ocrs_engine_detection_threshold(self._h))
 
     # ---- lib.rs:290-300
-    def get_text(self, inp, rectify=False):
-        """rectify=True: the same sequence (detect_words, find_text_lines, recognize_text) with rectified crops."""
+    def get_text(self, inp, rectify=False, orientation=None):
+        """rectify=True: the same sequence (detect_words, find_text_lines, recognize_text) with rectified crops.
+        orientation: None reads the page as given; an int turns it by that many quarter turns counter-clockwise first
+        (rotate); "auto" by what detect_orientation finds."""
+        if orientation is not None:
+            k = self.detect_orientation(inp).quarter_turns if orientation == "auto" else int(orientation)
+            inp = self.rotate(inp, k)
         if rectify:
             lines = self.find_text_lines(inp, self.detect_words(inp))
             return "\n".join(str(t) for t in self.recognize_text(inp, lines, rectify=True) if t is not None)

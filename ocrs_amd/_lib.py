@@ -81,6 +81,8 @@ DECLARED_SYMBOLS = [
     "ocrs_line_frame", "ocrs_line_char_boxes", "ocrs_engine_prepare_recognition_input_rectified",
     "ocrs_engine_recognize_text_rectified", "ocrs_engine_recognize_text_batch_rectified",
     "ocrs_group_recognize_text_batch_rectified", "ocrs_engine_recognize_tokens_rectified",
+    "ocrs_engine_rotate_page", "ocrs_engine_rotate_pages", "ocrs_unrotate_rects", "ocrs_unrotate_chars",
+    "ocrs_orientation_vote", "ocrs_engine_detect_orientation", "ocrs_engine_page_from_grey",
 ]
 
 ABI_VERSION = 6   # include/ocrs_amd.h OCRS_ABI_VERSION

@@ -58,6 +58,11 @@ def main(argv=None):
     ap.add_argument("--rectify", action="store_true",
                     help="crop every text line along its own axis instead of from its axis-aligned bounding box: for skewed "
                          "scans (no reference counterpart: DESIGN.md 8.4); also applies to --text-line-images")
+    ap.add_argument("--orientation", choices=("0", "90", "180", "270", "auto"), default=None, metavar="{0,90,180,270,auto}",
+                    help="turn the page counter-clockwise by that many degrees on the GPU before reading it, for scans that went "
+                         "through the feeder sideways or upside down; auto: the turn the engine's probe finds (uncalibrated on "
+                         "the synthetic models).  Boxes are reported in the frame of the file as given; the JSON gains "
+                         "\"orientation\" (no reference counterpart: DESIGN.md 8.5)")
     ap.add_argument("-o", "--output")
     ap.add_argument("--debug", action="store_true")
     ap.add_argument("--text-map", action="store_true", help="write text-map.png (detect_text_pixels)")
@@ -99,6 +104,17 @@ def main(argv=None):
         img = load_image(args.image)
         shape_hw = img.shape[:2]
         inp = engine.prepare_input(ImageSource.from_tensor(img, DimOrder.Hwc))
+    turns = None
+    if args.orientation is not None:   # from here on the turned page is the page; results are mapped back before output
+        if args.orientation == "auto":
+            found = engine.detect_orientation(inp)
+            turns = found.quarter_turns
+            if args.debug:
+                print("Orientation: vote %s (horizontal : vertical), scores %s over %s chars -> %d degrees"
+                      % (found.vote.tolist(), found.scores.tolist(), found.n_chars.tolist(), 90 * turns))
+        else:
+            turns = int(args.orientation) // 90
+        inp = engine.rotate(inp, turns)
     tiled = False if args.tiled is None else True if args.tiled < 0 else args.tiled
     if args.text_map or args.text_mask:
         tm = engine.detect_text_pixels(inp, tiled=tiled)
@@ -123,8 +139,14 @@ def main(argv=None):
         for i, line in enumerate(lines):
             write_image("lines/line-%d.png" % i, engine.prepare_recognition_input(inp, line, rectify=args.rectify) + np.float32(0.5))
     texts = engine.recognize_text(inp, lines, scores=args.confidence, rectify=args.rectify)
+    if turns is not None:
+        from . import unrotate_lines, unrotate_rects
+        texts = unrotate_lines(texts, tuple(shape_hw), turns)
+        if word_boxes is not None:
+            word_boxes = [[(unrotate_rects([r], tuple(shape_hw), turns)[0], s, n) for r, s, n in boxes] for boxes in word_boxes]
     if args.json:
-        content = output.format_json_output(args.image, tuple(shape_hw), texts, confidence=args.confidence, word_boxes=word_boxes)
+        content = output.format_json_output(args.image, tuple(shape_hw), texts, confidence=args.confidence, word_boxes=word_boxes,
+                                            orientation=None if turns is None else 90 * turns)
     else:
         content = output.format_text_output(texts)
     if args.output:

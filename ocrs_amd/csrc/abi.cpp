@@ -538,6 +538,19 @@ ocrs_status ocrs_page_image(const ocrs_page* p, float* out_hw) {
     });
 }
 
+ocrs_status ocrs_engine_page_from_grey(const ocrs_engine* e, const float* grey_hw, int height, int width, ocrs_page** out) {
+    return guarded_engine(e, [&] {
+        if (!e || !grey_hw || !out) fail(OCRS_ERR_INVALID_ARGUMENT, "null argument");
+        if (height <= 0 || width <= 0) fail(OCRS_ERR_INVALID_ARGUMENT, "image has no pixels");
+        auto page = std::make_unique<ocrs_page>();
+        page->h = height;
+        page->w = width;
+        page->grey = DevBuf((size_t)height * width * sizeof(float));
+        OCRS_HIP(hipMemcpy(page->grey.p, grey_hw, page->grey.bytes, hipMemcpyHostToDevice));
+        *out = page.release();
+    });
+}
+
 namespace {
 
 // ocrs_engine_detect_words[_batch][_scored | _tiled]: score / pixels null for the unscored calls; tile_overlap < 0: untiled

@@ -304,6 +304,20 @@ struct RectLineDesc {   // one text line to crop along its own axis: LineDesc's 
 void rectify_lines(const float* const* d_pages, const int32_t* d_page_hw /*[pages][2]*/, const RectLineDesc* d_lines,
                    const int32_t* d_ranges, int n_lines, int max_out_w, int out_h, float* d_out, hipStream_t s);
 
+// ---- kernels_rotate.hip ------------------------------------
+struct RotateDesc {      // one page to turn: dst = np.rot90(src, k)
+    const uint32_t* src; // [h, w] pixels as 32-bit words
+    uint32_t* dst;       // [h, w] for k even, [w, h] for k odd; never overlaps src
+    int32_t h, w;        // of the source
+    int32_t k;           // quarter turns counter-clockwise, 0 .. 3
+    int32_t tile0;       // first block of this page: the sum of rotate_tiles() of the pages before it
+    int32_t vec;         // k even only: w % 4 == 0 and both buffers 16-byte aligned, so 16-byte accesses are safe
+    int32_t pad_;
+};
+int64_t rotate_tiles(int h, int w);   // blocks a page of this size takes (host)
+// Pages of any mix of sizes and turns in one launch; total_tiles = the sum of rotate_tiles() over the pages.
+void rotate_pages(const RotateDesc* d_descs, int n_pages, int total_tiles, hipStream_t s);
+
 // kernels_peaks.hip
 void measure_peaks(double* mfma_tflops, double* copy_gbps);
 
