@@ -369,6 +369,58 @@ OCRS_API ocrs_status ocrs_engine_detect_words_batch_tiled(const ocrs_engine* e, 
 /* The stitched [H,W] probability map of the tiled call. */
 OCRS_API ocrs_status ocrs_engine_detect_text_pixels_tiled(const ocrs_engine* e, const ocrs_page* page, int overlap, float* out_hw);
 
+/* ------------------------------------------------------------------------
+ * Working resolution (no reference counterpart, opt-in).  The plain detection call squeezes any page into the
+ * model input with one bilinear resize; the tiled call never resizes.  These calls let the caller choose the resolution the
+ * detector sees: a resident page is resampled on the device to a work size, detection runs on that work page (plain or
+ * tiled), and the word rects come back in the frame of the page as given, so that layout and recognition run on the
+ * full-resolution page.  A resampled page is an ordinary ocrs_page: every other call takes it.
+ *
+ * ocrs_engine_resize_page[s]: *out = the page resampled to out_h x out_w (each 1 .. 65535, as are the page's own sides;
+ * else OCRS_ERR_INVALID_ARGUMENT), a new page on the page's device, independent of the source; release both with
+ * ocrs_page_free in any order.  The batch form serves n pages of any sizes, each to its own out_hw[2i], out_hw[2i+1] with its
+ * own filters[i], in one launch; out[n] receives the pages.  float32 arithmetic, every operation rounded on its own:
+ *   OCRS_RESAMPLE_BILINEAR  any sizes: the bilinear resize of the detection path (ONNX Resize linear / half_pixel) on the
+ *                           page itself, no padding.
+ *   OCRS_RESAMPLE_AREA      out_h <= H and out_w <= W (else OCRS_ERR_INVALID_ARGUMENT): the exact area average.  Along one
+ *                           axis L -> l: g = gcd(L, l), P = L / g, q = l / g; output j covers [jP, (j+1)P), source x covers
+ *                           [xq, (x+1)q); taps x = (jP) / q .. ((j+1)P - 1) / q ascending, each with the integer weight
+ *                           ov = min((j+1)P, (x+1)q) - max(jP, xq); acc = float(ov0) * in[x0], acc = acc + float(ov) * in[x],
+ *                           value = acc / float(P).  Horizontally per source row of the vertical footprint, then the same
+ *                           rule vertically over those values.  Equal sizes: the identity; a halving: ((a+b)/2 + (c+d)/2)/2.
+ *   OCRS_RESAMPLE_AUTO      area when neither side grows, else bilinear.
+ *
+ * ocrs_work_size (host only): the work size of a scale: h = clamp((int)floor(page_h * scale + 0.5), 1, 65535) in double, w
+ * likewise.  A scale that is not finite or not positive: OCRS_ERR_INVALID_ARGUMENT.
+ *
+ * ocrs_rescale_rects (host only, in place): rects of the from_h x from_w frame of a picture in its to_h x to_w frame.
+ * Coordinates are points of the pixel-index frame (pixel i covers [i - 0.5, i + 0.5)).  Equal sizes leave every bit as it
+ * is.  Otherwise, in double from the float32 values, each operation as written, the results rounded to float32:
+ * sx = to_w / from_w, sy = to_h / from_h; cx' = (cx + 0.5) * sx - 0.5, cy' likewise with sy; v = (up.x * sx, up.y * sy),
+ * lv = sqrt(v.x^2 + v.y^2); a = (-up.y * sx, up.x * sy), la = sqrt(a.x^2 + a.y^2); lv finite and > 0: up' = v / lv,
+ * h' = h * lv, w' = w * la; otherwise up stays, h' = h * sy, w' = w * sx.  An axis-aligned rect is mapped exactly; a tilted
+ * one under sx != sy (the rounding of a work size: under one pixel over the page) within that relative error.
+ *
+ * ocrs_engine_detect_words[_batch]_at: detection at a work size per page, work_hw[2i], work_hw[2i+1]; 0, 0 = the page's own
+ * size.  (1) The pages whose work size differs from their own are resampled with `filter` in one launch; (2) the work pages
+ * go through detection as the pages of ocrs_engine_detect_words_batch do (tiled == 0; may be merged with concurrent
+ * requests) or those of ocrs_engine_detect_words_batch_tiled (tiled != 0, overlap as there); (3) the rects return in each
+ * page's own frame through ocrs_rescale_rects.  score and pixels (both or neither; may be NULL) are those of the WORK page
+ * (§7.1), and the reference's 3-pixel pad of a word box and its area >= 100 rule apply at work resolution, before the map.
+ * A page whose work size is its own is not resampled and has the plain (or tiled) call's bits.  Outputs as
+ * ocrs_engine_detect_words_batch_scored. */
+typedef enum ocrs_resample_filter { OCRS_RESAMPLE_AUTO = 0, OCRS_RESAMPLE_BILINEAR = 1, OCRS_RESAMPLE_AREA = 2 } ocrs_resample_filter;
+OCRS_API ocrs_status ocrs_engine_resize_page(const ocrs_engine* e, const ocrs_page* page, int out_h, int out_w, int filter, ocrs_page** out);
+OCRS_API ocrs_status ocrs_engine_resize_pages(const ocrs_engine* e, const ocrs_page* const* pages, size_t n, const int* out_hw,
+                                              const int* filters, ocrs_page** out);
+OCRS_API ocrs_status ocrs_work_size(int page_h, int page_w, double scale, int* h, int* w);
+OCRS_API ocrs_status ocrs_rescale_rects(float* rects6, size_t n, int from_h, int from_w, int to_h, int to_w);
+OCRS_API ocrs_status ocrs_engine_detect_words_at(const ocrs_engine* e, const ocrs_page* page, int work_h, int work_w, int filter, int tiled,
+                                                 int overlap, float** rects, size_t* n, float** score, uint32_t** pixels);
+OCRS_API ocrs_status ocrs_engine_detect_words_batch_at(const ocrs_engine* e, const ocrs_page* const* pages, size_t n_pages,
+                                                       const int* work_hw, int filter, int tiled, int overlap, float** rects,
+                                                       size_t* offsets, float** score, uint32_t** pixels);
+
 /* OcrEngine::detection_threshold (lib.rs:282-287). */
 OCRS_API float ocrs_engine_detection_threshold(const ocrs_engine* e);
 

@@ -16,7 +16,7 @@ from ._lib import OcrsError, check, lib
 
 __all__ = ["OcrEngine", "OcrEngineParams", "ImageSource", "ImageSourceError", "DimOrder", "DecodeMethod", "Model",
            "OcrInput", "TextLine", "TextWord", "TextChar", "OcrsError", "DEFAULT_ALPHABET", "EngineGroup", "line_frame",
-           "Orientation", "orientation_vote", "unrotate_rects", "unrotate_lines"]
+           "Orientation", "orientation_vote", "unrotate_rects", "unrotate_lines", "work_size", "rescale_rects"]
 
 # lib.rs:34 (with the EUR sign the comment at lib.rs:33 asks for)
 DEFAULT_ALPHABET = " 0123456789!\"#$%&'()*+,-./:;<=>?@[\\]^_`{|}~€ABCDEFGHIJKLMNOPQRSTUVWXYZabcdefghijklmnopqrstuvwxyz"
@@ -423,6 +423,58 @@ def unrotate_lines(text_lines, page_hw, k):
     return out
 
 
+def work_size(page_hw, scale=None, max_side=None):
+    """ocrs_work_size (host only): the work size (height, width) of a page_hw = (height, width) page.
+    scale: each side is floor(side * scale + 0.5), kept within 1 .. 65535.  max_side=N: scale = min(1, N / max(H, W)): the
+    longest side becomes N at most and a smaller page keeps its size.  Exactly one of the two."""
+    if (scale is None) == (max_side is None):
+        raise ValueError("work_size: give scale or max_side")
+    h, w = int(page_hw[0]), int(page_hw[1])
+    if max_side is not None:
+        scale = min(1.0, float(max_side) / float(max(h, w)))
+    oh, ow = C.c_int(0), C.c_int(0)
+    check(lib().ocrs_work_size(C.c_int(h), C.c_int(w), C.c_double(float(scale)), C.byref(oh), C.byref(ow)))
+    return oh.value, ow.value
+
+
+def rescale_rects(rects, from_hw, to_hw):
+    """ocrs_rescale_rects (host only): word rects of the from_hw = (height, width) frame of a picture -> the same rects in
+    its to_hw frame, float32 [n, 6] (a copy).  Equal sizes keep every bit."""
+    a = _rects_to_array(rects).copy()
+    check(lib().ocrs_rescale_rects(a.ctypes.data_as(C.POINTER(C.c_float)), C.c_size_t(len(a)), C.c_int(int(from_hw[0])),
+                                   C.c_int(int(from_hw[1])), C.c_int(int(to_hw[0])), C.c_int(int(to_hw[1]))))
+    return a
+
+
+def _work_hw(work_size):
+    """None = the page's own size (0, 0)."""
+    return (0, 0) if work_size is None else (int(work_size[0]), int(work_size[1]))
+
+
+def _detect_words_batch_at(handle, inputs, work_sizes, scores, tiled, work_filter):
+    """ocrs_engine_detect_words_batch_at -> rects per page [, score per page, pixels per page]."""
+    n = len(inputs)
+    if len(work_sizes) != n:
+        raise ValueError("detect_words_batch: one work size per page")
+    pages = (C.c_void_p * n)(*[i._h for i in inputs])
+    hw = (C.c_int * (2 * n))(*[v for s in work_sizes for v in _work_hw(s)])
+    rects = C.POINTER(C.c_float)()
+    offs = (C.c_size_t * (n + 1))()
+    overlap = _tile_overlap(tiled)
+    sc, px = C.POINTER(C.c_float)(), C.POINTER(C.c_uint32)()
+    check(lib().ocrs_engine_detect_words_batch_at(handle, pages, C.c_size_t(n), hw, C.c_int(_lib.RESAMPLE_FILTERS[work_filter]),
+                                                  C.c_int(0 if overlap is None else 1), C.c_int(-1 if overlap is None else overlap),
+                                                  C.byref(rects), offs, C.byref(sc) if scores else None, C.byref(px) if scores else None))
+    total = offs[n]
+    flat = np.ctypeslib.as_array(rects, shape=(max(total, 1) * 6,))[: total * 6].reshape(-1, 6).copy()
+    lib().ocrs_buffer_free(rects)
+    words = [flat[offs[i]:offs[i + 1]] for i in range(n)]
+    if not scores:
+        return words
+    fs, fp = _take(sc, total, np.float32), _take(px, total, np.uint32)
+    return words, [fs[offs[i]:offs[i + 1]] for i in range(n)], [fp[offs[i]:offs[i + 1]] for i in range(n)]
+
+
 def _detect_words_batch(name, handle, inputs, scores, tiled=False):
     """ocrs_{engine,group}_detect_words_batch[_scored | _tiled] (name without the suffix) -> rects per page [, score per
     page, pixels per page]."""
@@ -594,12 +646,40 @@ class OcrEngine:
         o.quarter_turns = k.value
         return o
 
+    # ---- working resolution
+    def resize(self, inp, size, filter="auto"):
+        """ocrs_engine_resize_page: the page resampled to size = (height, width) as a new resident page.  filter: "area"
+        (the exact area average; only shrinks), "bilinear" (the detection path's resize) or "auto" (area when neither side
+        grows, else bilinear)."""
+        return self.resize_batch([inp], [size], [filter])[0]
+
+    def resize_batch(self, inputs, sizes, filters="auto"):
+        """ocrs_engine_resize_pages: pages of any sizes, each to its own size with its own filter (or one for all), in one
+        launch."""
+        n = len(inputs)
+        if isinstance(filters, str):
+            filters = [filters] * n
+        if len(sizes) != n or len(filters) != n:
+            raise ValueError("resize_batch: one size and one filter per page")
+        pages = (C.c_void_p * n)(*[i._h for i in inputs])
+        hw = (C.c_int * (2 * n))(*[int(v) for s in sizes for v in (s[0], s[1])])
+        fl = (C.c_int * n)(*[_lib.RESAMPLE_FILTERS[f] for f in filters])
+        out = (C.c_void_p * n)()
+        check(lib().ocrs_engine_resize_pages(self._h, pages, C.c_size_t(n), hw, fl, out))
+        return [OcrInput(C.c_void_p(out[i])) for i in range(n)]
+
     # ---- lib.rs:193-199
-    def detect_words(self, inp, scores=False, tiled=False):
+    def detect_words(self, inp, scores=False, tiled=False, work_size=None, work_filter="auto"):
         """scores=True: through ocrs_engine_detect_words_scored -> (words, score float32 [n], pixels uint32 [n]): per word
         the mean text probability of its component's pixels and their number.
         tiled=True | <overlap>: through ocrs_engine_detect_words_tiled: the page is cut into model-sized tiles at its own
-        resolution instead of being resized to the model input (about one detector run per tile)."""
+        resolution instead of being resized to the model input (about one detector run per tile).
+        work_size=(h, w): through ocrs_engine_detect_words_at: the detector sees the page resampled to that size (filter
+        work_filter, as resize) and the words come back in the page's own frame; scores and pixels are those of the work
+        page.  work_size() makes one from a scale or a longest side."""
+        if work_size is not None:
+            out = _detect_words_batch_at(self._h, [inp], [work_size], scores, tiled, work_filter)
+            return tuple(o[0] for o in out) if scores else out[0]
         rects = C.POINTER(C.c_float)()
         n = C.c_size_t(0)
         overlap = _tile_overlap(tiled)
@@ -618,8 +698,11 @@ class OcrEngine:
             return out
         return out, _take(sc, n.value, np.float32), _take(px, n.value, np.uint32)
 
-    def detect_words_batch(self, inputs, scores=False, tiled=False):
-        """scores=True: -> (words per page, score per page, pixels per page).  tiled: as detect_words."""
+    def detect_words_batch(self, inputs, scores=False, tiled=False, work_sizes=None, work_filter="auto"):
+        """scores=True: -> (words per page, score per page, pixels per page).  tiled: as detect_words.  work_sizes: one
+        (h, w) or None (the page's own size) per page, as detect_words' work_size; resampled in one launch."""
+        if work_sizes is not None:
+            return _detect_words_batch_at(self._h, inputs, work_sizes, scores, tiled, work_filter)
         return _detect_words_batch("ocrs_engine_detect_words_batch", self._h, inputs, scores, tiled)
 
     # ---- lib.rs:207-213
@@ -870,13 +953,18 @@ class OcrEngine:
         return float(lib().ocrs_engine_detection_threshold(self._h))
 
     # ---- lib.rs:290-300
-    def get_text(self, inp, rectify=False, orientation=None):
+    def get_text(self, inp, rectify=False, orientation=None, work_size=None):
         """rectify=True: the same sequence (detect_words, find_text_lines, recognize_text) with rectified crops.
         orientation: None reads the page as given; an int turns it by that many quarter turns counter-clockwise first
-        (rotate); "auto" by what detect_orientation finds."""
+        (rotate); "auto" by what detect_orientation finds.
+        work_size=(h, w): the words are detected at that size of the (turned) page, lines and text are read from the page at
+        its full resolution."""
         if orientation is not None:
             k = self.detect_orientation(inp).quarter_turns if orientation == "auto" else int(orientation)
             inp = self.rotate(inp, k)
+        if work_size is not None:
+            lines = self.find_text_lines(inp, self.detect_words(inp, work_size=work_size))
+            return "\n".join(str(t) for t in self.recognize_text(inp, lines, rectify=rectify) if t is not None)
         if rectify:
             lines = self.find_text_lines(inp, self.detect_words(inp))
             return "\n".join(str(t) for t in self.recognize_text(inp, lines, rectify=True) if t is not None)

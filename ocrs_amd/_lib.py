@@ -83,10 +83,13 @@ DECLARED_SYMBOLS = [
     "ocrs_group_recognize_text_batch_rectified", "ocrs_engine_recognize_tokens_rectified",
     "ocrs_engine_rotate_page", "ocrs_engine_rotate_pages", "ocrs_unrotate_rects", "ocrs_unrotate_chars",
     "ocrs_orientation_vote", "ocrs_engine_detect_orientation", "ocrs_engine_page_from_grey",
+    "ocrs_engine_resize_page", "ocrs_engine_resize_pages", "ocrs_work_size", "ocrs_rescale_rects",
+    "ocrs_engine_detect_words_at", "ocrs_engine_detect_words_batch_at",
 ]
 
 ABI_VERSION = 6   # include/ocrs_amd.h OCRS_ABI_VERSION
 TILE_OVERLAP_DEFAULT = 100   # include/ocrs_amd.h OCRS_TILE_OVERLAP_DEFAULT
+RESAMPLE_FILTERS = {"auto": 0, "bilinear": 1, "area": 2}   # include/ocrs_amd.h ocrs_resample_filter
 
 _lib = None
 

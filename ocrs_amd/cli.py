@@ -63,6 +63,15 @@ def main(argv=None):
                          "through the feeder sideways or upside down; auto: the turn the engine's probe finds (uncalibrated on "
                          "the synthetic models).  Boxes are reported in the frame of the file as given; the JSON gains "
                          "\"orientation\" (no reference counterpart: DESIGN.md 8.5)")
+    work = ap.add_mutually_exclusive_group()
+    work.add_argument("--work-scale", type=float, metavar="S",
+                      help="detect words on the page resampled by S on the GPU (area average when shrinking, bilinear when "
+                           "enlarging) and read the text from the page at its full resolution; boxes are reported in the frame of "
+                           "the file (no reference counterpart; what a detector gains is uncalibrated on the synthetic models: "
+                           "DESIGN.md 7.3)")
+    work.add_argument("--work-max-side", type=int, metavar="N",
+                      help="as --work-scale with S = min(1, N / the page's longer side): the detector sees a page of at most N "
+                           "pixels a side")
     ap.add_argument("-o", "--output")
     ap.add_argument("--debug", action="store_true")
     ap.add_argument("--text-map", action="store_true", help="write text-map.png (detect_text_pixels)")
@@ -116,15 +125,21 @@ def main(argv=None):
             turns = int(args.orientation) // 90
         inp = engine.rotate(inp, turns)
     tiled = False if args.tiled is None else True if args.tiled < 0 else args.tiled
-    if args.text_map or args.text_mask:
-        tm = engine.detect_text_pixels(inp, tiled=tiled)
+    work_hw = None   # the size the detector sees the (turned) page at: DESIGN.md 7.3
+    if args.work_scale is not None or args.work_max_side is not None:
+        from . import work_size
+        work_hw = work_size(inp.shape[-2:], scale=args.work_scale, max_side=args.work_max_side)
+        if args.debug:
+            print("Working resolution: %dx%d for a page of %dx%d" % (work_hw[1], work_hw[0], inp.shape[-1], inp.shape[-2]))
+    if args.text_map or args.text_mask:   # with a working resolution: the map of the work page, at its size
+        tm = engine.detect_text_pixels(inp if work_hw is None else engine.resize(inp, work_hw), tiled=tiled)
         if args.text_map:
             write_image("text-map.png", tm)
         if args.text_mask:
             write_image("text-mask.png", (tm > np.float32(engine.detection_threshold())).astype(np.float32))
     word_boxes = None
     if args.detection_confidence or args.min_word_score is not None:
-        words, wscore, wpixels = engine.detect_words(inp, scores=True, tiled=tiled)
+        words, wscore, wpixels = engine.detect_words(inp, scores=True, tiled=tiled, work_size=work_hw)
         if args.min_word_score is not None:
             keep = wscore >= np.float32(args.min_word_score)
             words, wscore, wpixels = words[keep], wscore[keep], wpixels[keep]
@@ -132,7 +147,7 @@ def main(argv=None):
         if args.detection_confidence:
             word_boxes = [[(words[k], wscore[k], wpixels[k]) for k in idx] for idx in index]
     else:
-        words = engine.detect_words(inp, tiled=tiled)
+        words = engine.detect_words(inp, tiled=tiled, work_size=work_hw)
         lines = engine.find_text_lines(inp, words)
     if args.text_line_images:  # main.rs:66-86
         os.makedirs("lines", exist_ok=True)

@@ -318,6 +318,20 @@ int64_t rotate_tiles(int h, int w);   // blocks a page of this size takes (host)
 // Pages of any mix of sizes and turns in one launch; total_tiles = the sum of rotate_tiles() over the pages.
 void rotate_pages(const RotateDesc* d_descs, int n_pages, int total_tiles, hipStream_t s);
 
+// ---- kernels_resample.hip ----------------------------------
+struct ResampleDesc {    // one page to resample: dst [dh, dw] from src [sh, sw]
+    const float* src;
+    float* dst;          // never overlaps src
+    int32_t sh, sw, dh, dw;   // each 1 .. 65535
+    int32_t area;        // 1: the area filter (dh <= sh and dw <= sw), 0: bilinear
+    int32_t block0;      // first block of this page: the sum of resample_blocks() of the pages before it
+    uint32_t py, qy;     // area only: sh / gcd(sh, dh), dh / gcd(sh, dh)
+    uint32_t px, qx;     // likewise along x
+};
+int64_t resample_blocks(int dh, int dw);   // blocks an output of this size takes (host)
+// Pages of any mix of sizes and filters in one launch; total_blocks = the sum of resample_blocks() over the pages.
+void resample_pages(const ResampleDesc* d_descs, int n_pages, int total_blocks, hipStream_t s);
+
 // kernels_peaks.hip
 void measure_peaks(double* mfma_tflops, double* copy_gbps);
 
