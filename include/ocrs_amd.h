@@ -421,6 +421,61 @@ OCRS_API ocrs_status ocrs_engine_detect_words_batch_at(const ocrs_engine* e, con
                                                        const int* work_hw, int filter, int tiled, int overlap, float** rects,
                                                        size_t* offsets, float** score, uint32_t** pixels);
 
+/* ------------------------------------------------------------------------
+ * Page normalisation (no reference counterpart, opt-in).  What rotate and resize do to a page's geometry,
+ * this does to its grey levels: a phone photo with a shadow across it, a faint photocopy or a dark-mode screenshot becomes
+ * a new resident page with ink at -0.5 and paper at +0.5, dark text on a light page whatever came in, and every other
+ * call takes that page.  Coordinates do not move, so nothing needs mapping back.  The source page is untouched; release
+ * both with ocrs_page_free in any order.  What a trained detector gains is uncalibrated: the figures of DESIGN.md §7.4
+ * are for the synthetic detection files only.
+ *
+ * The definition (tests/normalize_ref.py restates it and the library equals it bit for bit; float32, every operation
+ * rounded on its own; all counting in integers, so the result does not depend on schedule or batch):
+ *   bins      g = clamp(v + 0.5f, 0, 1), NaN stays NaN and is not counted; bin = floor(g * 256f) kept within 0 .. 255.
+ *             Tiles are tile x tile pixels from the page origin, edge tiles partial.  pct(h, num, den) = the smallest bin
+ *             whose cumulative count c has c * den >= num * n; -1 for an empty histogram.
+ *   polarity  AUTO: every non-empty tile adds pct(19,20) + pct(1,20) - 2 pct(1,2) of its histogram to a vote (does the
+ *             tile's median sit nearer its dark or its bright end, weighted by the tile's contrast); the page is dark iff
+ *             the vote > 0.  KEEP: light, INVERT: dark; the vote stays 0.  On a dark page g = clamp(0.5f - v, 0, 1)
+ *             and the tile and page histograms are read mirrored (bin 255 - b).
+ *   flatten   white bin of a tile = pct(3,4) of its effective histogram, Wg = the same of the page's.  A present tile's
+ *             value is max(white, Wg / 2) (a tile inside a dark figure is not blown up to white), then the maximum over
+ *             the present tiles of its 3 x 3 neighbourhood (a heading that fills a tile is not read as background); an
+ *             empty tile takes max(Wg, 0).  Level L = (bin + 1) / 256.  B = L interpolated bilinearly over tile centres:
+ *             fy = (y + 0.5f) * (1 / tile) - 0.5f kept within [0, tiles_y - 1], x likewise, top = (1 - wx) L00 + wx L01,
+ *             bot likewise, B = (1 - wy) top + wy bot.  u = min(g / B, 1).  flatten == 0: u = g.
+ *   levels    histogram of u over the page, binned as above; lo = pct(1,100), hi = pct(1,2) (the median is the paper).
+ *             hi > lo >= 0: out = clamp((u - lo/256) / (hi/256 - lo/256), 0, 1) - 0.5f; otherwise (a blank page, an
+ *             all-NaN page) and with levels == 0: out = u - 0.5f.
+ *   neither   flatten == 0 and levels == 0: the page's own 32-bit words, the sign bit flipped on a dark page.
+ * NaN stays NaN and only NaN does; with flatten or levels on, every other result lies in [-0.5, 0.5].
+ *
+ * ocrs_normalize_params_default: tile 64, OCRS_POLARITY_AUTO, flatten 1, levels 1.  ocrs_normalize_params_check (host
+ * only): OCRS_ERR_INVALID_ARGUMENT for a tile that is not a power of two in 16 .. 256 or an unknown polarity; the engine
+ * calls refuse the same, and a page with a side over 65535.  ocrs_engine_normalize_pages serves n pages of any sizes, each
+ * with its own params[i], in five launches for the whole batch on one stream; out_pages[n] receives the pages, out_info[n]
+ * (may be NULL) what was found.  ocrs_engine_normalize_page: params == NULL means the default. */
+typedef enum ocrs_polarity { OCRS_POLARITY_AUTO = 0, OCRS_POLARITY_KEEP = 1, OCRS_POLARITY_INVERT = 2 } ocrs_polarity;
+typedef struct ocrs_normalize_params {
+    int32_t tile;     /* a power of two, 16 .. 256 */
+    int32_t polarity; /* ocrs_polarity */
+    int32_t flatten;  /* 0 / 1 */
+    int32_t levels;   /* 0 / 1 */
+} ocrs_normalize_params;
+typedef struct ocrs_normalize_info {
+    int32_t dark;     /* 1: the page was read as light text on a dark page and inverted */
+    int32_t white;    /* Wg; -1: no pixel was counted */
+    int32_t lo, hi;   /* the bins of u the levels were taken from; -1, -1 with levels == 0 or nothing counted */
+    int64_t vote;     /* the polarity vote; 0 unless OCRS_POLARITY_AUTO */
+    uint64_t counted; /* pixels that are not NaN */
+} ocrs_normalize_info;
+OCRS_API ocrs_status ocrs_normalize_params_default(ocrs_normalize_params* out);
+OCRS_API ocrs_status ocrs_normalize_params_check(const ocrs_normalize_params* params);
+OCRS_API ocrs_status ocrs_engine_normalize_page(const ocrs_engine* e, const ocrs_page* page, const ocrs_normalize_params* params,
+                                                ocrs_page** out_page, ocrs_normalize_info* out_info);
+OCRS_API ocrs_status ocrs_engine_normalize_pages(const ocrs_engine* e, const ocrs_page* const* pages, size_t n,
+                                                 const ocrs_normalize_params* params, ocrs_page** out_pages, ocrs_normalize_info* out_info);
+
 /* OcrEngine::detection_threshold (lib.rs:282-287). */
 OCRS_API float ocrs_engine_detection_threshold(const ocrs_engine* e);
 

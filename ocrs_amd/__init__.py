@@ -16,7 +16,7 @@ from ._lib import OcrsError, check, lib
 
 __all__ = ["OcrEngine", "OcrEngineParams", "ImageSource", "ImageSourceError", "DimOrder", "DecodeMethod", "Model",
            "OcrInput", "TextLine", "TextWord", "TextChar", "OcrsError", "DEFAULT_ALPHABET", "EngineGroup", "line_frame",
-           "Orientation", "orientation_vote", "unrotate_rects", "unrotate_lines", "work_size", "rescale_rects"]
+           "Orientation", "orientation_vote", "unrotate_rects", "unrotate_lines", "work_size", "rescale_rects", "normalize_params"]
 
 # lib.rs:34 (with the EUR sign the comment at lib.rs:33 asks for)
 DEFAULT_ALPHABET = " 0123456789!\"#$%&'()*+,-./:;<=>?@[\\]^_`{|}~€ABCDEFGHIJKLMNOPQRSTUVWXYZabcdefghijklmnopqrstuvwxyz"
@@ -446,6 +446,31 @@ def rescale_rects(rects, from_hw, to_hw):
     return a
 
 
+def normalize_params(tile=None, polarity=None, flatten=None, levels=None):
+    """ocrs_normalize_params as a dict: ocrs_normalize_params_default (tile 64, polarity "auto", flatten and
+    levels on) with the given fields replaced, checked by ocrs_normalize_params_check (host only)."""
+    p = _normalize_struct(tile, polarity, flatten, levels)
+    check(lib().ocrs_normalize_params_check(C.byref(p)))
+    return {"tile": int(p.tile), "polarity": [k for k, v in _lib.POLARITIES.items() if v == p.polarity][0],
+            "flatten": bool(p.flatten), "levels": bool(p.levels)}
+
+
+def _normalize_struct(tile=None, polarity=None, flatten=None, levels=None):
+    p = _lib.NormalizeParams()
+    check(lib().ocrs_normalize_params_default(C.byref(p)))
+    if tile is not None:
+        p.tile = int(tile)
+    if polarity is not None:
+        if polarity not in _lib.POLARITIES:
+            raise ValueError("normalize: polarity is one of %s" % ", ".join(_lib.POLARITIES))
+        p.polarity = _lib.POLARITIES[polarity]
+    if flatten is not None:
+        p.flatten = 1 if flatten else 0
+    if levels is not None:
+        p.levels = 1 if levels else 0
+    return p
+
+
 def _work_hw(work_size):
     """None = the page's own size (0, 0)."""
     return (0, 0) if work_size is None else (int(work_size[0]), int(work_size[1]))
@@ -645,6 +670,32 @@ class OcrEngine:
                                                    o.n_chars.ctypes.data_as(C.POINTER(C.c_uint32))))
         o.quarter_turns = k.value
         return o
+
+    # ---- page normalisation
+    def normalize(self, inp, tile=64, polarity="auto", flatten=True, levels=True, info=False):
+        """ocrs_engine_normalize_page: the page with its background flattened, its levels stretched and its polarity made
+        dark-on-light, as a new resident page of the same size (ink -0.5, paper +0.5).  tile: a power of two, 16 .. 256;
+        polarity: "auto" (a per-tile vote), "keep" or "invert".  info=True: -> (page, {"dark", "vote", "white", "lo", "hi",
+        "counted"})."""
+        out = self.normalize_batch([inp], [{"tile": tile, "polarity": polarity, "flatten": flatten, "levels": levels}], info=info)
+        return (out[0][0], out[1][0]) if info else out[0]
+
+    def normalize_batch(self, inputs, params=None, info=False):
+        """ocrs_engine_normalize_pages: pages of any sizes, each with its own parameters (a dict of normalize's keywords, or
+        None for the default; one for all, or one per page), all passes for the whole batch on one stream.  info=True: ->
+        (pages, infos)."""
+        n = len(inputs)
+        if params is None or isinstance(params, dict):
+            params = [params] * n
+        if len(params) != n:
+            raise ValueError("normalize_batch: one parameter set per page")
+        pages = (C.c_void_p * n)(*[i._h for i in inputs])
+        ps = (_lib.NormalizeParams * n)(*[_normalize_struct(**(p or {})) for p in params])
+        out = (C.c_void_p * n)()
+        infos = (_lib.NormalizeInfo * n)()
+        check(lib().ocrs_engine_normalize_pages(self._h, pages, C.c_size_t(n), ps, out, infos if info else None))
+        made = [OcrInput(C.c_void_p(out[i])) for i in range(n)]
+        return (made, [infos[i].as_dict() for i in range(n)]) if info else made
 
     # ---- working resolution (DESIGN.md §7.3)
     def resize(self, inp, size, filter="auto"):
@@ -953,12 +1004,16 @@ class OcrEngine:
         return float(lib().ocrs_engine_detection_threshold(self._h))
 
     # ---- lib.rs:290-300
-    def get_text(self, inp, rectify=False, orientation=None, work_size=None):
+    def get_text(self, inp, rectify=False, orientation=None, work_size=None, normalize=None):
         """rectify=True: the same sequence (detect_words, find_text_lines, recognize_text) with rectified crops.
         orientation: None reads the page as given; an int turns it by that many quarter turns counter-clockwise first
         (rotate); "auto" by what detect_orientation finds.
         work_size=(h, w): the words are detected at that size of the (turned) page, lines and text are read from the page at
-        its full resolution."""
+        its full resolution.
+        normalize: None reads the page as given; True or a dict of normalize()'s keywords reads the normalised page
+        (DESIGN.md §7.4).  Applied first; the turn, the work size and the crops are then those of the normalised page."""
+        if normalize is not None and normalize is not False:
+            inp = self.normalize(inp, **({} if normalize is True else dict(normalize)))
         if orientation is not None:
             k = self.detect_orientation(inp).quarter_turns if orientation == "auto" else int(orientation)
             inp = self.rotate(inp, k)

@@ -85,11 +85,26 @@ DECLARED_SYMBOLS = [
     "ocrs_orientation_vote", "ocrs_engine_detect_orientation", "ocrs_engine_page_from_grey",
     "ocrs_engine_resize_page", "ocrs_engine_resize_pages", "ocrs_work_size", "ocrs_rescale_rects",
     "ocrs_engine_detect_words_at", "ocrs_engine_detect_words_batch_at",
+    "ocrs_normalize_params_default", "ocrs_normalize_params_check", "ocrs_engine_normalize_page", "ocrs_engine_normalize_pages",
 ]
 
 ABI_VERSION = 6   # include/ocrs_amd.h OCRS_ABI_VERSION
 TILE_OVERLAP_DEFAULT = 100   # include/ocrs_amd.h OCRS_TILE_OVERLAP_DEFAULT
 RESAMPLE_FILTERS = {"auto": 0, "bilinear": 1, "area": 2}   # include/ocrs_amd.h ocrs_resample_filter
+POLARITIES = {"auto": 0, "keep": 1, "invert": 2}   # include/ocrs_amd.h ocrs_polarity
+
+
+class NormalizeParams(C.Structure):   # include/ocrs_amd.h ocrs_normalize_params
+    _fields_ = [("tile", C.c_int32), ("polarity", C.c_int32), ("flatten", C.c_int32), ("levels", C.c_int32)]
+
+
+class NormalizeInfo(C.Structure):   # include/ocrs_amd.h ocrs_normalize_info
+    _fields_ = [("dark", C.c_int32), ("white", C.c_int32), ("lo", C.c_int32), ("hi", C.c_int32), ("vote", C.c_int64),
+                ("counted", C.c_uint64)]
+
+    def as_dict(self):
+        return {"dark": int(self.dark), "vote": int(self.vote), "white": int(self.white), "lo": int(self.lo), "hi": int(self.hi),
+                "counted": int(self.counted)}
 
 _lib = None
 

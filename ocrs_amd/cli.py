@@ -72,6 +72,14 @@ def main(argv=None):
     work.add_argument("--work-max-side", type=int, metavar="N",
                       help="as --work-scale with S = min(1, N / the page's longer side): the detector sees a page of at most N "
                            "pixels a side")
+    ap.add_argument("--normalize", action="store_true",
+                    help="normalise the page on the GPU before reading it: the background is flattened (shadows, uneven light), "
+                         "the levels are stretched (faint copies) and light text on a dark page is inverted; the JSON gains "
+                         "\"normalize\" (no reference counterpart; what a detector gains is uncalibrated: DESIGN.md 7.4)")
+    ap.add_argument("--normalize-tile", type=int, default=None, metavar="N",
+                    help="with --normalize: the tile the background is estimated over, a power of two from 16 to 256 (default 64)")
+    ap.add_argument("--normalize-polarity", choices=("auto", "keep", "invert"), default=None,
+                    help="with --normalize: auto (default) decides by a per-tile vote whether the page is light text on dark")
     ap.add_argument("-o", "--output")
     ap.add_argument("--debug", action="store_true")
     ap.add_argument("--text-map", action="store_true", help="write text-map.png (detect_text_pixels)")
@@ -86,6 +94,8 @@ def main(argv=None):
         ap.error("--confidence is only valid with -j/--json")
     if args.detection_confidence and not args.json:
         ap.error("--detection-confidence is only valid with -j/--json")
+    if (args.normalize_tile is not None or args.normalize_polarity is not None) and not args.normalize:
+        ap.error("--normalize-tile and --normalize-polarity are only valid with --normalize")
 
     from . import DecodeMethod, DimOrder, ImageSource, Model, OcrEngine, models, output
     from ._lib import OcrsError
@@ -113,6 +123,14 @@ def main(argv=None):
         img = load_image(args.image)
         shape_hw = img.shape[:2]
         inp = engine.prepare_input(ImageSource.from_tensor(img, DimOrder.Hwc))
+    norm_info = None
+    if args.normalize:   # from here on the normalised page is the page; coordinates do not move
+        inp, norm_info = engine.normalize(inp, tile=64 if args.normalize_tile is None else args.normalize_tile,
+                                          polarity=args.normalize_polarity or "auto", info=True)
+        if args.debug:
+            print("Normalize: %s page (vote %d), white bin %d, levels %d .. %d, %d pixels counted"
+                  % ("dark" if norm_info["dark"] else "light", norm_info["vote"], norm_info["white"], norm_info["lo"], norm_info["hi"],
+                     norm_info["counted"]))
     turns = None
     if args.orientation is not None:   # from here on the turned page is the page; results are mapped back before output
         if args.orientation == "auto":
@@ -161,7 +179,7 @@ def main(argv=None):
             word_boxes = [[(unrotate_rects([r], tuple(shape_hw), turns)[0], s, n) for r, s, n in boxes] for boxes in word_boxes]
     if args.json:
         content = output.format_json_output(args.image, tuple(shape_hw), texts, confidence=args.confidence, word_boxes=word_boxes,
-                                            orientation=None if turns is None else 90 * turns)
+                                            orientation=None if turns is None else 90 * turns, normalize=norm_info)
     else:
         content = output.format_text_output(texts)
     if args.output:

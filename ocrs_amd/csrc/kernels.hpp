@@ -332,6 +332,39 @@ int64_t resample_blocks(int dh, int dw);   // blocks an output of this size take
 // Pages of any mix of sizes and filters in one launch; total_blocks = the sum of resample_blocks() over the pages.
 void resample_pages(const ResampleDesc* d_descs, int n_pages, int total_blocks, hipStream_t s);
 
+// ---- kernels_normalize.hip ---------------------------------
+struct NormInfo {        // what a page's normalisation found: the layout of ocrs_normalize_info
+    int32_t dark;        // 1: read as light text on a dark page and inverted
+    int32_t white;       // Wg: the white bin of the page's effective histogram; -1: no pixel counted
+    int32_t lo, hi;      // the bins of u that levels stretched between; -1, -1 with levels off
+    int64_t vote;        // the polarity vote; 0 unless polarity is auto
+    uint64_t counted;    // pixels that are not NaN
+};
+struct NormState {       // per page, zeroed before the first pass
+    unsigned long long hist_v[256];   // page histogram of clamp(v + 0.5) (pass 1)
+    unsigned long long hist_u[256];   // page histogram of u (pass 3)
+    long long vote;                   // pass 1
+    NormInfo info;                    // passes 2 and 4
+};
+struct NormDesc {        // one page to normalise: dst [h, w] from src [h, w]
+    const float* src;
+    float* dst;          // never overlaps src
+    NormState* state;
+    uint32_t* tiles;     // [th, tw] what pass 1 keeps of a tile's histogram: pct(3,4) as it is | pct(3,4) read mirrored << 8 |
+                         // (the tile counted a pixel) << 16
+    uint8_t* grid;       // [th, tw] level bins (pass 2)
+    int32_t h, w;        // each 1 .. 65535
+    int32_t tshift;      // log2 of the tile size, 4 .. 8
+    int32_t th, tw;      // ceil(h / T), ceil(w / T)
+    int32_t block0;      // first block of this page: the sum of th * tw of the pages before it
+    int32_t polarity;    // 0 auto, 1 keep, 2 invert
+    int32_t flatten, levels;
+    int32_t vec;         // w % 4 == 0 and both buffers 16-byte aligned, so 16-byte accesses are safe
+};
+// Pages of any mix of sizes and parameters, five launches on `s`; total_blocks = the sum of th * tw over the pages.  The
+// states must be zero when the first launch starts.  d_info[n_pages] receives each page's NormInfo.
+void normalize_pages(const NormDesc* d_descs, int n_pages, int total_blocks, NormInfo* d_info, hipStream_t s);
+
 // kernels_peaks.hip
 void measure_peaks(double* mfma_tflops, double* copy_gbps);
 

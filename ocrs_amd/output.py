@@ -15,13 +15,15 @@ def rounded_vertex_coords(rect6):
     return [[_rround(x), _rround(y)] for x, y in rotated_rect_corners(rect6)]
 
 
-def ocr_json(input_path, input_hw, text_lines, confidence=False, word_boxes=None, orientation=None):
+def ocr_json(input_path, input_hw, text_lines, confidence=False, word_boxes=None, orientation=None, normalize=None):
     """output.rs:34-76.  text_lines: list of TextLine | None.  confidence (no reference counterpart): every line and word
     object also gets "confidence" (TextLine / TextWord.confidence; the lines must come from a scored recognize_text).
     word_boxes (no reference counterpart; indexed like text_lines): per line the detector's word boxes in reading order as
     (rect6, score, pixels); every line object then gets "word_boxes": [{"vertices", "confidence", "pixels"}].
     orientation (no reference counterpart): the degrees the page was turned counter-clockwise before it was read; the top
-    level then gets "orientation" (the boxes given here are already in the frame of the file)."""
+    level then gets "orientation" (the boxes given here are already in the frame of the file).
+    normalize (no reference counterpart): what OcrEngine.normalize(info=True) found on the page; the top level then gets
+    "normalize": {"counted", "dark", "hi", "lo", "vote", "white"}."""
     line_items = []
     for li, line in enumerate(text_lines):
         if line is None:
@@ -41,14 +43,16 @@ def ocr_json(input_path, input_hw, text_lines, confidence=False, word_boxes=None
     doc = {"url": input_path, "image_width": width, "image_height": height, "paragraphs": [{"lines": line_items}]}
     if orientation is not None:
         doc["orientation"] = int(orientation)
+    if normalize is not None:
+        doc["normalize"] = {k: int(normalize[k]) for k in ("counted", "dark", "hi", "lo", "vote", "white")}
     return doc
 
 
-def format_json_output(input_path, input_hw, text_lines, confidence=False, word_boxes=None, orientation=None):
+def format_json_output(input_path, input_hw, text_lines, confidence=False, word_boxes=None, orientation=None, normalize=None):
     """output.rs:98-101 (serde_json::to_string_pretty).  serde_json without `preserve_order` keeps `json!` maps in a
     BTreeMap, so the reference emits every object's keys in alphabetical order (ocrs-cli/test-data/
     format-json-expected.json: image_height, image_width, paragraphs, url / text, vertices, words): sort_keys."""
-    return json.dumps(ocr_json(input_path, input_hw, text_lines, confidence, word_boxes, orientation), indent=2, ensure_ascii=False,
+    return json.dumps(ocr_json(input_path, input_hw, text_lines, confidence, word_boxes, orientation, normalize), indent=2, ensure_ascii=False,
                       sort_keys=True)
 
 
