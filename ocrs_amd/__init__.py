@@ -312,6 +312,21 @@ def _take(ptr, n, dtype):
     return out
 
 
+def _take_rects(ptr, n):
+    """_take for n word rects -> float32 [n, 6]."""
+    return _take(ptr, n * 6, np.float32).reshape(-1, 6)
+
+
+def _page_array(inputs):
+    """The pages of OcrInputs as the `const ocrs_page* const*` argument of a batch call."""
+    return (C.c_void_p * len(inputs))(*[i._h for i in inputs])
+
+
+def _new_inputs(out, n):
+    """The n pages a batch call wrote into its `ocrs_page**` argument, each owned by a new OcrInput."""
+    return [OcrInput(C.c_void_p(out[i])) for i in range(n)]
+
+
 def _tile_overlap(tiled):
     """The `tiled` keyword of the detection calls -> None (untiled) or the overlap argument of the _tiled entry points:
     False / None: untiled; True: the default overlap (-1); an int: that many pixels (0 is a valid overlap)."""
@@ -476,50 +491,30 @@ def _work_hw(work_size):
     return (0, 0) if work_size is None else (int(work_size[0]), int(work_size[1]))
 
 
-def _detect_words_batch_at(handle, inputs, work_sizes, scores, tiled, work_filter):
-    """ocrs_engine_detect_words_batch_at -> rects per page [, score per page, pixels per page]."""
+def _detect_words_batch(name, handle, inputs, scores, tiled=False, work_sizes=None, work_filter="auto"):
+    """ocrs_{engine,group}_detect_words_batch[_at | _tiled | _scored] (name without the suffix; _at when work sizes are
+    given, else _tiled when tiled, else _scored when scored) -> rects per page [, score per page, pixels per page]."""
     n = len(inputs)
-    if len(work_sizes) != n:
+    if work_sizes is not None and len(work_sizes) != n:
         raise ValueError("detect_words_batch: one work size per page")
-    pages = (C.c_void_p * n)(*[i._h for i in inputs])
-    hw = (C.c_int * (2 * n))(*[v for s in work_sizes for v in _work_hw(s)])
+    pages = _page_array(inputs)
     rects = C.POINTER(C.c_float)()
     offs = (C.c_size_t * (n + 1))()
     overlap = _tile_overlap(tiled)
     sc, px = C.POINTER(C.c_float)(), C.POINTER(C.c_uint32)()
-    check(lib().ocrs_engine_detect_words_batch_at(handle, pages, C.c_size_t(n), hw, C.c_int(_lib.RESAMPLE_FILTERS[work_filter]),
-                                                  C.c_int(0 if overlap is None else 1), C.c_int(-1 if overlap is None else overlap),
-                                                  C.byref(rects), offs, C.byref(sc) if scores else None, C.byref(px) if scores else None))
-    total = offs[n]
-    flat = np.ctypeslib.as_array(rects, shape=(max(total, 1) * 6,))[: total * 6].reshape(-1, 6).copy()
-    lib().ocrs_buffer_free(rects)
-    words = [flat[offs[i]:offs[i + 1]] for i in range(n)]
-    if not scores:
-        return words
-    fs, fp = _take(sc, total, np.float32), _take(px, total, np.uint32)
-    return words, [fs[offs[i]:offs[i + 1]] for i in range(n)], [fp[offs[i]:offs[i + 1]] for i in range(n)]
-
-
-def _detect_words_batch(name, handle, inputs, scores, tiled=False):
-    """ocrs_{engine,group}_detect_words_batch[_scored | _tiled] (name without the suffix) -> rects per page [, score per
-    page, pixels per page]."""
-    n = len(inputs)
-    pages = (C.c_void_p * n)(*[i._h for i in inputs])
-    rects = C.POINTER(C.c_float)()
-    offs = (C.c_size_t * (n + 1))()
-    overlap = _tile_overlap(tiled)
-    if overlap is not None:
-        sc, px = C.POINTER(C.c_float)(), C.POINTER(C.c_uint32)()
-        check(getattr(lib(), name + "_tiled")(handle, pages, C.c_size_t(n), C.c_int(overlap), C.byref(rects), offs,
-                                              C.byref(sc) if scores else None, C.byref(px) if scores else None))
+    out = (C.byref(rects), offs, C.byref(sc) if scores else None, C.byref(px) if scores else None)
+    if work_sizes is not None:
+        hw = (C.c_int * (2 * n))(*[v for s in work_sizes for v in _work_hw(s)])
+        check(getattr(lib(), name + "_at")(handle, pages, C.c_size_t(n), hw, C.c_int(_lib.RESAMPLE_FILTERS[work_filter]),
+                                           C.c_int(0 if overlap is None else 1), C.c_int(-1 if overlap is None else overlap), *out))
+    elif overlap is not None:
+        check(getattr(lib(), name + "_tiled")(handle, pages, C.c_size_t(n), C.c_int(overlap), *out))
     elif scores:
-        sc, px = C.POINTER(C.c_float)(), C.POINTER(C.c_uint32)()
-        check(getattr(lib(), name + "_scored")(handle, pages, C.c_size_t(n), C.byref(rects), offs, C.byref(sc), C.byref(px)))
+        check(getattr(lib(), name + "_scored")(handle, pages, C.c_size_t(n), *out))
     else:
-        check(getattr(lib(), name)(handle, pages, C.c_size_t(n), C.byref(rects), offs))
+        check(getattr(lib(), name)(handle, pages, C.c_size_t(n), *out[:2]))
     total = offs[n]
-    flat = np.ctypeslib.as_array(rects, shape=(max(total, 1) * 6,))[: total * 6].reshape(-1, 6).copy()
-    lib().ocrs_buffer_free(rects)
+    flat = _take_rects(rects, total)
     words = [flat[offs[i]:offs[i + 1]] for i in range(n)]
     if not scores:
         return words
@@ -623,7 +618,7 @@ class OcrEngine:
         out = (C.c_void_p * n)()
         check(lib().ocrs_engine_prepare_input_batch(self._h, arr, C.c_size_t(n), 0 if dtype == np.uint8 else 1, order,
                                                     h, w, c, out))
-        return [OcrInput(C.c_void_p(out[i])) for i in range(n)]
+        return _new_inputs(out, n)
 
     def prepare_input_device(self, d_ptr, dtype, order, h, w, c):
         """Pixels already in HBM (a raw device pointer), e.g. from bench.py."""
@@ -652,11 +647,11 @@ class OcrEngine:
         n = len(inputs)
         if len(ks) != n:
             raise ValueError("rotate_batch: one k per page")
-        pages = (C.c_void_p * n)(*[i._h for i in inputs])
+        pages = _page_array(inputs)
         turns = (C.c_int * n)(*[int(k) for k in ks])
         out = (C.c_void_p * n)()
         check(lib().ocrs_engine_rotate_pages(self._h, pages, C.c_size_t(n), turns, out))
-        return [OcrInput(C.c_void_p(out[i])) for i in range(n)]
+        return _new_inputs(out, n)
 
     def detect_orientation(self, inp, max_lines=8):
         """ocrs_engine_detect_orientation -> Orientation: which quarter turn makes the page read (rotate(inp,
@@ -689,12 +684,12 @@ class OcrEngine:
             params = [params] * n
         if len(params) != n:
             raise ValueError("normalize_batch: one parameter set per page")
-        pages = (C.c_void_p * n)(*[i._h for i in inputs])
+        pages = _page_array(inputs)
         ps = (_lib.NormalizeParams * n)(*[_normalize_struct(**(p or {})) for p in params])
         out = (C.c_void_p * n)()
         infos = (_lib.NormalizeInfo * n)()
         check(lib().ocrs_engine_normalize_pages(self._h, pages, C.c_size_t(n), ps, out, infos if info else None))
-        made = [OcrInput(C.c_void_p(out[i])) for i in range(n)]
+        made = _new_inputs(out, n)
         return (made, [infos[i].as_dict() for i in range(n)]) if info else made
 
     # ---- working resolution
@@ -712,12 +707,12 @@ class OcrEngine:
             filters = [filters] * n
         if len(sizes) != n or len(filters) != n:
             raise ValueError("resize_batch: one size and one filter per page")
-        pages = (C.c_void_p * n)(*[i._h for i in inputs])
+        pages = _page_array(inputs)
         hw = (C.c_int * (2 * n))(*[int(v) for s in sizes for v in (s[0], s[1])])
         fl = (C.c_int * n)(*[_lib.RESAMPLE_FILTERS[f] for f in filters])
         out = (C.c_void_p * n)()
         check(lib().ocrs_engine_resize_pages(self._h, pages, C.c_size_t(n), hw, fl, out))
-        return [OcrInput(C.c_void_p(out[i])) for i in range(n)]
+        return _new_inputs(out, n)
 
     # ---- lib.rs:193-199
     def detect_words(self, inp, scores=False, tiled=False, work_size=None, work_filter="auto"):
@@ -729,7 +724,7 @@ class OcrEngine:
         work_filter, as resize) and the words come back in the page's own frame; scores and pixels are those of the work
         page.  work_size() makes one from a scale or a longest side."""
         if work_size is not None:
-            out = _detect_words_batch_at(self._h, [inp], [work_size], scores, tiled, work_filter)
+            out = self.detect_words_batch([inp], scores, tiled, [work_size], work_filter)
             return tuple(o[0] for o in out) if scores else out[0]
         rects = C.POINTER(C.c_float)()
         n = C.c_size_t(0)
@@ -743,8 +738,7 @@ class OcrEngine:
             check(lib().ocrs_engine_detect_words_scored(self._h, inp._h, C.byref(rects), C.byref(n), C.byref(sc), C.byref(px)))
         else:
             check(lib().ocrs_engine_detect_words(self._h, inp._h, C.byref(rects), C.byref(n)))
-        out = np.ctypeslib.as_array(rects, shape=(max(n.value, 1) * 6,))[: n.value * 6].reshape(-1, 6).copy()
-        lib().ocrs_buffer_free(rects)
+        out = _take_rects(rects, n.value)
         if not scores:
             return out
         return out, _take(sc, n.value, np.float32), _take(px, n.value, np.uint32)
@@ -752,9 +746,7 @@ class OcrEngine:
     def detect_words_batch(self, inputs, scores=False, tiled=False, work_sizes=None, work_filter="auto"):
         """scores=True: -> (words per page, score per page, pixels per page).  tiled: as detect_words.  work_sizes: one
         (h, w) or None (the page's own size) per page, as detect_words' work_size; resampled in one launch."""
-        if work_sizes is not None:
-            return _detect_words_batch_at(self._h, inputs, work_sizes, scores, tiled, work_filter)
-        return _detect_words_batch("ocrs_engine_detect_words_batch", self._h, inputs, scores, tiled)
+        return _detect_words_batch("ocrs_engine_detect_words_batch", self._h, inputs, scores, tiled, work_sizes, work_filter)
 
     # ---- lib.rs:207-213
     def detect_text_pixels(self, inp, tiled=False):
@@ -783,8 +775,7 @@ class OcrEngine:
         else:
             check(lib().ocrs_engine_find_text_lines(*args))
         offs = [lo[i] for i in range(nl.value + 1)]
-        flat = np.ctypeslib.as_array(lr, shape=(max(len(a), 1) * 6,))[: len(a) * 6].reshape(-1, 6).copy()
-        lib().ocrs_buffer_free(lr)
+        flat = _take_rects(lr, len(a))
         lib().ocrs_buffer_free(lo)
         lines = [flat[offs[i]:offs[i + 1]] for i in range(nl.value)]
         if not index:
@@ -813,8 +804,8 @@ class OcrEngine:
         poffs = np.ctypeslib.as_array(po, shape=(n + 1,)).astype(np.uintp)
         nl = int(poffs[n])
         loffs = np.ctypeslib.as_array(lo, shape=(nl + 1,)).astype(np.uintp)
-        rects = np.ctypeslib.as_array(lr, shape=(max(len(allw), 1) * 6,))[: len(allw) * 6].reshape(-1, 6).copy()
-        for p in (lr, lo, po):
+        rects = _take_rects(lr, len(allw))
+        for p in (lo, po):
             lib().ocrs_buffer_free(p)
         if index:
             return rects, loffs, poffs, _take(wi, len(allw), np.uintp).astype(np.int64)
@@ -826,7 +817,7 @@ class OcrEngine:
         scores=True: returns (chars, char_offsets, char_logp float32 [len(chars)], line_score float64 [lines]), every
         line scored, those without text included.  rectify=True: rectified crops."""
         n = len(inputs)
-        pages = (C.c_void_p * n)(*[i._h for i in inputs])
+        pages = _page_array(inputs)
         rects = np.ascontiguousarray(rects, np.float32)
         lo = np.ascontiguousarray(line_offsets, np.uintp)
         po = np.ascontiguousarray(page_line_offsets, np.uintp)
@@ -890,7 +881,7 @@ class OcrEngine:
 
     def recognize_text_batch(self, inputs, lines_per_page, scores=False, rectify=False):
         n = len(inputs)
-        pages = (C.c_void_p * n)(*[i._h for i in inputs])
+        pages = _page_array(inputs)
         all_lines = [l for lines in lines_per_page for l in lines]
         plo = [0]
         for lines in lines_per_page:
@@ -1017,12 +1008,9 @@ class OcrEngine:
         if orientation is not None:
             k = self.detect_orientation(inp).quarter_turns if orientation == "auto" else int(orientation)
             inp = self.rotate(inp, k)
-        if work_size is not None:
+        if work_size is not None or rectify:
             lines = self.find_text_lines(inp, self.detect_words(inp, work_size=work_size))
             return "\n".join(str(t) for t in self.recognize_text(inp, lines, rectify=rectify) if t is not None)
-        if rectify:
-            lines = self.find_text_lines(inp, self.detect_words(inp))
-            return "\n".join(str(t) for t in self.recognize_text(inp, lines, rectify=True) if t is not None)
         txt = C.c_char_p()
         check(lib().ocrs_engine_get_text(self._h, inp._h, C.byref(txt)))
         s = txt.value.decode("utf-8")
@@ -1169,7 +1157,7 @@ class EngineGroup:
         ptrs = (C.c_void_p * n)(*[a.ctypes.data for a in arrs])
         out = (C.c_void_p * n)()
         check(lib().ocrs_group_prepare_input_batch(self._h, ptrs, C.c_size_t(n), 0 if a0.dtype == np.uint8 else 1, order, h, w, c, out))
-        return [OcrInput(C.c_void_p(out[i])) for i in range(n)]
+        return _new_inputs(out, n)
 
     def prepare_input_device_batch(self, d_ptrs, dtype, order, h, w, c):
         n = len(d_ptrs)
@@ -1177,7 +1165,7 @@ class EngineGroup:
         out = (C.c_void_p * n)()
         check(lib().ocrs_group_prepare_input_device_batch(self._h, ptrs, C.c_size_t(n), 0 if dtype == np.uint8 else 1, order,
                                                           h, w, c, out))
-        return [OcrInput(C.c_void_p(out[i])) for i in range(n)]
+        return _new_inputs(out, n)
 
     def detect_words_batch(self, inputs, scores=False, tiled=False):
         """scores=True: -> (words per page, score per page, pixels per page), as OcrEngine.detect_words_batch; tiled likewise."""
@@ -1189,7 +1177,7 @@ class EngineGroup:
     def recognize_text_batch_raw(self, inputs, rects, line_offsets, page_line_offsets, rectify=False):
         """rectify=True: through ocrs_group_recognize_text_batch_rectified."""
         n = len(inputs)
-        pages = (C.c_void_p * n)(*[i._h for i in inputs])
+        pages = _page_array(inputs)
         rects = np.ascontiguousarray(rects, np.float32)
         lo = np.ascontiguousarray(line_offsets, np.uintp)
         po = np.ascontiguousarray(page_line_offsets, np.uintp)

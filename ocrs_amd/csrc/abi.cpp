@@ -11,6 +11,7 @@
 #include "host_pool.hpp"
 #include "jpeg.hpp"
 #include "kernels.hpp"
+#include "page_ops.hpp"
 
 using namespace ocrs;
 using namespace ocrs::geom;
@@ -152,20 +153,19 @@ ocrs_status ocrs_ctc_beam_search_scored(const float* logp, int t, int c, uint32_
 
 uint32_t ocrs_abi_version(void) { return OCRS_ABI_VERSION; }
 
+static void check_option_set(int r, const char* name, long value) {   // what set_option (common.hpp) returned
+    if (r == 1) fail(OCRS_ERR_INVALID_ARGUMENT, "unknown option '%s'", name ? name : "(null)");
+    if (r == 2) fail(OCRS_ERR_INVALID_ARGUMENT, "option '%s': value %ld is out of range", name, value);
+}
+
 ocrs_status ocrs_set_option(const char* name, long value) {
-    return guarded([&] {
-        const int r = set_option(name, value);
-        if (r == 1) fail(OCRS_ERR_INVALID_ARGUMENT, "unknown option '%s'", name ? name : "(null)");
-        if (r == 2) fail(OCRS_ERR_INVALID_ARGUMENT, "option '%s': value %ld is out of range", name, value);
-    });
+    return guarded([&] { check_option_set(set_option(name, value), name, value); });
 }
 
 ocrs_status ocrs_engine_set_option(ocrs_engine* e, const char* name, long value) {
     return guarded([&] {
         if (!e) fail(OCRS_ERR_INVALID_ARGUMENT, "null argument");
-        const int r = set_option(e->tuning, name, value);
-        if (r == 1) fail(OCRS_ERR_INVALID_ARGUMENT, "unknown option '%s'", name ? name : "(null)");
-        if (r == 2) fail(OCRS_ERR_INVALID_ARGUMENT, "option '%s': value %ld is out of range", name, value);
+        check_option_set(set_option(e->tuning, name, value), name, value);
     });
 }
 
@@ -508,14 +508,11 @@ ocrs_status ocrs_jpeg_coefficients(const void* jpeg, size_t len, int32_t geom[28
         }
         memcpy(quant, c.quant, sizeof c.quant);
         std::vector<int16_t> dense(c.nblocks() * 64, 0);
-        for (size_t b = 0; b < c.nblocks(); b++) {
-            uint32_t at = c.offset[b];
+        for (size_t b = 0; b < c.nblocks(); b++)
             for (int p = 0; p < 64; p++) {
                 const int z = ocrs::jpeg::Coefficients::kZigzagOfNatural[p];
                 if ((c.mask[b] >> z) & 1) dense[b * 64 + p] = c.values[c.offset[b] + __builtin_popcountll(c.mask[b] & ((uint64_t(1) << z) - 1))];
             }
-            (void)at;
-        }
         *coef = dup_buffer(dense);
         *n_blocks = c.nblocks();
     });
@@ -542,10 +539,7 @@ ocrs_status ocrs_engine_page_from_grey(const ocrs_engine* e, const float* grey_h
     return guarded_engine(e, [&] {
         if (!e || !grey_hw || !out) fail(OCRS_ERR_INVALID_ARGUMENT, "null argument");
         if (height <= 0 || width <= 0) fail(OCRS_ERR_INVALID_ARGUMENT, "image has no pixels");
-        auto page = std::make_unique<ocrs_page>();
-        page->h = height;
-        page->w = width;
-        page->grey = DevBuf((size_t)height * width * sizeof(float));
+        auto page = new_page(height, width);
         OCRS_HIP(hipMemcpy(page->grey.p, grey_hw, page->grey.bytes, hipMemcpyHostToDevice));
         *out = page.release();
     });
@@ -562,26 +556,7 @@ ocrs_status detect_words_batch(const ocrs_engine* e, const ocrs_page* const* pag
         std::vector<std::vector<RotatedRect>> rr;
         DetScores sc;
         e->detect(pages, n_pages, &rr, nullptr, scored ? &sc : nullptr, tile_overlap);
-        std::vector<float> flat, fscore;
-        std::vector<uint32_t> fpixels;
-        offsets[0] = 0;
-        for (size_t i = 0; i < n_pages; i++) {
-            for (const RotatedRect& r : rr[i]) {
-                float a[6];
-                r.to_array(a);
-                flat.insert(flat.end(), a, a + 6);
-            }
-            if (scored) {
-                fscore.insert(fscore.end(), sc.score[i].begin(), sc.score[i].end());
-                fpixels.insert(fpixels.end(), sc.pixels[i].begin(), sc.pixels[i].end());
-            }
-            offsets[i + 1] = flat.size() / 6;
-        }
-        if (scored) {
-            *score = dup_buffer(fscore);
-            *pixels = dup_buffer(fpixels);
-        }
-        *rects = dup_buffer(flat);
+        pack_words(rr, scored ? &sc : nullptr, rects, offsets, score, pixels);
     });
 }
 
@@ -627,7 +602,7 @@ ocrs_status ocrs_detection_tile_plan(int page_h, int page_w, int model_h, int mo
         if (!ny || !nx || !origin_y || !bound_y || !origin_x || !bound_x) fail(OCRS_ERR_INVALID_ARGUMENT, "null argument");
         if (page_h <= 0 || page_w <= 0 || model_h <= 0 || model_w <= 0)
             fail(OCRS_ERR_INVALID_ARGUMENT, "tile plan: page %d x %d, model input %d x %d", page_h, page_w, model_h, model_w);
-        const int v = overlap < 0 ? OCRS_TILE_OVERLAP_DEFAULT : overlap;
+        const int v = tile_overlap_arg(overlap);
         if (v > std::min(model_h, model_w) / 2)
             fail(OCRS_ERR_INVALID_ARGUMENT, "tile overlap %d: at most half the model input's shorter side (%d)", v, std::min(model_h, model_w) / 2);
         const TileAxisPlan py = tile_axis_plan(page_h, model_h, v), px = tile_axis_plan(page_w, model_w, v);
@@ -643,8 +618,7 @@ ocrs_status ocrs_detection_tile_plan(int page_h, int page_w, int model_h, int mo
 ocrs_status ocrs_engine_detect_words_batch_tiled(const ocrs_engine* e, const ocrs_page* const* pages, size_t n_pages, int overlap,
                                                  float** rects, size_t* offsets, float** score, uint32_t** pixels) {
     if (!score != !pixels) return guarded([&] { fail(OCRS_ERR_INVALID_ARGUMENT, "score and pixels come together"); });
-    return detect_words_batch(e, pages, n_pages, rects, offsets, score != nullptr, score, pixels,
-                              overlap < 0 ? OCRS_TILE_OVERLAP_DEFAULT : overlap);
+    return detect_words_batch(e, pages, n_pages, rects, offsets, score != nullptr, score, pixels, tile_overlap_arg(overlap));
 }
 
 ocrs_status ocrs_engine_detect_words_tiled(const ocrs_engine* e, const ocrs_page* page, int overlap, float** rects, size_t* n,
@@ -659,7 +633,7 @@ ocrs_status ocrs_engine_detect_text_pixels_tiled(const ocrs_engine* e, const ocr
     return guarded_engine(e, [&] {
         if (!e || !page || !out_hw) fail(OCRS_ERR_INVALID_ARGUMENT, "null argument");
         check_pages_on(e, &page, 1);
-        e->detect(&page, 1, nullptr, out_hw, nullptr, overlap < 0 ? OCRS_TILE_OVERLAP_DEFAULT : overlap);
+        e->detect(&page, 1, nullptr, out_hw, nullptr, tile_overlap_arg(overlap));
     });
 }
 
@@ -673,18 +647,12 @@ ocrs_status find_text_lines_one(const float* word_rects, size_t n_words, float**
     return guarded([&] {
         if (!line_rects || !line_offsets || !n_lines || (n_words && !word_rects) || (indexed && !word_index))
             fail(OCRS_ERR_INVALID_ARGUMENT, "null argument");
-        std::vector<RotatedRect> words(n_words);
-        for (size_t i = 0; i < n_words; i++) words[i] = RotatedRect::from_array(word_rects + 6 * i);
         std::vector<std::vector<size_t>> index;
-        auto lines = find_text_lines(words, indexed ? &index : nullptr);
+        auto lines = find_text_lines(unpack_words(word_rects, n_words), indexed ? &index : nullptr);
         std::vector<float> flat;
         std::vector<size_t> offs{0}, widx;
         for (size_t li = 0; li < lines.size(); li++) {
-            for (const RotatedRect& r : lines[li]) {
-                float a[6];
-                r.to_array(a);
-                flat.insert(flat.end(), a, a + 6);
-            }
+            append_rects(flat, lines[li]);
             if (indexed) widx.insert(widx.end(), index[li].begin(), index[li].end());
             offs.push_back(flat.size() / 6);
         }
@@ -740,9 +708,7 @@ ocrs_status find_text_lines_many(const ocrs_engine* e, size_t n_pages, const flo
         std::vector<std::string> errors(n_pages);
         auto work = [&](size_t p) {
             try {
-                std::vector<RotatedRect> words;
-                for (size_t k = word_offsets[p]; k < word_offsets[p + 1]; k++)
-                    words.push_back(RotatedRect::from_array(word_rects + 6 * k));
+                const std::vector<RotatedRect> words = unpack_words(word_rects + 6 * word_offsets[p], word_offsets[p + 1] - word_offsets[p]);
                 per_page[p] = find_text_lines(words, indexed ? &per_page_index[p] : nullptr);
             } catch (const std::exception& ex) {
                 errors[p] = ex.what();
@@ -759,11 +725,7 @@ ocrs_status find_text_lines_many(const ocrs_engine* e, size_t n_pages, const flo
         std::vector<size_t> loffs{0}, poffs{0}, widx;
         for (size_t p = 0; p < n_pages; p++) {
             for (size_t li = 0; li < per_page[p].size(); li++) {
-                for (const RotatedRect& r : per_page[p][li]) {
-                    float a[6];
-                    r.to_array(a);
-                    flat.insert(flat.end(), a, a + 6);
-                }
+                append_rects(flat, per_page[p][li]);
                 if (indexed) widx.insert(widx.end(), per_page_index[p][li].begin(), per_page_index[p][li].end());
                 loffs.push_back(flat.size() / 6);
             }
@@ -986,23 +948,30 @@ ocrs_status ocrs_rotated_rect_corners(const float rect6[6], float out8[8]) {
     });
 }
 
-ocrs_status ocrs_engine_prepare_recognition_input(const ocrs_engine* e, const ocrs_page* page, const float* line,
-                                                  size_t n_words, float** out, int* height, int* width) {
+// ocrs_engine_prepare_recognition_input[_rectified]
+static ocrs_status prepare_recognition_input(const ocrs_engine* e, const ocrs_page* page, const float* line, size_t n_words, float** out,
+                                             int* height, int* width, bool rectify) {
     return guarded_engine(e, [&] {
         if (!e || !page || !line || !out || !height || !width) fail(OCRS_ERR_INVALID_ARGUMENT, "null argument");
         check_pages_on(e, &page, 1);
         if (!e->recognition) fail(OCRS_ERR_MODEL_NOT_LOADED, "Recognition model not loaded");
-        std::vector<RotatedRect> words(n_words);
-        for (size_t i = 0; i < n_words; i++) words[i] = RotatedRect::from_array(line + 6 * i);
-        const RecLine ln = e->make_rec_line(words, 0, 0);
+        const RecLine ln = e->make_rec_line(unpack_words(line, n_words), 0, 0, rectify);
         const int rec_h = (int)e->rec_input_height();
-        const int rw = (int)ln.resized_width;
+        // a rectified line is cropped at its group's width (the kernel's rows are even) and cut to its own afterwards
+        const int rw = (int)ln.resized_width, cw = rectify ? (int)ln.group_width : rw;
         std::vector<float> host((size_t)rec_h * rw);
         if (rw > 0) {
             Workspace ws;
-            const float* d_out = stage_line_crops(ws, nullptr, &page, 1, {CropLine{&ln, (uint32_t)rw, 0}}, rec_h, (int64_t)rec_h * rw);
-            ws.download(host.data(), d_out, host.size() * 4);
-            ws.sync();
+            const float* d_out = stage_line_crops(ws, nullptr, &page, 1, {CropLine{&ln, (uint32_t)cw, 0}}, rec_h, (int64_t)rec_h * cw);
+            if (cw == rw) {
+                ws.download(host.data(), d_out, host.size() * 4);
+                ws.sync();
+            } else {
+                std::vector<float> full((size_t)rec_h * cw);
+                ws.download(full.data(), d_out, full.size() * 4);
+                ws.sync();
+                for (int y = 0; y < rec_h; y++) std::copy_n(&full[(size_t)y * cw], rw, &host[(size_t)y * rw]);
+            }
         }
         *out = dup_buffer(host);
         *height = rec_h;
@@ -1010,30 +979,14 @@ ocrs_status ocrs_engine_prepare_recognition_input(const ocrs_engine* e, const oc
     });
 }
 
+ocrs_status ocrs_engine_prepare_recognition_input(const ocrs_engine* e, const ocrs_page* page, const float* line,
+                                                  size_t n_words, float** out, int* height, int* width) {
+    return prepare_recognition_input(e, page, line, n_words, out, height, width, false);
+}
+
 ocrs_status ocrs_engine_prepare_recognition_input_rectified(const ocrs_engine* e, const ocrs_page* page, const float* line,
                                                             size_t n_words, float** out, int* height, int* width) {
-    return guarded_engine(e, [&] {
-        if (!e || !page || !line || !out || !height || !width) fail(OCRS_ERR_INVALID_ARGUMENT, "null argument");
-        check_pages_on(e, &page, 1);
-        if (!e->recognition) fail(OCRS_ERR_MODEL_NOT_LOADED, "Recognition model not loaded");
-        std::vector<RotatedRect> words(n_words);
-        for (size_t i = 0; i < n_words; i++) words[i] = RotatedRect::from_array(line + 6 * i);
-        const RecLine ln = e->make_rec_line(words, 0, 0, true);
-        const int rec_h = (int)e->rec_input_height();
-        const int rw = (int)ln.resized_width, gw = (int)ln.group_width;   // cropped at its group's width: the kernel's rows are even
-        std::vector<float> host((size_t)rec_h * rw);
-        if (rw > 0) {
-            Workspace ws;
-            const float* d_out = stage_line_crops(ws, nullptr, &page, 1, {CropLine{&ln, (uint32_t)gw, 0}}, rec_h, (int64_t)rec_h * gw);
-            std::vector<float> full((size_t)rec_h * gw);
-            ws.download(full.data(), d_out, full.size() * 4);
-            ws.sync();
-            for (int y = 0; y < rec_h; y++) std::copy_n(&full[(size_t)y * gw], rw, &host[(size_t)y * rw]);
-        }
-        *out = dup_buffer(host);
-        *height = rec_h;
-        *width = rw;
-    });
+    return prepare_recognition_input(e, page, line, n_words, out, height, width, true);
 }
 
 ocrs_status ocrs_engine_get_text(const ocrs_engine* e, const ocrs_page* page, char** text) {

@@ -2,6 +2,7 @@
 #include "abi_util.hpp"
 
 #include "kernels.hpp"
+#include "page_ops.hpp"
 
 namespace ocrs {
 namespace abi {
@@ -49,20 +50,13 @@ static const char kDefaultAlphabet[] =
 
 std::vector<std::vector<RotatedRect>> unpack_lines(const float* rects, const size_t* offsets, size_t first, size_t last) {
     std::vector<std::vector<RotatedRect>> lines;
-    for (size_t i = first; i < last; i++) {
-        std::vector<RotatedRect> words;
-        for (size_t k = offsets[i]; k < offsets[i + 1]; k++) words.push_back(RotatedRect::from_array(rects + 6 * k));
-        lines.push_back(std::move(words));
-    }
+    for (size_t i = first; i < last; i++) lines.push_back(unpack_words(rects + 6 * offsets[i], offsets[i + 1] - offsets[i]));
     return lines;
 }
 
 ocrs_page* make_page(const void* d_pixels, ocrs_pixel_type type, ocrs_dim_order order, int height, int width, int channels,
                      hipStream_t st, StageTimers* T) {
-    auto page = std::make_unique<ocrs_page>();
-    page->h = height;
-    page->w = width;
-    page->grey = DevBuf((size_t)height * width * sizeof(float));
+    auto page = new_page(height, width);
     {
         StageScope sc(T, ST_PREPARE, st);
         k::prepare_image(d_pixels, type == OCRS_U8, order == OCRS_HWC, height, width, channels, page->grey.as<float>(), st);

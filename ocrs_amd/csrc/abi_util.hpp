@@ -58,6 +58,53 @@ T* dup_buffer(const std::vector<T>& v) {
     return p;
 }
 
+// ---- word rects across the ABI: six floats per rect (RotatedRect::to_array), pages told apart by offsets
+inline void append_rects(std::vector<float>& flat, const std::vector<geom::RotatedRect>& rects) {
+    for (const geom::RotatedRect& r : rects) {
+        float a[6];
+        r.to_array(a);
+        flat.insert(flat.end(), a, a + 6);
+    }
+}
+
+inline std::vector<geom::RotatedRect> unpack_words(const float* rects6, size_t n) {
+    std::vector<geom::RotatedRect> words(n);
+    for (size_t i = 0; i < n; i++) words[i] = geom::RotatedRect::from_array(rects6 + 6 * i);
+    return words;
+}
+
+// The outputs of a detect_words_batch call from what detection found: rects / offsets[n + 1], and score / pixels when `sc` is
+// given.  per_page(i, rects6, n), if any, may rewrite page i's freshly appended rects in place.
+template <class PerPage>
+void pack_words(const std::vector<std::vector<geom::RotatedRect>>& rr, const DetScores* sc, float** rects, size_t* offsets,
+                float** score, uint32_t** pixels, PerPage&& per_page) {
+    std::vector<float> flat, fscore;
+    std::vector<uint32_t> fpixels;
+    offsets[0] = 0;
+    for (size_t i = 0; i < rr.size(); i++) {
+        const size_t first = flat.size();
+        append_rects(flat, rr[i]);
+        per_page(i, flat.data() + first, rr[i].size());
+        if (sc) {
+            fscore.insert(fscore.end(), sc->score[i].begin(), sc->score[i].end());
+            fpixels.insert(fpixels.end(), sc->pixels[i].begin(), sc->pixels[i].end());
+        }
+        offsets[i + 1] = flat.size() / 6;
+    }
+    if (sc) {
+        *score = dup_buffer(fscore);
+        *pixels = dup_buffer(fpixels);
+    }
+    *rects = dup_buffer(flat);
+}
+inline void pack_words(const std::vector<std::vector<geom::RotatedRect>>& rr, const DetScores* sc, float** rects, size_t* offsets,
+                       float** score, uint32_t** pixels) {
+    pack_words(rr, sc, rects, offsets, score, pixels, [](size_t, float*, size_t) {});
+}
+
+// the overlap argument of the _tiled entry points: negative = the default
+inline int tile_overlap_arg(int overlap) { return overlap < 0 ? OCRS_TILE_OVERLAP_DEFAULT : overlap; }
+
 void check_pages_on(const ocrs_engine* e, const ocrs_page* const* pages, size_t n);
 std::u32string decode_utf8(const char* s);
 void append_utf8(std::string& s, uint32_t c);

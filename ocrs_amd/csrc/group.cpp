@@ -31,6 +31,7 @@
 #include "host_pool.hpp"
 #include "numa.hpp"
 #include "kernels.hpp"
+#include "page_ops.hpp"
 
 using namespace ocrs;
 using namespace ocrs::abi;
@@ -594,10 +595,8 @@ static void group_prepare(ocrs_engine_group* g, const void* const* pixels, size_
         const ocrs_engine* e = g->members[m].engine.get();
         if (g->replay_mode == 2) {   // no upload, no conversion: a page object of the right size on the member's device, after the share's time
             for (size_t i : of_member[m]) {
-                auto page = std::make_unique<ocrs_page>();
-                page->h = height; page->w = width; page->source = pixels[i];
-                page->grey = DevBuf((size_t)height * width * sizeof(float));
-                made[i] = std::move(page);
+                made[i] = new_page(height, width);
+                made[i]->source = pixels[i];
             }
             std::this_thread::sleep_for(std::chrono::duration<double>(g->replay_s[0]));
             return;
@@ -667,14 +666,13 @@ static ocrs_status group_detect_words_batch(ocrs_engine_group* g, const ocrs_pag
                 }
             }
             auto& pl = payloads[m];
+            std::vector<float> flat;
             for (size_t j = 0; j < rr.size(); j++) {
                 const uint64_t cnt = rr[j].size();
                 append_bytes(pl, &cnt, 1);
-                for (const RotatedRect& r : rr[j]) {
-                    float a[6];
-                    r.to_array(a);
-                    append_bytes(pl, a, 6);
-                }
+                flat.clear();
+                append_rects(flat, rr[j]);
+                append_bytes(pl, flat.data(), flat.size());
                 if (scored) {
                     append_bytes(pl, sc.score[j].data(), cnt);
                     append_bytes(pl, sc.pixels[j].data(), cnt);
@@ -726,8 +724,7 @@ ocrs_status ocrs_group_detect_words_batch_scored(ocrs_engine_group* g, const ocr
 ocrs_status ocrs_group_detect_words_batch_tiled(ocrs_engine_group* g, const ocrs_page* const* pages, size_t n_pages, int overlap,
                                                 float** rects, size_t* offsets, float** score, uint32_t** pixels) {
     if (!score != !pixels) return guarded([&] { fail(OCRS_ERR_INVALID_ARGUMENT, "score and pixels come together"); });
-    return group_detect_words_batch(g, pages, n_pages, rects, offsets, score != nullptr, score, pixels,
-                                    overlap < 0 ? OCRS_TILE_OVERLAP_DEFAULT : overlap);
+    return group_detect_words_batch(g, pages, n_pages, rects, offsets, score != nullptr, score, pixels, tile_overlap_arg(overlap));
 }
 
 static ocrs_status group_recognize_text_batch(ocrs_engine_group* g, const ocrs_page* const* pages, size_t n_pages,

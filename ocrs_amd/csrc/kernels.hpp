@@ -310,7 +310,7 @@ struct RotateDesc {      // one page to turn: dst = np.rot90(src, k)
     uint32_t* dst;       // [h, w] for k even, [w, h] for k odd; never overlaps src
     int32_t h, w;        // of the source
     int32_t k;           // quarter turns counter-clockwise, 0 .. 3
-    int32_t tile0;       // first block of this page: the sum of rotate_tiles() of the pages before it
+    int32_t block0;      // first block of this page: the sum of rotate_tiles() of the pages before it
     int32_t vec;         // k even only: w % 4 == 0 and both buffers 16-byte aligned, so 16-byte accesses are safe
     int32_t pad_;
 };

@@ -31,6 +31,7 @@
 // with a trip count that is uniform in the block, so that the shuffles and ballots see all 64 lanes; pixels outside the
 // page carry bin -1.  The barriers are at the top level of each kernel and every thread of every block reaches them.
 #include "bilinear.hpp"
+#include "find_desc.hpp"
 #include "kernels.hpp"
 
 namespace ocrs {
@@ -52,16 +53,6 @@ __device__ __forceinline__ uint32_t tile_word(int white_light, int white_dark, b
 }
 typedef float float4v __attribute__((ext_vector_type(4)));
 typedef __attribute__((address_space(1))) float4v gquad;
-
-__device__ __forceinline__ int find_page(const NormDesc* __restrict__ descs, int n_pages, int b) {
-    int lo = 0, hi = n_pages - 1;   // the last page whose first block is <= b
-    while (lo < hi) {
-        const int mid = (lo + hi + 1) >> 1;
-        if (descs[mid].block0 <= b) lo = mid;
-        else hi = mid - 1;
-    }
-    return lo;
-}
 
 __device__ __forceinline__ float clamp01(float a) { return a < 0.0f ? 0.0f : (a > 1.0f ? 1.0f : a); }   // NaN stays
 
@@ -202,7 +193,7 @@ norm_tiles_kernel(const NormDesc* __restrict__ descs, int n_pages) {
     __shared__ uint32_t wave_sum[NORM_WAVES];
     __shared__ int found[5];   // p5, p50, p95, white as it is, white mirrored
     const int b = (int)blockIdx.x, tid = (int)threadIdx.x;
-    const NormDesc d = descs[find_page(descs, n_pages, b)];
+    const NormDesc d = descs[find_desc(descs, n_pages, b)];
     const int t = b - d.block0;
 #pragma unroll
     for (int i = 0; i < NORM_WAVES; i++) hist[i][tid] = 0u;
@@ -288,7 +279,7 @@ __global__ void __launch_bounds__(NORM_THREADS)
 norm_hist_kernel(const NormDesc* __restrict__ descs, int n_pages) {
     __shared__ uint32_t hist[NORM_WAVES][256];
     const int b = (int)blockIdx.x, tid = (int)threadIdx.x;
-    const NormDesc d = descs[find_page(descs, n_pages, b)];
+    const NormDesc d = descs[find_desc(descs, n_pages, b)];
     gstate* __restrict__ st = (gstate*)(uintptr_t)d.state;
 #pragma unroll
     for (int i = 0; i < NORM_WAVES; i++) hist[i][tid] = 0u;
@@ -344,7 +335,7 @@ __device__ __forceinline__ float norm_out(const NormCtx& c, float v, int x, int 
 __global__ void __launch_bounds__(NORM_THREADS)
 norm_map_kernel(const NormDesc* __restrict__ descs, int n_pages) {
     const int b = (int)blockIdx.x;
-    const NormDesc d = descs[find_page(descs, n_pages, b)];
+    const NormDesc d = descs[find_desc(descs, n_pages, b)];
     const gstate* __restrict__ st = (const gstate*)(uintptr_t)d.state;
     const int dark = st->info.dark, lo = st->info.lo, hi = st->info.hi;
     const NormCtx c = make_ctx(d, dark);

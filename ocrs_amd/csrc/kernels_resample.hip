@@ -19,6 +19,7 @@
 // footprints touch + 4 B written per output pixel (descriptors: 56 B per page, through the scalar cache).  No LDS.
 // Index arithmetic is unsigned 32-bit: the largest grid coordinate is L * l / g <= 65535 * 65534 < 2^32.
 #include "bilinear.hpp"
+#include "find_desc.hpp"
 #include "kernels.hpp"
 
 namespace ocrs {
@@ -37,13 +38,7 @@ __device__ __forceinline__ uint32_t umax(uint32_t a, uint32_t b) { return a > b 
 __global__ void __launch_bounds__(RS_COLS * RS_ROWS)
 resample_pages_kernel(const ResampleDesc* __restrict__ descs, int n_pages) {
     const int b = (int)blockIdx.x;
-    int lo = 0, hi = n_pages - 1;   // the last page whose first block is <= b
-    while (lo < hi) {
-        const int mid = (lo + hi + 1) >> 1;
-        if (descs[mid].block0 <= b) lo = mid;
-        else hi = mid - 1;
-    }
-    const ResampleDesc d = descs[lo];
+    const ResampleDesc d = descs[find_desc(descs, n_pages, b)];
     const int sw = d.sw, dh = d.dh, dw = d.dw;
     const int blocks_x = (dw + RS_COLS - 1) / RS_COLS;
     const int t = b - d.block0;

@@ -3,7 +3,7 @@
 // payloads, -0.0) arrives as it left.  A code object of its own, as kernels_rectify.hip is.
 //
 // One block = one 64 x 64 tile of a SOURCE page; blocks find their page by bisecting the descriptors' tile prefix
-// (tile0, ascending; uniform loads).  Four waves.
+// (block0, ascending; uniform loads).  Four waves.
 //   k = 1, 3  the tile goes through LDS.  In: wave w reads source rows w, w + 4, ... of the tile, lane = column: 256
 //             contiguous bytes per wave-instruction.  Out: a source column is a destination row, so wave w writes the
 //             destination rows of columns w, w + 4, ..., lane = source row (k = 3: row 63 - lane, so that addresses
@@ -19,6 +19,7 @@
 //             the mirrored quad W - 4 - c: 16-byte loads and stores, a thread per quad, a wave per 4 rows x 256 bytes.
 //             Otherwise the scalar path: lane = column, as the k = 1, 3 read.
 // Traffic: 4 B read + 4 B written per pixel, nothing else (descriptors: 40 B per page, through the scalar cache).
+#include "find_desc.hpp"
 #include "kernels.hpp"
 
 namespace ocrs {
@@ -38,16 +39,10 @@ __global__ void __launch_bounds__(64 * ROT_WAVES)
 rotate_pages_kernel(const RotateDesc* __restrict__ descs, int n_pages) {
     __shared__ uint32_t tile[ROT_TILE * ROT_PITCH];
     const int b = (int)blockIdx.x;
-    int lo = 0, hi = n_pages - 1;   // the last page whose first tile is <= b
-    while (lo < hi) {
-        const int mid = (lo + hi + 1) >> 1;
-        if (descs[mid].tile0 <= b) lo = mid;
-        else hi = mid - 1;
-    }
-    const RotateDesc d = descs[lo];
+    const RotateDesc d = descs[find_desc(descs, n_pages, b)];
     const int h = d.h, w = d.w, k = d.k;
     const int tiles_x = (w + ROT_TILE - 1) / ROT_TILE;
-    const int t = b - d.tile0;
+    const int t = b - d.block0;
     const int r0 = (t / tiles_x) * ROT_TILE, c0 = (t % tiles_x) * ROT_TILE;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const gword* __restrict__ src = (const gword*)(uintptr_t)d.src;

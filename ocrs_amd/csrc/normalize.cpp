@@ -2,11 +2,11 @@
 // polarity of resident pages on the device.  The kernels are in kernels_normalize.hip; tests/normalize_ref.py is the
 // definition.
 #include <cstddef>
-#include <limits>
 
 #include "abi_util.hpp"
 #include "engine.hpp"
 #include "kernels.hpp"
+#include "page_ops.hpp"
 
 using namespace ocrs;
 using namespace ocrs::abi;
@@ -16,8 +16,6 @@ static_assert(offsetof(ocrs_normalize_info, vote) == offsetof(k::NormInfo, vote)
               "ocrs_normalize_info is what the kernels write");
 
 namespace {
-
-constexpr int MAX_SIDE = 65535;
 
 int tile_shift(const ocrs_normalize_params& p) {
     for (int s = 4; s <= 8; s++)
@@ -32,55 +30,46 @@ void check_params(const ocrs_normalize_params& p) {
 }
 
 // every page normalised into a new page of its own, all passes for all pages on `ws`'s stream; waits for them
-std::vector<std::unique_ptr<ocrs_page>> normalize_pages(Workspace& ws, const ocrs_page* const* pages, size_t n,
-                                                        const ocrs_normalize_params* params, ocrs_normalize_info* out_info) {
-    std::vector<std::unique_ptr<ocrs_page>> made;
-    if (n == 0) return made;
-    std::vector<k::NormDesc> descs(n);
-    int64_t blocks = 0;
+PageBatch<k::NormDesc> normalize_pages(Workspace& ws, const ocrs_page* const* pages, size_t n, const ocrs_normalize_params* params,
+                                       ocrs_normalize_info* out_info) {
+    PageBatch<k::NormDesc> batch{"normalize"};
+    if (n == 0) return batch;
+    for (size_t i = 0; i < n; i++) check_page_side("normalize", pages[i]);
     for (size_t i = 0; i < n; i++) {
         const ocrs_page* p = pages[i];
-        if (p->h > MAX_SIDE || p->w > MAX_SIDE) fail(OCRS_ERR_INVALID_ARGUMENT, "normalize: a page of %d x %d: a side is at most %d", p->h, p->w, MAX_SIDE);
-        k::NormDesc& d = descs[i];
-        d.tshift = tile_shift(params[i]);
+        const int tshift = tile_shift(params[i]);
+        const int th = (p->h + (1 << tshift) - 1) >> tshift, tw = (p->w + (1 << tshift) - 1) >> tshift;
+        k::NormDesc& d = batch.add(p->h, p->w, (int64_t)th * tw);
+        d.src = p->grey.as<float>();
+        d.dst = batch.made.back()->grey.as<float>();
         d.h = p->h;
         d.w = p->w;
-        d.th = (p->h + (1 << d.tshift) - 1) >> d.tshift;
-        d.tw = (p->w + (1 << d.tshift) - 1) >> d.tshift;
-        d.block0 = (int32_t)blocks;
-        blocks += (int64_t)d.th * d.tw;
-        if (blocks > std::numeric_limits<int32_t>::max()) fail(OCRS_ERR_CAPACITY, "normalize: the pages of one call take more than 2^31 tiles");
+        d.tshift = tshift;
+        d.th = th;
+        d.tw = tw;
         d.polarity = params[i].polarity;
         d.flatten = params[i].flatten ? 1 : 0;
         d.levels = params[i].levels ? 1 : 0;
+        d.vec = vec16_ok(p->w, d.src, d.dst) ? 1 : 0;
     }
+    // per page: its state; per tile (= block): its record and its level bin
     k::NormState* d_states = ws.alloc_n<k::NormState>(n);
-    uint32_t* d_tiles = ws.alloc_n<uint32_t>((size_t)blocks);
-    uint8_t* d_grid = ws.alloc_n<uint8_t>((size_t)blocks);
+    uint32_t* d_tiles = ws.alloc_n<uint32_t>((size_t)batch.blocks);
+    uint8_t* d_grid = ws.alloc_n<uint8_t>((size_t)batch.blocks);
     k::NormInfo* d_info = ws.alloc_n<k::NormInfo>(n);
     for (size_t i = 0; i < n; i++) {
-        const ocrs_page* p = pages[i];
-        auto out = std::make_unique<ocrs_page>();
-        out->h = p->h;
-        out->w = p->w;
-        out->grey = DevBuf((size_t)p->h * p->w * sizeof(float));
-        k::NormDesc& d = descs[i];
-        d.src = p->grey.as<float>();
-        d.dst = out->grey.as<float>();
+        k::NormDesc& d = batch.descs[i];
         d.state = d_states + i;
         d.tiles = d_tiles + d.block0;
         d.grid = d_grid + d.block0;
-        d.vec = (p->w % 4 == 0 && (((uintptr_t)d.src | (uintptr_t)d.dst) & 15) == 0) ? 1 : 0;
-        made.push_back(std::move(out));
     }
-    k::NormDesc* d_descs = ws.alloc_n<k::NormDesc>(n);
-    ws.upload(d_descs, descs.data(), n * sizeof(k::NormDesc));
-    OCRS_HIP(hipMemsetAsync(d_states, 0, n * sizeof(k::NormState), ws.s()));
-    k::normalize_pages(d_descs, (int)n, (int)blocks, d_info, ws.s());
-    OCRS_HIP(hipGetLastError());
-    if (out_info) ws.download(out_info, d_info, n * sizeof(k::NormInfo));
-    ws.sync();
-    return made;
+    batch.run(ws, [&](const k::NormDesc* d_descs, int n_pages, int blocks) {
+        OCRS_HIP(hipMemsetAsync(d_states, 0, n * sizeof(k::NormState), ws.s()));
+        k::normalize_pages(d_descs, n_pages, blocks, d_info, ws.s());
+        OCRS_HIP(hipGetLastError());   // of the launches, before the download is queued
+        if (out_info) ws.download(out_info, d_info, n * sizeof(k::NormInfo));
+    });
+    return batch;
 }
 
 }  // namespace
@@ -111,8 +100,7 @@ ocrs_status ocrs_engine_normalize_pages(const ocrs_engine* e, const ocrs_page* c
         check_pages_on(e, pages, n);
         for (size_t i = 0; i < n; i++) check_params(params[i]);
         Workspace ws;
-        auto made = normalize_pages(ws, pages, n, params, out_info);
-        for (size_t i = 0; i < n; i++) out_pages[i] = made[i].release();
+        normalize_pages(ws, pages, n, params, out_info).release_into(out_pages);
     });
 }
 

@@ -7,6 +7,7 @@
 #include "abi_util.hpp"
 #include "engine.hpp"
 #include "kernels.hpp"
+#include "page_ops.hpp"
 
 using namespace ocrs;
 using namespace ocrs::geom;
@@ -17,37 +18,21 @@ namespace {
 inline int reduce_turns(int k) { return ((k % 4) + 4) % 4; }
 
 // np.rot90(page, k) of every page as a new page of its own, all in one launch on `ws`'s stream; waits for it.
-std::vector<std::unique_ptr<ocrs_page>> rotate_pages(Workspace& ws, const ocrs_page* const* pages, size_t n, const int* turns) {
-    std::vector<std::unique_ptr<ocrs_page>> made;
-    if (n == 0) return made;
-    std::vector<k::RotateDesc> descs(n);
-    int64_t tiles = 0;
+PageBatch<k::RotateDesc> rotate_pages(Workspace& ws, const ocrs_page* const* pages, size_t n, const int* turns) {
+    PageBatch<k::RotateDesc> batch{"rotate"};
     for (size_t i = 0; i < n; i++) {
         const ocrs_page* p = pages[i];
         const int k = reduce_turns(turns[i]);
-        auto out = std::make_unique<ocrs_page>();
-        out->h = (k & 1) ? p->w : p->h;
-        out->w = (k & 1) ? p->h : p->w;
-        out->grey = DevBuf((size_t)p->h * p->w * sizeof(float));
-        k::RotateDesc& d = descs[i];
+        k::RotateDesc& d = batch.add((k & 1) ? p->w : p->h, (k & 1) ? p->h : p->w, k::rotate_tiles(p->h, p->w));
         d.src = p->grey.as<uint32_t>();
-        d.dst = out->grey.as<uint32_t>();
+        d.dst = batch.made.back()->grey.as<uint32_t>();
         d.h = p->h;
         d.w = p->w;
         d.k = k;
-        d.tile0 = (int32_t)tiles;
-        d.vec = (p->w % 4 == 0 && (((uintptr_t)d.src | (uintptr_t)d.dst) & 15) == 0) ? 1 : 0;
-        d.pad_ = 0;
-        tiles += k::rotate_tiles(p->h, p->w);
-        if (tiles > std::numeric_limits<int32_t>::max()) fail(OCRS_ERR_CAPACITY, "rotate: the pages of one call take more than 2^31 tiles");
-        made.push_back(std::move(out));
+        d.vec = vec16_ok(p->w, d.src, d.dst) ? 1 : 0;
     }
-    k::RotateDesc* d_descs = ws.alloc_n<k::RotateDesc>(n);
-    ws.upload(d_descs, descs.data(), n * sizeof(k::RotateDesc));
-    k::rotate_pages(d_descs, (int)n, (int)tiles, ws.s());
-    OCRS_HIP(hipGetLastError());
-    ws.sync();
-    return made;
+    batch.run(ws, [&](const k::RotateDesc* d_descs, int n_pages, int tiles) { k::rotate_pages(d_descs, n_pages, tiles, ws.s()); });
+    return batch;
 }
 
 // the word-shape vote: out[0] = summed widths of the words that are wider than tall, out[1] = summed heights of the others
@@ -94,8 +79,7 @@ ocrs_status ocrs_engine_rotate_pages(const ocrs_engine* e, const ocrs_page* cons
         if (!e || (n > 0 && (!pages || !quarter_turns || !out))) fail(OCRS_ERR_INVALID_ARGUMENT, "null argument");
         check_pages_on(e, pages, n);
         Workspace ws;
-        auto made = rotate_pages(ws, pages, n, quarter_turns);
-        for (size_t i = 0; i < n; i++) out[i] = made[i].release();
+        rotate_pages(ws, pages, n, quarter_turns).release_into(out);
     });
 }
 
@@ -150,11 +134,7 @@ ocrs_status ocrs_engine_detect_orientation(const ocrs_engine* e, const ocrs_page
         std::vector<std::vector<RotatedRect>> words0;
         e->detect(&page, 1, &words0, nullptr);
         std::vector<float> flat;
-        for (const RotatedRect& r : words0[0]) {
-            float a[6];
-            r.to_array(a);
-            flat.insert(flat.end(), a, a + 6);
-        }
+        append_rects(flat, words0[0]);
         double v[2];
         orientation_vote(flat.data(), words0[0].size(), v);
         const int cand[2] = {v[0] >= v[1] ? 0 : 1, v[0] >= v[1] ? 2 : 3};
@@ -166,7 +146,7 @@ ocrs_status ocrs_engine_detect_orientation(const ocrs_engine* e, const ocrs_page
         std::vector<std::unique_ptr<ocrs_page>> turned;
         {
             Workspace ws;
-            turned = rotate_pages(ws, src.data(), src.size(), turns.data());
+            turned = std::move(rotate_pages(ws, src.data(), src.size(), turns.data()).made);
         }
         std::vector<const ocrs_page*> tp;
         for (const auto& p : turned) tp.push_back(p.get());

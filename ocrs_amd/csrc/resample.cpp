@@ -1,12 +1,12 @@
 // Working-resolution detection (include/ocrs_amd.h "Working resolution"): resampling resident pages on
 // the device, the host maps between a page and its work page, and detection at a work size the caller chooses.
 #include <cmath>
-#include <limits>
 #include <numeric>
 
 #include "abi_util.hpp"
 #include "engine.hpp"
 #include "kernels.hpp"
+#include "page_ops.hpp"
 
 using namespace ocrs;
 using namespace ocrs::geom;
@@ -14,68 +14,54 @@ using namespace ocrs::abi;
 
 namespace {
 
-constexpr int MAX_SIDE = 65535;
-
 struct ResizeJob {
     const ocrs_page* page;
     int h, w;     // of the result
     bool area;
 };
 
+void check_filter(const char* what, int filter) {
+    if (filter != OCRS_RESAMPLE_AUTO && filter != OCRS_RESAMPLE_BILINEAR && filter != OCRS_RESAMPLE_AREA)
+        fail(OCRS_ERR_INVALID_ARGUMENT, "%s: unknown filter %d", what, filter);
+}
+
 // AUTO resolved, sizes and the filter's own limits checked
 ResizeJob resize_job(const ocrs_page* p, int out_h, int out_w, int filter) {
-    if (out_h < 1 || out_h > MAX_SIDE || out_w < 1 || out_w > MAX_SIDE)
-        fail(OCRS_ERR_INVALID_ARGUMENT, "resize: %d x %d: a side is 1 .. %d", out_h, out_w, MAX_SIDE);
-    if (p->h > MAX_SIDE || p->w > MAX_SIDE) fail(OCRS_ERR_INVALID_ARGUMENT, "resize: a page of %d x %d: a side is at most %d", p->h, p->w, MAX_SIDE);
+    if (out_h < 1 || out_h > MAX_PAGE_SIDE || out_w < 1 || out_w > MAX_PAGE_SIDE)
+        fail(OCRS_ERR_INVALID_ARGUMENT, "resize: %d x %d: a side is 1 .. %d", out_h, out_w, MAX_PAGE_SIDE);
+    check_page_side("resize", p);
     const bool shrinks = out_h <= p->h && out_w <= p->w;
-    if (filter != OCRS_RESAMPLE_AUTO && filter != OCRS_RESAMPLE_BILINEAR && filter != OCRS_RESAMPLE_AREA)
-        fail(OCRS_ERR_INVALID_ARGUMENT, "resize: unknown filter %d", filter);
+    check_filter("resize", filter);
     if (filter == OCRS_RESAMPLE_AREA && !shrinks)
         fail(OCRS_ERR_INVALID_ARGUMENT, "resize: the area filter only shrinks (%d x %d -> %d x %d)", p->h, p->w, out_h, out_w);
     return {p, out_h, out_w, filter == OCRS_RESAMPLE_AREA || (filter == OCRS_RESAMPLE_AUTO && shrinks)};
 }
 
 // every job's page resampled into a new page of its own, all in one launch on `ws`'s stream; waits for it
-std::vector<std::unique_ptr<ocrs_page>> resize_pages(Workspace& ws, const std::vector<ResizeJob>& jobs) {
-    std::vector<std::unique_ptr<ocrs_page>> made;
-    if (jobs.empty()) return made;
-    std::vector<k::ResampleDesc> descs(jobs.size());
-    int64_t blocks = 0;
-    for (size_t i = 0; i < jobs.size(); i++) {
-        const ResizeJob& j = jobs[i];
-        auto out = std::make_unique<ocrs_page>();
-        out->h = j.h;
-        out->w = j.w;
-        out->grey = DevBuf((size_t)j.h * j.w * sizeof(float));
-        k::ResampleDesc& d = descs[i];
+PageBatch<k::ResampleDesc> resize_pages(Workspace& ws, const std::vector<ResizeJob>& jobs) {
+    PageBatch<k::ResampleDesc> batch{"resize"};
+    for (const ResizeJob& j : jobs) {
+        k::ResampleDesc& d = batch.add(j.h, j.w, k::resample_blocks(j.h, j.w));
         d.src = j.page->grey.as<float>();
-        d.dst = out->grey.as<float>();
+        d.dst = batch.made.back()->grey.as<float>();
         d.sh = j.page->h;
         d.sw = j.page->w;
         d.dh = j.h;
         d.dw = j.w;
         d.area = j.area ? 1 : 0;
-        d.block0 = (int32_t)blocks;
         const int gy = std::gcd(d.sh, d.dh), gx = std::gcd(d.sw, d.dw);
         d.py = (uint32_t)(d.sh / gy);
         d.qy = (uint32_t)(d.dh / gy);
         d.px = (uint32_t)(d.sw / gx);
         d.qx = (uint32_t)(d.dw / gx);
-        blocks += k::resample_blocks(j.h, j.w);
-        if (blocks > std::numeric_limits<int32_t>::max()) fail(OCRS_ERR_CAPACITY, "resize: the pages of one call take more than 2^31 blocks");
-        made.push_back(std::move(out));
     }
-    k::ResampleDesc* d_descs = ws.alloc_n<k::ResampleDesc>(jobs.size());
-    ws.upload(d_descs, descs.data(), jobs.size() * sizeof(k::ResampleDesc));
-    k::resample_pages(d_descs, (int)jobs.size(), (int)blocks, ws.s());
-    OCRS_HIP(hipGetLastError());
-    ws.sync();
-    return made;
+    batch.run(ws, [&](const k::ResampleDesc* d_descs, int n_pages, int blocks) { k::resample_pages(d_descs, n_pages, blocks, ws.s()); });
+    return batch;
 }
 
 int work_side(int side, double scale) {
     const double v = std::floor((double)side * scale + 0.5);
-    return v < 1.0 ? 1 : v > (double)MAX_SIDE ? MAX_SIDE : (int)v;
+    return v < 1.0 ? 1 : v > (double)MAX_PAGE_SIDE ? MAX_PAGE_SIDE : (int)v;
 }
 
 // rects of a from_h x from_w frame -> the to_h x to_w frame of the same picture; points of the pixel-index frame
@@ -117,8 +103,7 @@ ocrs_status ocrs_engine_resize_pages(const ocrs_engine* e, const ocrs_page* cons
         std::vector<ResizeJob> jobs;
         for (size_t i = 0; i < n; i++) jobs.push_back(resize_job(pages[i], out_hw[2 * i], out_hw[2 * i + 1], filters[i]));
         Workspace ws;
-        auto made = resize_pages(ws, jobs);
-        for (size_t i = 0; i < n; i++) out[i] = made[i].release();
+        resize_pages(ws, jobs).release_into(out);
     });
 }
 
@@ -152,8 +137,7 @@ ocrs_status ocrs_engine_detect_words_batch_at(const ocrs_engine* e, const ocrs_p
     return guarded_engine(e, [&] {
         if (!e || !rects || !offsets || (n_pages > 0 && (!pages || !work_hw))) fail(OCRS_ERR_INVALID_ARGUMENT, "null argument");
         if (!score != !pixels) fail(OCRS_ERR_INVALID_ARGUMENT, "score and pixels come together");
-        if (filter != OCRS_RESAMPLE_AUTO && filter != OCRS_RESAMPLE_BILINEAR && filter != OCRS_RESAMPLE_AREA)
-            fail(OCRS_ERR_INVALID_ARGUMENT, "detect at: unknown filter %d", filter);
+        check_filter("detect at", filter);
         check_pages_on(e, pages, n_pages);
         // 1. the pages whose work size is not their own, resampled in one launch
         std::vector<ResizeJob> jobs;
@@ -168,7 +152,7 @@ ocrs_status ocrs_engine_detect_words_batch_at(const ocrs_engine* e, const ocrs_p
         std::vector<std::unique_ptr<ocrs_page>> made;
         if (!jobs.empty()) {
             Workspace ws;
-            made = resize_pages(ws, jobs);
+            made = std::move(resize_pages(ws, jobs).made);
         }
         std::vector<const ocrs_page*> work(n_pages);
         for (size_t i = 0; i < n_pages; i++) work[i] = job_of[i] == (size_t)-1 ? pages[i] : made[job_of[i]].get();
@@ -176,30 +160,11 @@ ocrs_status ocrs_engine_detect_words_batch_at(const ocrs_engine* e, const ocrs_p
         const bool scored = score != nullptr;
         std::vector<std::vector<RotatedRect>> rr;
         DetScores sc;
-        e->detect(work.data(), n_pages, &rr, nullptr, scored ? &sc : nullptr, !tiled ? -1 : overlap < 0 ? OCRS_TILE_OVERLAP_DEFAULT : overlap);
+        e->detect(work.data(), n_pages, &rr, nullptr, scored ? &sc : nullptr, tiled ? tile_overlap_arg(overlap) : -1);
         // 3. the rects back in each page's own frame
-        std::vector<float> flat, fscore;
-        std::vector<uint32_t> fpixels;
-        offsets[0] = 0;
-        for (size_t i = 0; i < n_pages; i++) {
-            const size_t first = flat.size();
-            for (const RotatedRect& r : rr[i]) {
-                float a[6];
-                r.to_array(a);
-                flat.insert(flat.end(), a, a + 6);
-            }
-            rescale_rects(flat.data() + first, rr[i].size(), work[i]->h, work[i]->w, pages[i]->h, pages[i]->w);
-            if (scored) {
-                fscore.insert(fscore.end(), sc.score[i].begin(), sc.score[i].end());
-                fpixels.insert(fpixels.end(), sc.pixels[i].begin(), sc.pixels[i].end());
-            }
-            offsets[i + 1] = flat.size() / 6;
-        }
-        if (scored) {
-            *score = dup_buffer(fscore);
-            *pixels = dup_buffer(fpixels);
-        }
-        *rects = dup_buffer(flat);
+        pack_words(rr, scored ? &sc : nullptr, rects, offsets, score, pixels, [&](size_t i, float* rects6, size_t n) {
+            rescale_rects(rects6, n, work[i]->h, work[i]->w, pages[i]->h, pages[i]->w);
+        });
     });
 }
 

@@ -194,6 +194,38 @@ def test_mixed_batch_equals_each_page_alone_twenty_times(eng):
         eng.normalize_batch(inputs, params[:2])
 
 
+# a page boundary inside, on and just past a 64-tile edge; 64 x 64 takes the 16-byte accesses, 130 x 7 cannot
+EDGE_MIXED = [((1, 1), {"tile": 16}), ((63, 65), {"tile": 64}), ((64, 64), {"tile": 16}), ((65, 63), {"tile": 64}), ((130, 7), {"tile": 16})]
+
+
+def test_edge_sized_batch_equals_each_page_alone(eng):
+    srcs = [noise(60 + i, *s, plant=i % 2 == 1) for i, (s, _) in enumerate(EDGE_MIXED)]
+    inputs = [eng.input_from_grey(s) for s in srcs]
+    params = [p for _, p in EDGE_MIXED]
+    pages, infos = eng.normalize_batch(inputs, params, info=True)
+    for i, (src, inp, p, out, info) in enumerate(zip(srcs, inputs, params, pages, infos)):
+        alone, alone_info = eng.normalize(inp, info=True, **p)
+        assert alone_info == info and image_of(alone).tobytes() == image_of(out).tobytes(), "page %d alone" % i
+        exp, exp_info = N.normalize(src, **p)
+        assert info == exp_info, (i, info, exp_info)
+        assert_same_words(image_of(out), exp, "batch page %d" % i)
+
+
+def test_a_bad_page_in_the_middle_returns_nothing_and_leaks_nothing(eng):
+    inputs = [eng.input_from_grey(noise(80 + i, 40, 50)) for i in range(3)]
+    pages = (C.c_void_p * 3)(*[i._h for i in inputs])
+    ps = (_lib.NormalizeParams * 3)(_lib.NormalizeParams(64, 0, 1, 1), _lib.NormalizeParams(48, 0, 1, 1), _lib.NormalizeParams(64, 0, 1, 1))
+    out = (C.c_void_p * 3)()
+    live = _lib.pool_stats()["device_live"]
+    assert _lib.lib().ocrs_engine_normalize_pages(eng._h, pages, C.c_size_t(3), ps, out, None) == 1, "INVALID_ARGUMENT"
+    assert [out[i] for i in range(3)] == [None] * 3, "a failed call writes no page"
+    assert _lib.pool_stats()["device_live"] == live, "nothing stays allocated"
+    with pytest.raises(_lib.OcrsError) as e:
+        eng.normalize_batch(inputs, [None, {"tile": 48}, None])
+    assert e.value.status_name == "INVALID_ARGUMENT", e.value
+    assert _lib.pool_stats()["device_live"] == live
+
+
 def test_source_is_unchanged_and_outlives_the_result(eng):
     src = noise(99, 131, 70)
     inp = eng.input_from_grey(src)

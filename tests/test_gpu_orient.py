@@ -97,6 +97,20 @@ def test_mixed_batch_equals_each_page_alone(eng):
         eng.rotate_batch(inputs, ks[:2])
 
 
+EDGE_SIZES = [(1, 1), (63, 65), (64, 64), (65, 63), (130, 7)]   # a page boundary inside, on and just past a 64-tile edge
+
+
+def test_edge_sized_batch_equals_each_page_alone(eng):
+    """One launch over pages that end inside, on and just past a tile edge, with and without 16-byte accesses (64 x 64 at an
+    even k takes them, 130 x 7 cannot), each by its own k: every page is the page turned alone, bit for bit."""
+    ks = [5, 1, 2, 3, 0]
+    srcs = [bits_page(70 + i, *hw) for i, hw in enumerate(EDGE_SIZES)]
+    inputs = [eng.input_from_grey(s) for s in srcs]
+    for src, inp, k, out in zip(srcs, inputs, ks, eng.rotate_batch(inputs, ks)):
+        assert words_of(out).tobytes() == words_of(eng.rotate(inp, k)).tobytes(), (src.shape, k)
+        assert words_of(out).tobytes() == np.ascontiguousarray(np.rot90(src.view(np.uint32), k)).tobytes(), (src.shape, k)
+
+
 def test_source_is_unchanged_and_outlives_the_turned_page(eng):
     src = bits_page(99, 131, 70)
     inp = eng.input_from_grey(src)

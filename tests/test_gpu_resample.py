@@ -136,6 +136,36 @@ def test_mixed_batch_equals_each_page_alone(eng):
         eng.resize_batch(inputs, [(5, 5)])
 
 
+# a page boundary inside, on and just past a 64-column block edge; a grow, a shrink, an identity, a grow and a shrink
+EDGE_MIXED = [((1, 1), (3, 2), "auto"), ((63, 65), (31, 33), "area"), ((64, 64), (64, 64), "auto"), ((65, 63), (70, 64), "bilinear"),
+              ((130, 7), (65, 7), "auto")]
+
+
+def test_edge_sized_batch_equals_each_page_alone(eng):
+    srcs = [planted_page(60 + i, *s) for i, (s, _, _) in enumerate(EDGE_MIXED)]
+    inputs = [eng.input_from_grey(s) for s in srcs]
+    batch = eng.resize_batch(inputs, [o for _, o, _ in EDGE_MIXED], [f for _, _, f in EDGE_MIXED])
+    for src, inp, (_, out_hw, filt), out in zip(srcs, inputs, EDGE_MIXED, batch):
+        assert_same_words(image_of(out), image_of(eng.resize(inp, out_hw, filt)), "batch against alone %s %s" % (out_hw, filt))
+        assert_same_words(image_of(out), R.resize(src, out_hw, filt), "batch %s %s" % (out_hw, filt))
+
+
+def test_a_bad_page_in_the_middle_returns_nothing_and_leaks_nothing(eng):
+    inputs = [eng.input_from_grey(planted_page(80 + i, 40, 50)) for i in range(3)]
+    pages = (C.c_void_p * 3)(*[i._h for i in inputs])
+    hw = (C.c_int * 6)(20, 25, 0, 25, 20, 25)
+    fl = (C.c_int * 3)(0, 0, 0)
+    out = (C.c_void_p * 3)()
+    live = _lib.pool_stats()["device_live"]
+    assert _lib.lib().ocrs_engine_resize_pages(eng._h, pages, C.c_size_t(3), hw, fl, out) == 1, "INVALID_ARGUMENT"
+    assert [out[i] for i in range(3)] == [None] * 3, "a failed call writes no page"
+    assert _lib.pool_stats()["device_live"] == live, "nothing stays allocated"
+    with pytest.raises(_lib.OcrsError) as e:
+        eng.resize_batch(inputs, [(20, 25), (0, 25), (20, 25)])
+    assert e.value.status_name == "INVALID_ARGUMENT", e.value
+    assert _lib.pool_stats()["device_live"] == live
+
+
 def test_source_is_unchanged_and_outlives_the_result(eng):
     src = planted_page(99, 131, 70, plant=False)
     inp = eng.input_from_grey(src)
