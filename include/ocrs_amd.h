@@ -476,6 +476,90 @@ OCRS_API ocrs_status ocrs_engine_normalize_page(const ocrs_engine* e, const ocrs
 OCRS_API ocrs_status ocrs_engine_normalize_pages(const ocrs_engine* e, const ocrs_page* const* pages, size_t n,
                                                  const ocrs_normalize_params* params, ocrs_page** out_pages, ocrs_normalize_info* out_info);
 
+/* ------------------------------------------------------------------------
+ * Page deskew (no reference counterpart, opt-in).  A page that went through the feeder a few degrees off
+ * breaks find_text_lines' grouping before the rectified crops (§8.4) can help.  These calls measure the skew of a resident
+ * page without a detector and without knowing its polarity, make the upright page as a new resident page, and map what was
+ * found on it back to the frame of the scan.  tests/deskew_ref.py restates every definition; the library equals it bit for
+ * bit (the trigonometry of ocrs_skew_table and ocrs_deskew_map is libm's: held within one unit of the last place).
+ *
+ * ocrs_engine_skew_scores: out_scores[i * n_angles + a] = the profile score of page i at angle a, for n pages of any sizes
+ * in one launch (plus one small launch that squares and sums).  sc_table[2a], sc_table[2a + 1] = S, C = the angle's sine
+ * and cosine in Q16 (round(sin * 65536)); the caller makes the table (ocrs_skew_table), so the result is integer arithmetic
+ * throughout and does not depend on schedule, batch or launch shape.  For a page of H x W:
+ *   q(x, y)   the bin of Page normalisation above: g = clamp(v + 0.5f, 0, 1), floor(g * 256f) kept within 0 .. 255
+ *   d(x, y)   |q(x, y) - q(x, y + 1)| for y < H - 1; 0 on the last row and when either pixel is NaN.  A vertical
+ *             difference is polarity-free, and flat paper weighs nothing, so the varying length of a projection row needs
+ *             no correction
+ *   bin       (x S + y C - t0) >> 16, t0 = min(0, (W - 1) S) + min(0, (H - 1) C) (the minimum over the four corners)
+ *   P[b]      the sum of d over the pixels of bin b (uint32);  score = sum over b of P[b]^2 (uint64)
+ * y points down: a page whose content was turned counter-clockwise by t (PIL's rotate(t)) has baselines along
+ * (cos t, -sin t), constant in x sin t + y cos t, so the score peaks at +t.  OCRS_ERR_INVALID_ARGUMENT for n_angles < 1
+ * (or > 65535), an |S| or |C| above 65536, and a page side above 4096 (x S + y C - t0 must stay inside int32: the
+ * estimate is meant for a work copy); OCRS_ERR_CAPACITY for more than 65535 pages or more than 2 GiB of profiles
+ * (4 n_angles (H + W) bytes per page) in one call.
+ *
+ * ocrs_skew_table (host only): sc_table[2i], [2i + 1] = S, C of the angle (first + i) * step_deg degrees, i < n:
+ * round-to-nearest-even of sin / cos (double, libm) * 65536.
+ *
+ * ocrs_engine_estimate_skew: (1) a page whose longer side exceeds work_max_side is shrunk with OCRS_RESAMPLE_AREA to
+ * ocrs_work_size(scale = work_max_side / longer side); a smaller page goes as it is; (2) the scores of the coarse angles
+ * k r * fine_step_deg, k = -K .. K, r = coarse_step_deg / fine_step_deg (a whole number), K = floor(max_deg /
+ * coarse_step_deg); (3) the scores of the 2 r + 1 angles one fine step apart around the best coarse one; (4) the arg max,
+ * on the host.  Every angle is an integer multiple of the fine step; ties go to the smaller |angle|, then to the negative
+ * one, so a blank page has angle 0.  params == NULL: ocrs_skew_params_default (work_max_side 1024, max_deg 15, coarse 0.5,
+ * fine 0.1).  ocrs_skew_params_check (host only) refuses work_max_side outside 1 .. 4096, max_deg outside (0, 45], steps
+ * that are not positive or whose ratio is not whole, and fewer than one coarse step.
+ *
+ * ocrs_engine_warp_page[s]: *out = a new out_h x out_w page (sides 1 .. 65535), independent of its source; release both
+ * with ocrs_page_free in any order.  The batch form serves n pages of any sizes, each with its own out_hw[2i], [2i + 1],
+ * m[6i .. 6i + 5] and fill[i], in one launch.  float32, every operation rounded on its own (§8.4's expression form):
+ * fx = ox + 0.5f, fy = oy + 0.5f; X = (m0 + m1 fx) + m2 fy, Y = (m3 + m4 fx) + m5 fy; ix = floor(X), wx = X - ix, y
+ * likewise; taps (ix, iy) .. (ix + 1, iy + 1), a tap outside the page is `fill`; top = (1 - wx) t00 + wx t01, bot likewise,
+ * v = (1 - wy) top + wy bot.  Coefficients that are not finite: OCRS_ERR_INVALID_ARGUMENT.
+ *
+ * ocrs_deskew_map (host only): the map that undoes a skew of +angle_deg (|angle| <= 45, else OCRS_ERR_INVALID_ARGUMENT):
+ * the output is the page turned clockwise by t about its centre.  In double, each coefficient rounded once to float32:
+ * W' = ceil(w |cos t| + h |sin t|), H' = ceil(w |sin t| + h |cos t|) when expand, else W' = w, H' = h;  m1 = cos t,
+ * m2 = sin t, m0 = (w/2 - 0.5) - cos t W'/2 - sin t H'/2;  m4 = -sin t, m5 = cos t, m3 = (h/2 - 0.5) + sin t W'/2 -
+ * cos t H'/2.  out_hw = {H', W'}.  t = 0 gives the identity map and the page's own size.
+ *
+ * ocrs_unwarp_rects / ocrs_unwarp_chars (host only, in place): results found on a page warped with m, in the frame of its
+ * source.  In double from the float32 coefficients.  Rects: centre X = (m0 + m1 (x + 0.5)) + m2 (y + 0.5), Y likewise;
+ * up' = L up / |L up| with L = (m1 m2; m4 m5) (up stays when |L up| is 0 or not finite); w' = w * |(m1, m4)|,
+ * h' = h * |(m2, m5)| (1 for a rotation); each result rounded to float32.  A rect with a value that is not finite passes
+ * through as it is.  Char boxes: the four corners (points of the pixel-index frame) go through the map; left and top are
+ * the floor of the minimum, right and bottom the ceil of the maximum (saturating at int32). */
+typedef struct ocrs_skew_params {
+    double max_deg;         /* the coarse search covers -max_deg .. +max_deg; (0, 45] */
+    double coarse_step_deg; /* a whole multiple of fine_step_deg */
+    double fine_step_deg;   /* > 0; the estimate's resolution */
+    int32_t work_max_side;  /* 1 .. 4096 */
+    int32_t reserved;       /* 0 */
+} ocrs_skew_params;
+typedef struct ocrs_skew_info {
+    double angle_deg;       /* fine_index * fine_step_deg */
+    uint64_t best_score;    /* the best coarse score */
+    uint64_t second_score;  /* the runner-up among the coarse scores */
+    uint64_t fine_score;    /* the score at angle_deg */
+    int32_t work_h, work_w; /* the size the scores were taken at */
+    int32_t coarse_index;   /* the best coarse angle, in fine steps */
+    int32_t fine_index;     /* the estimate, in fine steps */
+} ocrs_skew_info;
+OCRS_API ocrs_status ocrs_skew_params_default(ocrs_skew_params* out);
+OCRS_API ocrs_status ocrs_skew_params_check(const ocrs_skew_params* params);
+OCRS_API ocrs_status ocrs_skew_table(int first, size_t n, double step_deg, int32_t* sc_table);
+OCRS_API ocrs_status ocrs_engine_skew_scores(const ocrs_engine* e, const ocrs_page* const* pages, size_t n, const int32_t* sc_table,
+                                             size_t n_angles, uint64_t* out_scores);
+OCRS_API ocrs_status ocrs_engine_estimate_skew(const ocrs_engine* e, const ocrs_page* page, const ocrs_skew_params* params,
+                                               ocrs_skew_info* out);
+OCRS_API ocrs_status ocrs_engine_warp_page(const ocrs_engine* e, const ocrs_page* page, int out_h, int out_w, const float m[6], float fill,
+                                           ocrs_page** out);
+OCRS_API ocrs_status ocrs_engine_warp_pages(const ocrs_engine* e, const ocrs_page* const* pages, size_t n, const int* out_hw,
+                                            const float* m, const float* fill, ocrs_page** out);
+OCRS_API ocrs_status ocrs_deskew_map(int h, int w, double angle_deg, int expand, int out_hw[2], float m[6]);
+OCRS_API ocrs_status ocrs_unwarp_rects(float* rects6, size_t n, const float m[6]);
+
 /* OcrEngine::detection_threshold (lib.rs:282-287). */
 OCRS_API float ocrs_engine_detection_threshold(const ocrs_engine* e);
 
@@ -664,6 +748,8 @@ OCRS_API ocrs_status ocrs_engine_rotate_pages(const ocrs_engine* e, const ocrs_p
                                               ocrs_page** out);
 OCRS_API ocrs_status ocrs_unrotate_rects(float* rects6, size_t n, int page_h, int page_w, int k);
 OCRS_API ocrs_status ocrs_unrotate_chars(ocrs_text_char* chars, size_t n, int page_h, int page_w, int k);
+/* "Page deskew" above: its char boxes (declared here, after ocrs_text_char). */
+OCRS_API ocrs_status ocrs_unwarp_chars(ocrs_text_char* chars, size_t n, const float m[6]);
 OCRS_API ocrs_status ocrs_orientation_vote(const float* rects6, size_t n, double out[2]);
 OCRS_API ocrs_status ocrs_engine_detect_orientation(const ocrs_engine* e, const ocrs_page* page, size_t max_lines, int* quarter_turns,
                                                     double vote[2], double score[4], uint32_t n_chars[4]);

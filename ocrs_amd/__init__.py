@@ -486,6 +486,94 @@ def _normalize_struct(tile=None, polarity=None, flatten=None, levels=None):
     return p
 
 
+class Skew:
+    """ocrs_engine_estimate_skew's outputs: angle (degrees; the page's content is turned counter-clockwise
+    by it, deskew_map(.., angle) undoes it), scores (best coarse, runner-up coarse, at the angle), work_hw (the size the
+    scores were taken at), coarse_index and fine_index (the best coarse angle and the estimate, in fine steps)."""
+    __slots__ = ("angle", "scores", "work_hw", "coarse_index", "fine_index")
+
+    def __repr__(self):
+        return "Skew(angle=%r, scores=%r, work_hw=%r)" % (self.angle, self.scores, self.work_hw)
+
+
+def _skew_struct(work_max_side=None, max_deg=None, coarse_step_deg=None, fine_step_deg=None):
+    p = _lib.SkewParams()
+    check(lib().ocrs_skew_params_default(C.byref(p)))
+    if work_max_side is not None:
+        p.work_max_side = int(work_max_side)
+    if max_deg is not None:
+        p.max_deg = float(max_deg)
+    if coarse_step_deg is not None:
+        p.coarse_step_deg = float(coarse_step_deg)
+    if fine_step_deg is not None:
+        p.fine_step_deg = float(fine_step_deg)
+    return p
+
+
+def skew_params(work_max_side=None, max_deg=None, coarse_step_deg=None, fine_step_deg=None):
+    """ocrs_skew_params as a dict: ocrs_skew_params_default (work_max_side 1024, max_deg 15, coarse step 0.5,
+    fine step 0.1) with the given fields replaced, checked by ocrs_skew_params_check (host only)."""
+    p = _skew_struct(work_max_side, max_deg, coarse_step_deg, fine_step_deg)
+    check(lib().ocrs_skew_params_check(C.byref(p)))
+    return {"work_max_side": int(p.work_max_side), "max_deg": float(p.max_deg), "coarse_step_deg": float(p.coarse_step_deg),
+            "fine_step_deg": float(p.fine_step_deg)}
+
+
+def skew_table(first, n, step_deg):
+    """ocrs_skew_table (host only): int32 [n, 2], the Q16 sine and cosine of the angles (first + i) * step_deg degrees."""
+    t = np.zeros((int(n), 2), np.int32)
+    check(lib().ocrs_skew_table(C.c_int(int(first)), C.c_size_t(int(n)), C.c_double(float(step_deg)), t.ctypes.data_as(C.POINTER(C.c_int32))))
+    return t
+
+
+def deskew_map(page_hw, angle_deg, expand=True):
+    """ocrs_deskew_map (host only): the warp that undoes a skew of +angle_deg on a page_hw = (height, width) page ->
+    ((out_h, out_w), m float32 [6]).  expand: the upright page holds the whole scan; else it keeps the scan's size."""
+    hw = (C.c_int * 2)()
+    m = np.zeros(6, np.float32)
+    check(lib().ocrs_deskew_map(C.c_int(int(page_hw[0])), C.c_int(int(page_hw[1])), C.c_double(float(angle_deg)), C.c_int(1 if expand else 0),
+                                hw, m.ctypes.data_as(C.POINTER(C.c_float))))
+    return (int(hw[0]), int(hw[1])), m
+
+
+def _map_arg(m):
+    a = np.ascontiguousarray(m, np.float32).reshape(-1)
+    if a.size != 6:
+        raise ValueError("a map is six coefficients")
+    return a
+
+
+def unwarp_rects(rects, m):
+    """ocrs_unwarp_rects (host only): word rects found on a page warped with m -> the same rects in the frame of the
+    warp's source, float32 [n, 6] (a copy)."""
+    a, mm = _rects_to_array(rects).copy(), _map_arg(m)
+    check(lib().ocrs_unwarp_rects(a.ctypes.data_as(C.POINTER(C.c_float)), C.c_size_t(len(a)), mm.ctypes.data_as(C.POINTER(C.c_float))))
+    return a
+
+
+def unwarp_boxes(boxes, m):
+    """ocrs_unwarp_chars on bare boxes: int32 [n, 4] (top, left, bottom, right) on a page warped with m -> in its source's frame."""
+    b, mm = np.asarray(boxes, np.int32).reshape(-1, 4), _map_arg(m)
+    arr = (_lib.TextCharC * max(len(b), 1))()
+    for i, (t, l, bo, r) in enumerate(b.tolist()):
+        arr[i] = _lib.TextCharC(0, t, l, bo, r)
+    check(lib().ocrs_unwarp_chars(arr, C.c_size_t(len(b)), mm.ctypes.data_as(C.POINTER(C.c_float))))
+    return np.array([[arr[i].top, arr[i].left, arr[i].bottom, arr[i].right] for i in range(len(b))], np.int32).reshape(-1, 4)
+
+
+def unwarp_lines(text_lines, m):
+    """recognize_text's output on a page warped with m -> new TextLines (None stays None) whose char boxes are in the frame
+    of the warp's source (ocrs_unwarp_chars); text, log-probs and scores are kept."""
+    out = []
+    for t in text_lines:
+        if t is None:
+            out.append(None)
+            continue
+        boxes = unwarp_boxes([c.rect for c in t.chars()], m)
+        out.append(TextLine([TextChar(c.char, tuple(int(v) for v in b), c.logp) for c, b in zip(t.chars(), boxes)], t.score))
+    return out
+
+
 def _work_hw(work_size):
     """None = the page's own size (0, 0)."""
     return (0, 0) if work_size is None else (int(work_size[0]), int(work_size[1]))
@@ -691,6 +779,62 @@ class OcrEngine:
         check(lib().ocrs_engine_normalize_pages(self._h, pages, C.c_size_t(n), ps, out, infos if info else None))
         made = _new_inputs(out, n)
         return (made, [infos[i].as_dict() for i in range(n)]) if info else made
+
+    # ---- page deskew
+    def skew_scores(self, inputs, sc_table):
+        """ocrs_engine_skew_scores: the skew profile scores of pages of any sizes (a side at most 4096) at the angles of
+        sc_table (int32 [A, 2], Q16 sine and cosine: skew_table) -> uint64 [n, A], in one launch."""
+        n = len(inputs)
+        t = np.ascontiguousarray(sc_table, np.int32).reshape(-1, 2)
+        out = np.zeros((n, len(t)), np.uint64)
+        check(lib().ocrs_engine_skew_scores(self._h, _page_array(inputs), C.c_size_t(n), t.ctypes.data_as(C.POINTER(C.c_int32)),
+                                            C.c_size_t(len(t)), out.ctypes.data_as(C.POINTER(C.c_uint64))))
+        return out
+
+    def estimate_skew(self, inp, work_max_side=None, max_deg=None, coarse_step_deg=None, fine_step_deg=None):
+        """ocrs_engine_estimate_skew -> Skew: the angle the page's content is turned by, counter-clockwise, in degrees
+        (defaults: searched within +-15 in steps of 0.5, then 0.1, on a copy of at most 1024 pixels a side)."""
+        p = _skew_struct(work_max_side, max_deg, coarse_step_deg, fine_step_deg)
+        info = _lib.SkewInfo()
+        check(lib().ocrs_engine_estimate_skew(self._h, inp._h, C.byref(p), C.byref(info)))
+        s = Skew()
+        s.angle, s.scores, s.work_hw = float(info.angle_deg), (int(info.best_score), int(info.second_score), int(info.fine_score)), (int(info.work_h), int(info.work_w))
+        s.coarse_index, s.fine_index = int(info.coarse_index), int(info.fine_index)
+        return s
+
+    def warp(self, inp, m, out_hw, fill=0.5):
+        """ocrs_engine_warp_page: the page seen through the affine map m (six coefficients: output pixel -> page position)
+        as a new resident page of out_hw = (height, width); a tap outside the page is `fill`."""
+        return self.warp_batch([inp], [m], [out_hw], [fill])[0]
+
+    def warp_batch(self, inputs, ms, out_hws, fills=0.5):
+        """ocrs_engine_warp_pages: pages of any sizes, each with its own map, size and fill (or one fill for all), in one
+        launch."""
+        n = len(inputs)
+        if not isinstance(fills, (list, tuple, np.ndarray)):
+            fills = [fills] * n
+        if len(ms) != n or len(out_hws) != n or len(fills) != n:
+            raise ValueError("warp_batch: one map, one size and one fill per page")
+        mm = np.ascontiguousarray(np.concatenate([_map_arg(m) for m in ms]) if n else np.zeros(0), np.float32)
+        hw = (C.c_int * (2 * n))(*[int(v) for s in out_hws for v in (s[0], s[1])])
+        fl = np.ascontiguousarray(np.asarray(fills, np.float32).reshape(-1))
+        out = (C.c_void_p * n)()
+        check(lib().ocrs_engine_warp_pages(self._h, _page_array(inputs), C.c_size_t(n), hw, mm.ctypes.data_as(C.POINTER(C.c_float)),
+                                           fl.ctypes.data_as(C.POINTER(C.c_float)), out))
+        return _new_inputs(out, n)
+
+    def deskew(self, inp, angle=None, expand=True, fill=0.5, min_deg=0.2):
+        """The upright page -> (page, m, angle).  angle: the skew in degrees (None: what estimate_skew finds).  m is the
+        map of the warp (deskew_map): unwarp_rects / unwarp_lines with it bring results back to inp's frame.  An |angle|
+        below min_deg leaves the page alone: inp itself comes back, with the identity map."""
+        if angle is None:
+            angle = self.estimate_skew(inp).angle
+        angle = float(angle)
+        hw = inp.shape[-2:]
+        if abs(angle) < min_deg:
+            return inp, deskew_map(hw, 0.0, expand=False)[1], angle
+        out_hw, m = deskew_map(hw, angle, expand=expand)
+        return self.warp(inp, m, out_hw, fill=fill), m, angle
 
     # ---- working resolution (DESIGN.md §7.3)
     def resize(self, inp, size, filter="auto"):
@@ -995,19 +1139,24 @@ class OcrEngine:
         return float(lib().ocrs_engine_detection_threshold(self._h))
 
     # ---- lib.rs:290-300
-    def get_text(self, inp, rectify=False, orientation=None, work_size=None, normalize=None):
+    def get_text(self, inp, rectify=False, orientation=None, work_size=None, normalize=None, deskew=None, deskew_fill=0.5):
         """rectify=True: the same sequence (detect_words, find_text_lines, recognize_text) with rectified crops.
         orientation: None reads the page as given; an int turns it by that many quarter turns counter-clockwise first
         (rotate); "auto" by what detect_orientation finds.
         work_size=(h, w): the words are detected at that size of the (turned) page, lines and text are read from the page at
         its full resolution.
         normalize: None reads the page as given; True or a dict of normalize()'s keywords reads the normalised page
-        (DESIGN.md §7.4).  Applied first; the turn, the work size and the crops are then those of the normalised page."""
+        (DESIGN.md §7.4).  Applied first; the turn, the work size and the crops are then those of the normalised page.
+        deskew: None reads the page as given; a number straightens a skew of that many degrees first, "auto" one of what
+        estimate_skew finds (deskew(); under 0.2 degrees the page is left alone).  Applied after
+        normalisation, which puts paper at +0.5, the default deskew_fill, and after the turn."""
         if normalize is not None and normalize is not False:
             inp = self.normalize(inp, **({} if normalize is True else dict(normalize)))
         if orientation is not None:
             k = self.detect_orientation(inp).quarter_turns if orientation == "auto" else int(orientation)
             inp = self.rotate(inp, k)
+        if deskew is not None:
+            inp = self.deskew(inp, None if deskew == "auto" else float(deskew), fill=deskew_fill)[0]
         if work_size is not None or rectify:
             lines = self.find_text_lines(inp, self.detect_words(inp, work_size=work_size))
             return "\n".join(str(t) for t in self.recognize_text(inp, lines, rectify=rectify) if t is not None)

@@ -86,6 +86,8 @@ DECLARED_SYMBOLS = [
     "ocrs_engine_resize_page", "ocrs_engine_resize_pages", "ocrs_work_size", "ocrs_rescale_rects",
     "ocrs_engine_detect_words_at", "ocrs_engine_detect_words_batch_at",
     "ocrs_normalize_params_default", "ocrs_normalize_params_check", "ocrs_engine_normalize_page", "ocrs_engine_normalize_pages",
+    "ocrs_skew_params_default", "ocrs_skew_params_check", "ocrs_skew_table", "ocrs_engine_skew_scores", "ocrs_engine_estimate_skew",
+    "ocrs_engine_warp_page", "ocrs_engine_warp_pages", "ocrs_deskew_map", "ocrs_unwarp_rects", "ocrs_unwarp_chars",
 ]
 
 ABI_VERSION = 6   # include/ocrs_amd.h OCRS_ABI_VERSION
@@ -105,6 +107,17 @@ class NormalizeInfo(C.Structure):   # include/ocrs_amd.h ocrs_normalize_info
     def as_dict(self):
         return {"dark": int(self.dark), "vote": int(self.vote), "white": int(self.white), "lo": int(self.lo), "hi": int(self.hi),
                 "counted": int(self.counted)}
+
+
+class SkewParams(C.Structure):   # include/ocrs_amd.h ocrs_skew_params
+    _fields_ = [("max_deg", C.c_double), ("coarse_step_deg", C.c_double), ("fine_step_deg", C.c_double), ("work_max_side", C.c_int32),
+                ("reserved", C.c_int32)]
+
+
+class SkewInfo(C.Structure):   # include/ocrs_amd.h ocrs_skew_info
+    _fields_ = [("angle_deg", C.c_double), ("best_score", C.c_uint64), ("second_score", C.c_uint64), ("fine_score", C.c_uint64),
+                ("work_h", C.c_int32), ("work_w", C.c_int32), ("coarse_index", C.c_int32), ("fine_index", C.c_int32)]
+
 
 _lib = None
 

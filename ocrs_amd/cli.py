@@ -80,6 +80,15 @@ def main(argv=None):
                     help="with --normalize: the tile the background is estimated over, a power of two from 16 to 256 (default 64)")
     ap.add_argument("--normalize-polarity", choices=("auto", "keep", "invert"), default=None,
                     help="with --normalize: auto (default) decides by a per-tile vote whether the page is light text on dark")
+    ap.add_argument("--deskew", nargs="?", const="auto", default=None, metavar="auto|DEG",
+                    help="straighten a page that went through the feeder a few degrees off, on the GPU, before reading it: DEG is "
+                         "the skew in degrees, counter-clockwise, at most 45 either way; auto (the default) measures it from the "
+                         "page's projection profiles, within 15 degrees (under 0.2 degrees the page is left alone).  Boxes are "
+                         "reported in the frame of the file as given; the JSON gains \"skew\" (no reference counterpart: "
+                         "DESIGN.md 7.6)")
+    ap.add_argument("--deskew-fill", type=float, default=None, metavar="X",
+                    help="with --deskew: the grey level around the straightened page, -0.5 black .. 0.5 white (default 0.5, the "
+                         "paper of a page that went through --normalize)")
     ap.add_argument("-o", "--output")
     ap.add_argument("--debug", action="store_true")
     ap.add_argument("--text-map", action="store_true", help="write text-map.png (detect_text_pixels)")
@@ -96,6 +105,15 @@ def main(argv=None):
         ap.error("--detection-confidence is only valid with -j/--json")
     if (args.normalize_tile is not None or args.normalize_polarity is not None) and not args.normalize:
         ap.error("--normalize-tile and --normalize-polarity are only valid with --normalize")
+    if args.deskew_fill is not None and args.deskew is None:
+        ap.error("--deskew-fill is only valid with --deskew")
+    if args.deskew is not None and args.deskew != "auto":
+        try:
+            args.deskew = float(args.deskew)
+        except ValueError:
+            ap.error("--deskew takes auto or a number of degrees")
+        if not abs(args.deskew) <= 45.0:
+            ap.error("--deskew: at most 45 degrees either way (--orientation turns by quarter turns)")
 
     from . import DecodeMethod, DimOrder, ImageSource, Model, OcrEngine, models, output
     from ._lib import OcrsError
@@ -142,6 +160,20 @@ def main(argv=None):
         else:
             turns = int(args.orientation) // 90
         inp = engine.rotate(inp, turns)
+    skew, skew_map = None, None
+    if args.deskew is not None:   # from here on the upright page is the page; results are mapped back before output
+        skew = args.deskew
+        if skew == "auto":
+            found = engine.estimate_skew(inp)
+            skew = found.angle
+            if args.debug:
+                print("Skew: %.1f degrees (scores: best coarse %d, runner-up %d, at the angle %d; taken at %dx%d)"
+                      % (skew, found.scores[0], found.scores[1], found.scores[2], found.work_hw[1], found.work_hw[0]))
+        upright, m, _ = engine.deskew(inp, skew, fill=0.5 if args.deskew_fill is None else args.deskew_fill)
+        if upright is inp:
+            skew = 0.0
+        else:
+            inp, skew_map = upright, m
     tiled = False if args.tiled is None else True if args.tiled < 0 else args.tiled
     work_hw = None   # the size the detector sees the (turned) page at: DESIGN.md 7.3
     if args.work_scale is not None or args.work_max_side is not None:
@@ -172,6 +204,11 @@ def main(argv=None):
         for i, line in enumerate(lines):
             write_image("lines/line-%d.png" % i, engine.prepare_recognition_input(inp, line, rectify=args.rectify) + np.float32(0.5))
     texts = engine.recognize_text(inp, lines, scores=args.confidence, rectify=args.rectify)
+    if skew_map is not None:
+        from . import unwarp_lines, unwarp_rects
+        texts = unwarp_lines(texts, skew_map)
+        if word_boxes is not None:
+            word_boxes = [[(unwarp_rects([r], skew_map)[0], s, n) for r, s, n in boxes] for boxes in word_boxes]
     if turns is not None:
         from . import unrotate_lines, unrotate_rects
         texts = unrotate_lines(texts, tuple(shape_hw), turns)
@@ -179,7 +216,7 @@ def main(argv=None):
             word_boxes = [[(unrotate_rects([r], tuple(shape_hw), turns)[0], s, n) for r, s, n in boxes] for boxes in word_boxes]
     if args.json:
         content = output.format_json_output(args.image, tuple(shape_hw), texts, confidence=args.confidence, word_boxes=word_boxes,
-                                            orientation=None if turns is None else 90 * turns, normalize=norm_info)
+                                            orientation=None if turns is None else 90 * turns, normalize=norm_info, skew=skew)
     else:
         content = output.format_text_output(texts)
     if args.output:

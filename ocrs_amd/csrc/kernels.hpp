@@ -365,6 +365,33 @@ struct NormDesc {        // one page to normalise: dst [h, w] from src [h, w]
 // states must be zero when the first launch starts.  d_info[n_pages] receives each page's NormInfo.
 void normalize_pages(const NormDesc* d_descs, int n_pages, int total_blocks, NormInfo* d_info, hipStream_t s);
 
+// ---- kernels_deskew.hip ------------------------------------
+struct SkewDesc {        // one page whose skew profiles are taken
+    const float* src;    // [h, w]
+    uint32_t* prof;      // [n_angles, nb] the page's profiles; zero when the launch starts
+    int32_t h, w;        // each 1 .. 4096
+    int32_t nb;          // h + w: dwords per profile
+    int32_t block0;      // first block of this page: the sum of skew_tiles() of the pages before it
+};
+int64_t skew_tiles(int h, int w);   // blocks a page of this size takes (host)
+// Pages of any mix of sizes, two launches on `s`; total_tiles = the sum of skew_tiles() over the pages.  d_sc_table:
+// int32 [n_angles, 2] (S, C), each within +-65536.  d_scores [n_pages, n_angles].  n_pages <= 65535.
+void skew_scores(const SkewDesc* d_descs, int n_pages, int total_tiles, const int32_t* d_sc_table, int n_angles,
+                 unsigned long long* d_scores, hipStream_t s);
+struct WarpDesc {        // one page to warp: dst [dh, dw] from src [sh, sw]
+    const float* src;
+    float* dst;          // never overlaps src
+    int32_t sh, sw, dh, dw;   // each 1 .. 65535
+    int32_t block0;      // first block of this page: the sum of warp_blocks() of the pages before it
+    int32_t vec;         // dw % 4 == 0 and dst 16-byte aligned, so 16-byte stores are safe
+    float m[6];          // X = (m0 + m1 fx) + m2 fy, Y = (m3 + m4 fx) + m5 fy
+    float fill;          // a tap outside the page
+    int32_t pad_;
+};
+int64_t warp_blocks(int dh, int dw);   // blocks an output of this size takes (host)
+// Pages of any mix of sizes and maps in one launch; total_blocks = the sum of warp_blocks() over the pages.
+void warp_pages(const WarpDesc* d_descs, int n_pages, int total_blocks, hipStream_t s);
+
 // kernels_peaks.hip
 void measure_peaks(double* mfma_tflops, double* copy_gbps);
 

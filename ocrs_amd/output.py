@@ -15,7 +15,7 @@ def rounded_vertex_coords(rect6):
     return [[_rround(x), _rround(y)] for x, y in rotated_rect_corners(rect6)]
 
 
-def ocr_json(input_path, input_hw, text_lines, confidence=False, word_boxes=None, orientation=None, normalize=None):
+def ocr_json(input_path, input_hw, text_lines, confidence=False, word_boxes=None, orientation=None, normalize=None, skew=None):
     """output.rs:34-76.  text_lines: list of TextLine | None.  confidence (no reference counterpart): every line and word
     object also gets "confidence" (TextLine / TextWord.confidence; the lines must come from a scored recognize_text).
     word_boxes (no reference counterpart; indexed like text_lines): per line the detector's word boxes in reading order as
@@ -23,7 +23,9 @@ def ocr_json(input_path, input_hw, text_lines, confidence=False, word_boxes=None
     orientation (no reference counterpart): the degrees the page was turned counter-clockwise before it was read; the top
     level then gets "orientation" (the boxes given here are already in the frame of the file).
     normalize (no reference counterpart): what OcrEngine.normalize(info=True) found on the page; the top level then gets
-    "normalize": {"counted", "dark", "hi", "lo", "vote", "white"}."""
+    "normalize": {"counted", "dark", "hi", "lo", "vote", "white"}.
+    skew (no reference counterpart): the degrees of skew the page was straightened by before it was read (0 when it was
+    left alone); the top level then gets "skew" (the boxes given here are already in the frame of the file)."""
     line_items = []
     for li, line in enumerate(text_lines):
         if line is None:
@@ -45,14 +47,16 @@ def ocr_json(input_path, input_hw, text_lines, confidence=False, word_boxes=None
         doc["orientation"] = int(orientation)
     if normalize is not None:
         doc["normalize"] = {k: int(normalize[k]) for k in ("counted", "dark", "hi", "lo", "vote", "white")}
+    if skew is not None:
+        doc["skew"] = float(skew)
     return doc
 
 
-def format_json_output(input_path, input_hw, text_lines, confidence=False, word_boxes=None, orientation=None, normalize=None):
+def format_json_output(input_path, input_hw, text_lines, confidence=False, word_boxes=None, orientation=None, normalize=None, skew=None):
     """output.rs:98-101 (serde_json::to_string_pretty).  serde_json without `preserve_order` keeps `json!` maps in a
     BTreeMap, so the reference emits every object's keys in alphabetical order (ocrs-cli/test-data/
     format-json-expected.json: image_height, image_width, paragraphs, url / text, vertices, words): sort_keys."""
-    return json.dumps(ocr_json(input_path, input_hw, text_lines, confidence, word_boxes, orientation, normalize), indent=2, ensure_ascii=False,
+    return json.dumps(ocr_json(input_path, input_hw, text_lines, confidence, word_boxes, orientation, normalize, skew), indent=2, ensure_ascii=False,
                       sort_keys=True)
 
 
