@@ -103,6 +103,14 @@ OCRS_API ocrs_status ocrs_gru_tile_plan(const int32_t* lengths_desc, size_t n_li
 OCRS_API ocrs_status ocrs_coalescer_selftest(int n_threads, int requests_per_thread, int max_active, int max_pages,
                                              long window_us, int fail_every, uint64_t out[5]);
 
+/* Test hook (host only, no GPU work) for the stream plan of a device (option "stream_budget"): a plan of `budget` streams is
+ * driven through n_ops operations, ops = n_ops pairs {op, arg}, one result each in out:
+ *   0 a call starts, avoiding light lane arg (-1: none) -> its light lane, -1 = a stream of its own (budget 0)
+ *   1 a call on lane arg ends                           -> calls still in flight
+ *   2 the budget becomes arg                            -> 1 taken up, 0 refused (a call is in flight, or not 0 / 3 .. 16)
+ *   3 calls on light lane arg, 4 the budget, 5 the number of light lanes. */
+OCRS_API ocrs_status ocrs_stream_plan_selftest(int budget, const int32_t* ops, size_t n_ops, int32_t* out);
+
 /* Integer tuning options (no reference counterpart: RTen's equivalents are compile-time).  They select between kernels
  * that compute the SAME bits — results never depend on an option; the tests run the alternatives against each other.
  *
@@ -136,6 +144,11 @@ OCRS_API ocrs_status ocrs_coalescer_selftest(int n_threads, int requests_per_thr
  *   "beam_gpu"        1 = DecodeMethod::BeamSearch runs on the GPU (default), 0 = on the host (threaded over lines)
  *   "det_tile_batch"  tiled detection (ocrs_engine_detect_words_tiled ...): tiles per run of the detection model, 1 .. 1024
  *                     (default 16); bounds the activation memory of a request whatever its page sizes, never changes a result
+ *   "stream_budget"   streams a device uses, 3 .. 16 (default 4, the hardware queues the runtime opens by default): one for
+ *                     the recognition conv stacks, one for the recurrences, the rest shared by everything else of all calls
+ *                     in flight, each call on the least loaded; 0 = a stream per call in flight, as before this option.  A
+ *                     device's plan serves every engine on it: a process option only (ocrs_engine_set_option refuses it),
+ *                     taken up by a device between calls, and OCRS_ERR_INVALID_ARGUMENT while a call is in flight on one
  *
  * OCRS_ERR_INVALID_ARGUMENT for an unknown name.  (Rounds 2-4 carried 28 process-wide options, many of them switches for
  * experiments that had lost their A/B; round 5 removed those kernels and moved what is configuration — numerics, request
@@ -172,7 +185,7 @@ OCRS_API ocrs_status ocrs_device_pool_trim(int device);
  * request.  device < 0: the default device. */
 typedef enum { OCRS_ISOLATION_AUTO = 0, OCRS_ISOLATION_NONE = 1 } ocrs_isolation;
 OCRS_API ocrs_status ocrs_device_set_isolation(int device, ocrs_isolation policy);
-/* out = {what a request starting now is told: 0 free (own stream per call), 1 serial (one stream);
+/* out = {what a request starting now is told: 0 free (the lanes of option "stream_budget"), 1 serial (one stream);
  *        engines with numerics != exact alive on the device; compute units of the device}. */
 OCRS_API ocrs_status ocrs_device_isolation(int device, int out[3]);
 

@@ -68,6 +68,26 @@ ocrs_status ocrs_coalescer_selftest(int n_threads, int requests_per_thread, int 
     });
 }
 
+// Host-only test hook for stream_plan.hpp (the devices' plans need a GPU to be driven through requests).
+ocrs_status ocrs_stream_plan_selftest(int budget, const int32_t* ops, size_t n_ops, int32_t* out) {
+    return guarded([&] {
+        if (!out || (n_ops > 0 && !ops) || !LanePlan::valid_budget(budget)) fail(OCRS_ERR_INVALID_ARGUMENT, "bad argument");
+        LanePlan plan(budget);
+        for (size_t i = 0; i < n_ops; i++) {
+            const int32_t op = ops[2 * i], arg = ops[2 * i + 1];
+            switch (op) {
+                case 0: out[i] = plan.acquire(arg); break;
+                case 1: plan.release(arg); out[i] = plan.outstanding(); break;
+                case 2: out[i] = plan.set_budget(arg) ? 1 : 0; break;
+                case 3: out[i] = plan.load(arg); break;
+                case 4: out[i] = plan.budget(); break;
+                case 5: out[i] = plan.light_lanes(); break;
+                default: fail(OCRS_ERR_INVALID_ARGUMENT, "unknown op %d", (int)op);
+            }
+        }
+    });
+}
+
 namespace {
 
 // ocrs_ctc_beam_search[_scored]: score / step_logp null for the unscored hook
@@ -156,6 +176,8 @@ uint32_t ocrs_abi_version(void) { return OCRS_ABI_VERSION; }
 static void check_option_set(int r, const char* name, long value) {   // what set_option (common.hpp) returned
     if (r == 1) fail(OCRS_ERR_INVALID_ARGUMENT, "unknown option '%s'", name ? name : "(null)");
     if (r == 2) fail(OCRS_ERR_INVALID_ARGUMENT, "option '%s': value %ld is out of range", name, value);
+    if (r == 3) fail(OCRS_ERR_INVALID_ARGUMENT, "option '%s' cannot change while a request is in flight on a device", name);
+    if (r == 4) fail(OCRS_ERR_INVALID_ARGUMENT, "option '%s' belongs to the devices, not to an engine: set it with ocrs_set_option", name);
 }
 
 ocrs_status ocrs_set_option(const char* name, long value) {
@@ -405,14 +427,16 @@ ocrs_status ocrs_engine_prepare_input_batch(const ocrs_engine* e, const void* co
         for (size_t i = 0; i < n; i++) check_image_args(pixels[i], height, width, channels);
         Workspace ws;
         const size_t bytes = (size_t)height * width * channels * (type == OCRS_U8 ? 1 : 4);
-        std::vector<std::unique_ptr<ocrs_page>> made;   // freed if a later page fails
+        // every copy is queued, then ONE conversion launch over all pages, before the one wait below: from pinned memory
+        // (ocrs_host_malloc) the copies are DMA transfers back to back; the conversion of all pages together takes less
+        // than one page's copy, and a launch per page was sixteen packets per request in the lane's queue
+        std::vector<const void*> d_px(n);
         for (size_t i = 0; i < n; i++) {
-            // every copy and conversion is queued before the one wait below: from pinned memory (ocrs_host_malloc)
-            // the copies are DMA transfers that overlap the conversion kernels of the pages before them
-            void* d_px = ws.alloc(bytes);
-            OCRS_HIP(hipMemcpyAsync(d_px, pixels[i], bytes, hipMemcpyHostToDevice, ws.s()));
-            made.emplace_back(make_page(d_px, type, order, height, width, channels, ws.s(), e->tm()));
+            void* d = ws.alloc(bytes);
+            OCRS_HIP(hipMemcpyAsync(d, pixels[i], bytes, hipMemcpyHostToDevice, ws.s()));
+            d_px[i] = d;
         }
+        std::vector<std::unique_ptr<ocrs_page>> made = make_pages(d_px.data(), n, type, order, height, width, channels, ws.s(), e->tm());
         ws.sync();
         if (e->tm()) e->tm()->collect();
         for (size_t i = 0; i < n; i++) out[i] = made[i].release();

@@ -65,6 +65,22 @@ ocrs_page* make_page(const void* d_pixels, ocrs_pixel_type type, ocrs_dim_order 
     return page.release();
 }
 
+std::vector<std::unique_ptr<ocrs_page>> make_pages(const void* const* d_pixels, size_t n, ocrs_pixel_type type, ocrs_dim_order order,
+                                                   int height, int width, int channels, hipStream_t st, StageTimers* T) {
+    std::vector<std::unique_ptr<ocrs_page>> made;
+    std::vector<float*> outs;
+    for (size_t i = 0; i < n; i++) {
+        made.push_back(new_page(height, width));
+        outs.push_back(made.back()->grey.as<float>());
+    }
+    if (n) {
+        StageScope sc(T, ST_PREPARE, st, (n + k::PrepareTable::kPages - 1) / k::PrepareTable::kPages);
+        k::prepare_image_batch(d_pixels, outs.data(), (int)n, type == OCRS_U8, order == OCRS_HWC, height, width, channels, st);
+    }
+    OCRS_HIP(hipGetLastError());
+    return made;
+}
+
 void check_image_args(const void* pixels, int height, int width, int channels) {
     if (!pixels) fail(OCRS_ERR_INVALID_ARGUMENT, "pixels is null");
     // ImageSource::from_tensor (preprocess.rs:116-122)

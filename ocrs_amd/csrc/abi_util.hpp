@@ -112,6 +112,9 @@ std::vector<std::vector<geom::RotatedRect>> unpack_lines(const float* rects, con
 // OcrEngine::prepare_input on pixels that are already on the bound device (launch only, no sync)
 ocrs_page* make_page(const void* d_pixels, ocrs_pixel_type type, ocrs_dim_order order, int height, int width, int channels,
                      hipStream_t st, StageTimers* T);
+// the same for the n pages of one call (one size, one format) in one launch (k::prepare_image_batch); same bits
+std::vector<std::unique_ptr<ocrs_page>> make_pages(const void* const* d_pixels, size_t n, ocrs_pixel_type type, ocrs_dim_order order,
+                                                   int height, int width, int channels, hipStream_t st, StageTimers* T);
 void check_image_args(const void* pixels, int height, int width, int channels);
 // OcrEngine::new (lib.rs:132-180)
 std::unique_ptr<ocrs_engine> make_engine(const ocrs_engine_params& params);

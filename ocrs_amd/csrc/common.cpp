@@ -40,6 +40,14 @@ DeviceContext& device_context(int device) {
     return *c;
 }
 
+static bool any_device_has_calls_in_flight() {
+    for (auto& slot : g_ctx) {
+        DeviceContext* c = slot.load(std::memory_order_acquire);
+        if (c && c->calls_in_flight()) return true;
+    }
+    return false;
+}
+
 int default_device() { return g_default_device.load(); }
 
 void select_device(int device) {
@@ -326,35 +334,59 @@ PoolStats HostPool::stats() {
     return st;
 }
 
+// Every stream of the device's plan is created here, under lazy_mu_, in one fixed order: conv lane, recurrence lane, light
+// lanes.  The first call on a device creates the whole budget at once, so which hardware queue a lane lands on does not
+// depend on which request happened to come first.
+void DeviceContext::create_lanes_locked(int n_light) {
+    if (heavy_ && recurrent_ && (int)light_.size() >= n_light) return;
+    // All at the highest queue priority.  The conv stacks are the critical resource of the pipeline: their stream never runs
+    // dry in steady state and a step takes as long as its conv stack does.  (Round 1 ran this stream at the LOWEST
+    // priority so that the 1 200 dependent GRU step launches of a request would get freed CU slots first; with
+    // the recurrence in one persistent launch per layer that reason is gone.  The GPU is work-conserving — every
+    // combination of stream priorities measured the same 256-259 pages/s — but here the dominant kernels are
+    // stretched least by what runs beside them: 9.9-10.4 ms per launch against 11.2-11.4.)
+    // Round 3 tried the lowest priority again: +0.8 % on the 16-page bench — and 2-8 pages/s instead of 180 for one-page
+    // calls from 12 threads (detect latencies of seconds): its kernels starve as long as any other request has something queued.
+    DeviceScope bind(device);
+    int least = 0, greatest = 0;
+    OCRS_HIP(hipDeviceGetStreamPriorityRange(&least, &greatest));
+    if (!heavy_) OCRS_HIP(hipStreamCreateWithPriority(&heavy_, hipStreamNonBlocking, greatest));
+    if (!recurrent_) OCRS_HIP(hipStreamCreateWithPriority(&recurrent_, hipStreamNonBlocking, greatest));
+    while ((int)light_.size() < n_light) {
+        hipStream_t s = nullptr;
+        OCRS_HIP(hipStreamCreateWithPriority(&s, hipStreamNonBlocking, greatest));
+        light_.push_back(s);
+    }
+}
+
+// light lanes of the plan as a call starting now would find it (the option is taken up when no call holds a lease)
+int DeviceContext::planned_light_lanes() {
+    (void)plan.set_budget((int)process_option(OPT_STREAM_BUDGET));
+    return plan.light_lanes();
+}
+
 hipStream_t DeviceContext::heavy_stream() {
     std::lock_guard<std::mutex> g(lazy_mu_);
-    if (!heavy_) {
-        // Highest queue priority.  The conv stacks are the critical resource of the pipeline: their stream never runs
-        // dry in steady state and a step takes as long as its conv stack does.  (Round 1 ran this stream at the LOWEST
-        // priority so that the 1 200 dependent GRU step launches of a request would get freed CU slots first; with
-        // the recurrence in one persistent launch per layer that reason is gone.  The GPU is work-conserving — every
-        // combination of stream priorities measured the same 256-259 pages/s — but here the dominant kernels are
-        // stretched least by what runs beside them: 9.9-10.4 ms per launch against 11.2-11.4.)
-        // Round 3 tried the lowest priority again: +0.8 % on the 16-page bench — and 2-8 pages/s instead of 180 for one-page
-        // calls from 12 threads (detect latencies of seconds): its kernels starve as long as any other request has something queued.
-        DeviceScope bind(device);
-        int least = 0, greatest = 0;
-        OCRS_HIP(hipDeviceGetStreamPriorityRange(&least, &greatest));
-        OCRS_HIP(hipStreamCreateWithPriority(&heavy_, hipStreamNonBlocking, greatest));
-    }
+    create_lanes_locked(planned_light_lanes());
     return heavy_;
 }
 
 hipStream_t DeviceContext::recurrent_stream(int mode) {
     if (mode == MODE_SERIAL) return heavy_stream();
     std::lock_guard<std::mutex> g(lazy_mu_);
-    if (!recurrent_) {
-        DeviceScope bind(device);
-        int least = 0, greatest = 0;
-        OCRS_HIP(hipDeviceGetStreamPriorityRange(&least, &greatest));
-        OCRS_HIP(hipStreamCreateWithPriority(&recurrent_, hipStreamNonBlocking, greatest));
-    }
+    create_lanes_locked(planned_light_lanes());
     return recurrent_;
+}
+
+hipStream_t DeviceContext::light_lane(int lane) {
+    std::lock_guard<std::mutex> g(lazy_mu_);
+    create_lanes_locked(std::max(lane + 1, plan.light_lanes()));
+    return light_[lane];
+}
+
+bool DeviceContext::calls_in_flight() {
+    std::lock_guard<std::mutex> lk(iso_mu_);
+    return leases_ > 0;
 }
 
 // per host thread and device: leases the thread already holds (a nested lease must not wait for a switch that waits for it)
@@ -442,6 +474,7 @@ const OptDef kOptDefs[OPT_COUNT] = {
     {"conv_flat", "OCRS_CONV_FLAT", 1},                 // recognition 3x3 convs: patches tile a width group's whole strip of images (0: every image on its own)
     {"beam_gpu", "OCRS_BEAM_GPU", 1},                   // 1 CTC beam search on the GPU, 0 on the host
     {"det_tile_batch", "OCRS_DET_TILE_BATCH", 16},      // tiled detection: tiles per model run (bounds a request's activation memory)
+    {"stream_budget", "OCRS_STREAM_BUDGET", LanePlan::kDefaultBudget},   // streams per device: conv lane, recurrence lane, budget - 2 light lanes; 0 = a stream per call (stream_plan.hpp)
     // not options: ocrs_engine_params fields (no name, no environment variable)
     // (ocrs_engine_set_option accepts these names too, except numerics: an engine's numerics are fixed when it is created)
     {"numerics", nullptr, 0},                           // exact
@@ -456,11 +489,12 @@ const OptDef kOptDefs[OPT_COUNT] = {
 struct OptRange { long lo, hi; long also[4]; };
 const OptRange kOptRanges[OPT_COUNT] = {
     {0, 1, {}}, {0, 1, {}}, {0, 1, {}}, {0, 2, {}}, {0, 1, {8, 14, 32}}, {0, 1, {8, 14, 20, 32}}, {0, 1, {}}, {0, 1, {}}, {0, 1, {}}, {0, 1, {}},
-    {1, 1024, {}},
+    {1, 1024, {}}, {LanePlan::kMinBudget, LanePlan::kMaxBudget, {}},   // (stream_budget: also 0, see in_range)
     {0, 2, {}}, {0, 64, {}}, {1, 4096, {}}, {0, 10000000, {}}, {0, 4096, {}}, {0, INT64_MAX, {}},
 };
 bool in_range(int i, long v) {
     const OptRange& r = kOptRanges[i];
+    if (i == OPT_STREAM_BUDGET) return LanePlan::valid_budget(v);
     if (v >= r.lo && v <= r.hi) return true;
     for (long a : r.also) if (a && v == a) return true;
     return false;
@@ -491,6 +525,11 @@ TuningScope::TuningScope(const Tuning* t) : prev_(t_tuning) { t_tuning = t; }
 TuningScope::~TuningScope() { t_tuning = prev_; }
 const Tuning* current_tuning() { return t_tuning; }
 
+long process_option(Option o) {
+    std::call_once(g_opts_once, init_options);
+    return g_opts[o].load(std::memory_order_relaxed);
+}
+
 long option_long(Option o) {
     // relaxed atomic accesses: ocrs_engine_set_option may run while another thread serves a request of the same engine
     if (t_tuning) return __atomic_load_n(&t_tuning->v[o], __ATOMIC_RELAXED);
@@ -516,6 +555,8 @@ int set_option(const char* name, long value) {
         return 1;
     }
     if (!in_range(i, value)) return 2;
+    // the stream plan belongs to the devices, not to a request: it changes only between calls
+    if (i == OPT_STREAM_BUDGET && value != g_opts[i].load() && any_device_has_calls_in_flight()) return 3;
     g_opts[i].store(value);
     return 0;
 }
@@ -523,6 +564,7 @@ int set_option(const char* name, long value) {
 int set_option(Tuning& t, const char* name, long value) {
     const int i = find_option(name, OPT_COUNT);   // an engine's copy: also the configuration fields, by their field names
     if (i < 0) return 1;
+    if (i == OPT_STREAM_BUDGET) return 4;         // a device's plan serves every engine on it: the process option only
     if (!in_range(i, value)) return 2;
     __atomic_store_n(&t.v[i], value, __ATOMIC_RELAXED);
     return 0;
@@ -537,22 +579,44 @@ bool get_option(const Tuning& t, const char* name, long* value) {
 }
 
 // ---------------------------------------------------------------- streams
-StreamLease::StreamLease(bool high_priority) : ctx_(&ctx()), high_(high_priority) {
-    high_ = true;  // every request stream outranks nothing and is outranked by nothing: all at the highest priority (see heavy_stream())
+static hipEvent_t take_lease_event(DeviceContext* c) {
+    {
+        std::lock_guard<std::mutex> g(c->stream_mu);
+        if (!c->lease_events.empty()) {
+            hipEvent_t e = c->lease_events.back();
+            c->lease_events.pop_back();
+            return e;
+        }
+    }
+    hipEvent_t e = nullptr;
+    OCRS_HIP(hipEventCreateWithFlags(&e, hipEventBlockingSync | hipEventDisableTiming));
+    return e;
+}
+
+StreamLease::StreamLease(bool high_priority, int avoid_lane) : ctx_(&ctx()), high_(high_priority) {
+    high_ = true;  // every request stream outranks nothing and is outranked by nothing: all at the highest priority (see create_lanes_locked())
     mode_ = ctx_->lease_begin();
     try {
+        done_ = take_lease_event(ctx_);
         if (mode_ == DeviceContext::MODE_SERIAL) {   // one stream for everything on this device; the lease owns only its event
             s_ = ctx_->heavy_stream();
             shared_ = true;
-            OCRS_HIP(hipEventCreateWithFlags(&done_, hipEventBlockingSync | hipEventDisableTiming));
+            return;
+        }
+        // The budget is taken up between calls: with this lease the only one in flight the plan follows the option, with
+        // others in flight set_budget refuses and this call joins the plan they run on.
+        (void)ctx_->planned_light_lanes();
+        lane_ = ctx_->plan.acquire(avoid_lane);
+        counted_ = true;
+        if (lane_ >= 0) {
+            s_ = ctx_->light_lane(lane_);
             return;
         }
         {
             std::lock_guard<std::mutex> g(ctx_->stream_mu);
             auto& v = ctx_->streams;
             if (!v.empty()) {
-                s_ = v.back().first;
-                done_ = v.back().second;
+                s_ = v.back();
                 v.pop_back();
                 return;
             }
@@ -560,20 +624,24 @@ StreamLease::StreamLease(bool high_priority) : ctx_(&ctx()), high_(high_priority
         int least = 0, greatest = 0;
         OCRS_HIP(hipDeviceGetStreamPriorityRange(&least, &greatest));
         OCRS_HIP(hipStreamCreateWithPriority(&s_, hipStreamNonBlocking, greatest));
-        OCRS_HIP(hipEventCreateWithFlags(&done_, hipEventBlockingSync | hipEventDisableTiming));
     } catch (...) {
+        if (counted_) ctx_->plan.release(lane_);
+        if (done_) {
+            std::lock_guard<std::mutex> g(ctx_->stream_mu);
+            ctx_->lease_events.push_back(done_);
+        }
         ctx_->lease_end();
         throw;
     }
 }
 
 StreamLease::~StreamLease() {
-    if (shared_) {
-        (void)hipEventDestroy(done_);
-    } else {
+    {
         std::lock_guard<std::mutex> g(ctx_->stream_mu);
-        ctx_->streams.emplace_back(s_, done_);
+        ctx_->lease_events.push_back(done_);
+        if (!shared_ && lane_ < 0) ctx_->streams.push_back(s_);
     }
+    if (counted_) ctx_->plan.release(lane_);
     ctx_->lease_end();
 }
 

@@ -19,6 +19,7 @@
 #include <vector>
 
 #include "../../include/ocrs_amd.h"
+#include "stream_plan.hpp"
 
 namespace ocrs {
 
@@ -52,8 +53,8 @@ void set_last_error(const std::string& msg);
 // binds the calling host thread to its handle's device for the duration of the call (DeviceScope) — HIP's current
 // device is per host thread.  One process can therefore drive several GPUs (ocrs_engine_group_*), or one GPU per
 // process (ocrs_set_device = the default device of handles created without an explicit one).
-// Everything that used to be a process singleton — the caching allocators, the stream pool, the shared conv-stack
-// and recurrence streams with the mutexes that order submissions to them — lives in the device's DeviceContext.
+// Everything that used to be a process singleton — the caching allocators, the stream plan with its lanes (the shared
+// conv-stack and recurrence streams and the mutexes that order submissions to them) — lives in the device's DeviceContext.
 // ---------------------------------------------------------------------------------------------------------
 
 // Size-bucketed caching allocator: hipMalloc is far too slow to sit on the
@@ -109,8 +110,10 @@ struct DeviceContext {
     HostPool host_pool;
     // One stream per device for the throughput-bound conv stacks of all in-flight requests (model.cpp), and one
     // for the persistent GRU recurrences (kernels_gru.hip): their workgroups wait on each other, so they are
-    // serialised on the device; both at the highest queue priority.  The *_phase mutexes keep "record event, make
-    // the shared stream wait, launch, record, make the request stream wait" atomic per request.
+    // serialised on the device; both at the highest queue priority (the conv lane and the recurrence lane of
+    // stream_plan.hpp).  The *_phase mutexes keep "record event, make the shared stream wait, launch, record" atomic
+    // per request; the request then waits for that last event with the mutex released (on the host where its stream
+    // is a lane shared with other calls).
     std::mutex heavy_phase, rec_phase;
     hipStream_t heavy_stream();
     hipStream_t recurrent_stream(int mode = 0);   // of a request in Mode `mode`: MODE_SERIAL -> the device's one stream
@@ -137,9 +140,16 @@ struct DeviceContext {
     // intermediate activations of the conv stacks that run on heavy_stream(): shared by all requests (stream order is
     // the exclusion), guarded by heavy_phase; see HipModel::run_prefix_ragged
     std::vector<struct DevBuf> heavy_arena;
-    // recycled per-call streams (StreamLease)
+    // ---- the stream plan (stream_plan.hpp): the device's lanes, or at stream budget 0 the recycled per-call streams
+    // (StreamLease).  The budget is the process default of option "stream_budget" and is taken up when a call starts
+    // with no other call in flight on the device.
     std::mutex stream_mu;
-    std::vector<std::pair<hipStream_t, hipEvent_t>> streams;
+    LanePlan plan;
+    std::vector<hipStream_t> streams;        // budget 0: private streams not in use
+    std::vector<hipEvent_t> lease_events;    // "my last enqueue has finished" events not in use (one per call, on any plan)
+    hipStream_t light_lane(int lane);        // created with the other lanes on first use
+    int planned_light_lanes();               // takes up the option if no call holds a lease; the plan's light lanes
+    bool calls_in_flight();                  // the option system asks before it lets "stream_budget" change
 
     explicit DeviceContext(int d) : device(d), pool(d) {}
 
@@ -148,6 +158,8 @@ struct DeviceContext {
     template <class F> void switch_isolation(F&& change);
     std::mutex lazy_mu_;
     hipStream_t heavy_ = nullptr, recurrent_ = nullptr;
+    std::vector<hipStream_t> light_;
+    void create_lanes_locked(int n_light);   // conv lane, recurrence lane, light lanes: in that order, whatever is missing
     int cus_ = 0;
     std::mutex iso_mu_;
     std::condition_variable iso_cv_;
@@ -190,14 +202,15 @@ inline hipStream_t heavy_stream() { return ctx().heavy_stream(); }
 // thread (TuningScope); code outside an engine call (ocrs_model_run on a bare model) sees the process defaults.
 // The entries after OPT_PUBLIC_COUNT are not options: they are fields of ocrs_engine_params that travel the same way.
 enum Option { OPT_GRU_MODE = 0, OPT_GRU_GATES, OPT_GRU_LOCAL, OPT_DET_FUSE, OPT_DET_STREAM, OPT_DET_ROWS, OPT_CCL_QUAD,
-              OPT_CONV12_FUSE, OPT_CONV_FLAT, OPT_BEAM_GPU, OPT_DET_TILE_BATCH, OPT_PUBLIC_COUNT,
+              OPT_CONV12_FUSE, OPT_CONV_FLAT, OPT_BEAM_GPU, OPT_DET_TILE_BATCH, OPT_STREAM_BUDGET, OPT_PUBLIC_COUNT,
               OPT_NUMERICS = OPT_PUBLIC_COUNT,   // ocrs_engine_params.numerics: 0 exact (the numeric spec), 1 relaxed, 2 reduced
               OPT_COALESCE, OPT_COALESCE_PAGES, OPT_COALESCE_WINDOW_US,   // ocrs_engine_params.coalesce*
               OPT_LAYOUT_THREADS, OPT_REC_MAX_PIXELS,                     // ocrs_engine_params.layout_threads / rec_max_pixels
               OPT_COUNT };
 struct Tuning { long v[OPT_COUNT]; };
 Tuning default_tuning();                                   // the process defaults as they are now
-// 0 = set (or a retired name: accepted, ignored), 1 = unknown name, 2 = value outside the option's range
+// 0 = set (or a retired name: accepted, ignored), 1 = unknown name, 2 = value outside the option's range,
+// 3 = "stream_budget" while a call is in flight on some device, 4 = "stream_budget" on an engine (it is a device's)
 int set_option(const char* name, long value);             // process default
 int set_option(Tuning& t, const char* name, long value);  // one engine's copy (safe while the engine serves requests)
 bool get_option(const Tuning& t, const char* name, long* value);
@@ -214,6 +227,7 @@ class TuningScope {   // installs `t` for the calling thread for the lifetime of
 const Tuning* current_tuning();   // what the calling thread has installed (nullptr: none) — handed to worker threads
 enum { GRU_PERSISTENT = 0, GRU_STEP = 1 };
 int option(Option o);
+long process_option(Option o);   // the process default, whatever the calling thread has installed
 
 // Kernels that need more than 64 KB of dynamic LDS have to opt in with hipFuncSetAttribute — per DEVICE (the function
 // object belongs to the device that is current): once per (kernel, device), remembered in `done` (bit = device ordinal
@@ -262,27 +276,37 @@ struct PinnedBuf {
     template <class T> T* as() const { return static_cast<T*>(p); }
 };
 
-// One stream per API call, recycled: calls from different host threads run on
-// different streams (the reference calls Model::run concurrently,
-// recognition.rs:465-485).
+// Host wait for an event that has been recorded.  hipStreamSynchronize / hipEventSynchronize spin a core for the
+// whole wait here (measured: every request thread at ~100 % CPU, also with hipEventBlockingSync), which with
+// several requests in flight per process and several processes per host costs more cores than the layout
+// analysis does.  So: poll briefly, then sleep between polls (<= 0.1 ms added latency).
+inline hipError_t wait_event(hipEvent_t ev) noexcept {
+    for (int i = 0;; i++) {
+        const hipError_t e = hipEventQuery(ev);
+        if (e != hipErrorNotReady) return e;
+        if (i < 64) std::this_thread::yield();
+        else std::this_thread::sleep_for(std::chrono::microseconds(i < 256 ? 20 : 100));
+    }
+}
+
+// The stream of one API call: one of the device's light lanes, shared with the other calls the plan dealt to it
+// (stream_plan.hpp), or at stream budget 0 a recycled stream of its own.  Calls from different host threads run
+// concurrently either way (the reference calls Model::run concurrently, recognition.rs:465-485).  Nothing may assume
+// that it owns the stream: a call waits for an event recorded after its own last enqueue, never for the stream.
 class StreamLease {
   public:
-    explicit StreamLease(bool high_priority = false);
+    // avoid_lane: a light lane the caller already has work on (a second lease of one call goes to another lane)
+    explicit StreamLease(bool high_priority = false, int avoid_lane = LanePlan::kPrivate);
     ~StreamLease();
     hipStream_t get() const { return s_; }
-    // Host wait for everything enqueued so far.  hipStreamSynchronize / hipEventSynchronize spin a core for the
-    // whole wait here (measured: every request thread at ~100 % CPU, also with hipEventBlockingSync), which with
-    // several requests in flight per process and several processes per host costs more cores than the layout
-    // analysis does.  So: record an event, poll it briefly, then sleep between polls (<= 0.1 ms added latency).
+    int lane() const { return lane_; }   // light lane index, LanePlan::kPrivate for a stream of the call's own
+    // May this call park a device-side wait for the conv / recurrence lane in its stream?  Yes on a stream of its own
+    // and in the one-stream regime; on a shared lane only while no other call is in flight on the device.
+    bool may_park_waits() const { return lane_ < 0 || ctx_->plan.outstanding() <= 1; }
+    // Host wait for everything this call has enqueued so far: an event of the call's own, recorded now (wait_event).
     hipError_t wait_done() const noexcept {
-        hipError_t e = hipEventRecord(done_, s_);
-        if (e != hipSuccess) return e;
-        for (int i = 0;; i++) {
-            e = hipEventQuery(done_);
-            if (e != hipErrorNotReady) return e;
-            if (i < 64) std::this_thread::yield();
-            else std::this_thread::sleep_for(std::chrono::microseconds(i < 256 ? 20 : 100));
-        }
+        const hipError_t e = hipEventRecord(done_, s_);
+        return e != hipSuccess ? e : wait_event(done_);
     }
     void sync() const { OCRS_HIP(wait_done()); }
     hipError_t sync_noexcept() const noexcept { return wait_done(); }
@@ -297,8 +321,10 @@ class StreamLease {
     DeviceContext* ctx_;   // the pool the stream goes back to
     DeviceContext::Mode mode_ = DeviceContext::MODE_FREE;
     bool shared_ = false;  // s_ is the device's one serial stream (MODE_SERIAL), not a leased one
-    hipStream_t s_;
-    hipEvent_t done_;
+    bool counted_ = false; // the plan counts this lease (MODE_FREE)
+    int lane_ = LanePlan::kPrivate;
+    hipStream_t s_ = nullptr;
+    hipEvent_t done_ = nullptr;
     bool high_;
 };
 
@@ -367,8 +393,8 @@ struct StageScope {
     ~StageScope() { if (t && token >= 0) t->end(token, s); }
 };
 
-// Everything one API call launches: a leased stream plus the scratch buffers its
-// kernels use.  The destructor drains the stream BEFORE the buffers go back to
+// Everything one API call launches: a leased stream (or lane) plus the scratch buffers its
+// kernels use.  The destructor waits for the call's last enqueue BEFORE the buffers go back to
 // the pool, so no other call can be handed memory that is still in flight.
 struct Workspace {
     StreamLease stream;
@@ -377,12 +403,14 @@ struct Workspace {
     std::vector<hipEvent_t> events;            // cross-stream dependencies created by this call
     hipEvent_t make_event() {
         hipEvent_t e;
-        OCRS_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+        OCRS_HIP(hipEventCreateWithFlags(&e, hipEventBlockingSync | hipEventDisableTiming));   // streams and the host wait for these
         events.push_back(e);
         return e;
     }
     Workspace() = default;
-    explicit Workspace(bool high_priority) : stream(high_priority) {}
+    explicit Workspace(bool high_priority, int avoid_lane = LanePlan::kPrivate) : stream(high_priority, avoid_lane) {}
+    // host wait for `ev`, recorded by this call on the conv or recurrence lane (never under heavy_phase / rec_phase)
+    void host_wait(hipEvent_t ev) { OCRS_HIP(wait_event(ev)); }
     // copy `bytes` from a host temporary to the device without a sync: the bytes are parked in pinned staging
     // owned by the workspace (released once its stream has drained), so the copy is a real asynchronous DMA
     std::vector<void*> upload_staging;

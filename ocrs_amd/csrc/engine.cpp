@@ -1,6 +1,7 @@
 #include "engine.hpp"
 
 #include <algorithm>
+#include <exception>
 #include <limits>
 #include <map>
 #include <thread>
@@ -1251,8 +1252,9 @@ void recognize_packed(const ocrs_engine& e, Workspace& ws, const std::vector<Chu
     check_rec_output(ndim, 0, 0, rq.C, e.alphabet.size());
     // Two ragged batches when the request mixes long and short lines: the recurrence is a chain
     // of up to 600 dependent, latency-bound steps whose tail only involves the few longest lines.
-    // The long groups run first on a high-priority stream; their recurrence then overlaps the
-    // conv stack of the short groups (the bulk of the FLOPs) on this call's main stream.
+    // The long groups run first, on a light lane other than this call's own (a stream of their own at stream budget 0),
+    // taken only when the request does split; their recurrence then overlaps the conv stack of the short groups (the
+    // bulk of the FLOPs) on this call's main stream.
     const int T_SPLIT = 160;
     size_t first_long = chunks.size();
     for (size_t c = 0; c < chunks.size(); c++)
@@ -1260,18 +1262,43 @@ void recognize_packed(const ocrs_engine& e, Workspace& ws, const std::vector<Chu
     size_t n_long_lines = 0, n_short_lines = 0;
     for (size_t c = 0; c < chunks.size(); c++) (c >= first_long ? n_long_lines : n_short_lines) += chunks[c].members.size();
     const bool split = n_long_lines > 0 && n_short_lines >= 64;
-    Workspace ws_long(true);  // high-priority stream (idle if unused)
     Sub sub_long, sub_short;
     if (split) {
-        {   // the crops were produced on ws's stream: the long lines' stream starts after them
-            hipEvent_t crops = ws.make_event();
+        Workspace ws_long(true, ws.stream.lane());
+        if (ws_long.s() != ws.s()) {   // the crops were produced on ws's stream: the long lines' stream starts after them
+            hipEvent_t crops = ws.make_event();   // (light-lane work, runnable as queued: a lane may wait for it)
             OCRS_HIP(hipEventRecord(crops, ws.s()));
             OCRS_HIP(hipStreamWaitEvent(ws_long.s(), crops, 0));
         }
-        launch_packed(rq, first_long, chunks.size(), ws_long, sub_long);
-        launch_packed(rq, 0, first_long, ws, sub_short);
-        ws_long.sync();
-        ws.sync();
+        if (ws.stream.may_park_waits()) {
+            launch_packed(rq, first_long, chunks.size(), ws_long, sub_long);
+            launch_packed(rq, 0, first_long, ws, sub_short);
+            ws_long.sync();
+            ws.sync();
+        } else {
+            // On shared lanes a batch's host thread waits for its conv stack and its recurrences (stream_plan.hpp): the
+            // long lines get a host thread of their own for the length of this call, or nothing would overlap.
+            std::exception_ptr long_error;
+            const Tuning* tuning = current_tuning();
+            const int device = ctx().device;
+            std::thread long_thread([&] {
+                try {
+                    DeviceScope bind(device);
+                    TuningScope tune(tuning);
+                    launch_packed(rq, first_long, chunks.size(), ws_long, sub_long);
+                    ws_long.sync();
+                    if (StageTimers* T = e.tm()) T->collect();
+                } catch (...) {
+                    long_error = std::current_exception();
+                }
+                StageTimers::release_thread_events();
+            });
+            struct Join { std::thread& t; ~Join() { if (t.joinable()) t.join(); } } join{long_thread};
+            launch_packed(rq, 0, first_long, ws, sub_short);
+            ws.sync();
+            long_thread.join();
+            if (long_error) std::rethrow_exception(long_error);
+        }
         unpack_packed(rq, sub_long);
         unpack_packed(rq, sub_short);
     } else {

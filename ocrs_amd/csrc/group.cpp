@@ -602,14 +602,19 @@ static void group_prepare(ocrs_engine_group* g, const void* const* pixels, size_
             return;
         }
         Workspace ws;
+        std::vector<const void*> d_px;
         for (size_t i : of_member[m]) {
-            const void* d_px = pixels[i];
+            d_px.push_back(pixels[i]);
             if (!on_device) {
                 void* d = ws.alloc(bytes);
                 OCRS_HIP(hipMemcpyAsync(d, pixels[i], bytes, hipMemcpyHostToDevice, ws.s()));
-                d_px = d;
+                d_px.back() = d;
             }
-            made[i].reset(make_page(d_px, type, order, height, width, channels, ws.s(), e->tm()));
+        }
+        auto share = make_pages(d_px.data(), d_px.size(), type, order, height, width, channels, ws.s(), e->tm());   // one launch
+        for (size_t j = 0; j < share.size(); j++) {
+            const size_t i = of_member[m][j];
+            made[i] = std::move(share[j]);
             made[i]->source = pixels[i];
         }
         ws.sync();

@@ -14,6 +14,15 @@ namespace k {
 // prepare_image (preprocess.rs:149-248): pixels -> grey f32 [H,W] in [-0.5,0.5].
 void prepare_image(const void* d_pixels, bool is_u8, bool chans_last, int h, int w, int chans, float* d_out,
                    hipStream_t s);
+// The same for the n pages of one call, all h x w of one format, in one launch per PrepareTable::kPages pages: the
+// descriptor table (source and destination of each page) travels in the kernel's arguments.  Same bits as prepare_image.
+struct PrepareTable {
+    enum { kPages = 32 };
+    const void* src[kPages];
+    float* dst[kPages];
+};
+void prepare_image_batch(const void* const* d_pixels, float* const* d_out, int n, bool is_u8, bool chans_last, int h, int w,
+                         int chans, hipStream_t s);
 // pad(-0.5) + bilinear resize of N equally sized pages to the model input
 // (detection.rs:155-171).  src_ptrs: device array of N page pointers [sh,sw].
 void resize_pages_to_model(const float* const* d_src_ptrs, int n, int sh, int sw, int vh, int vw, float* d_dst,

@@ -16,8 +16,8 @@ namespace k {
 // Algorithmic bytes: chans (u8) or 4*chans (f32) in, 4 out per pixel.
 // ---------------------------------------------------------------------------
 template <bool IS_U8, bool CHANS_LAST, int CHANS>
-__global__ void __launch_bounds__(256) prepare_image_kernel(const void* __restrict__ src, float* __restrict__ out,
-                                                            int64_t plane, float w0, float w1, float w2) {
+__device__ __forceinline__ void prepare_pixels(const void* __restrict__ src, float* __restrict__ out, int64_t plane, float w0,
+                                               float w1, float w2) {
     constexpr int NW = CHANS == 1 ? 1 : 3;
     const float wts[3] = {w0, w1, w2};
     const uint8_t* s8 = static_cast<const uint8_t*>(src);
@@ -36,9 +36,8 @@ __global__ void __launch_bounds__(256) prepare_image_kernel(const void* __restri
 }
 
 // Fast path: u8 RGB HWC, 4 pixels (12 B in, 16 B out) per thread.
-__global__ void __launch_bounds__(256) prepare_image_rgb8_x4_kernel(const uint32_t* __restrict__ src,
-                                                                    float4* __restrict__ out, int64_t quads,
-                                                                    float w0, float w1, float w2) {
+__device__ __forceinline__ void prepare_quads_rgb8(const uint32_t* __restrict__ src, float4* __restrict__ out, int64_t quads,
+                                                   float w0, float w1, float w2) {
     for (int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; q < quads;
          q += (int64_t)gridDim.x * blockDim.x) {
         uint32_t a = src[3 * q], b = src[3 * q + 1], c = src[3 * q + 2];
@@ -56,17 +55,51 @@ __global__ void __launch_bounds__(256) prepare_image_rgb8_x4_kernel(const uint32
     }
 }
 
-void prepare_image(const void* d_pixels, bool is_u8, bool chans_last, int h, int w, int chans, float* d_out,
-                   hipStream_t s) {
+// One page per launch (prepare_input): the grid's x blocks stride over the page.
+template <bool IS_U8, bool CHANS_LAST, int CHANS>
+__global__ void __launch_bounds__(256) prepare_image_kernel(const void* __restrict__ src, float* __restrict__ out,
+                                                            int64_t plane, float w0, float w1, float w2) {
+    prepare_pixels<IS_U8, CHANS_LAST, CHANS>(src, out, plane, w0, w1, w2);
+}
+
+__global__ void __launch_bounds__(256) prepare_image_rgb8_x4_kernel(const uint32_t* __restrict__ src,
+                                                                    float4* __restrict__ out, int64_t quads,
+                                                                    float w0, float w1, float w2) {
+    prepare_quads_rgb8(src, out, quads, w0, w1, w2);
+}
+
+// The pages of one call in one launch (prepare_input_batch): the pages of such a call share their size and
+// format, so the descriptor table is two pointers per page, small enough to travel in the kernel's arguments, and a block
+// finds its page in blockIdx.y.  Per pixel the same operations in the same order as the kernels above: the same bits.
+template <bool IS_U8, bool CHANS_LAST, int CHANS>
+__global__ void __launch_bounds__(256) prepare_image_batch_kernel(PrepareTable t, int64_t plane, float w0, float w1, float w2) {
+    prepare_pixels<IS_U8, CHANS_LAST, CHANS>(t.src[blockIdx.y], t.dst[blockIdx.y], plane, w0, w1, w2);
+}
+
+__global__ void __launch_bounds__(256) prepare_image_rgb8_x4_batch_kernel(PrepareTable t, int64_t quads, float w0, float w1, float w2) {
+    prepare_quads_rgb8(static_cast<const uint32_t*>(t.src[blockIdx.y]), reinterpret_cast<float4*>(t.dst[blockIdx.y]), quads, w0, w1, w2);
+}
+
+namespace {
+void prepare_weights(bool is_u8, int chans, float wt[3]) {
     const float itu[3] = {0.299f, 0.587f, 0.114f};
-    float wt[3];
     for (int c = 0; c < 3; c++) {
         if (chans == 1) wt[c] = is_u8 ? (1.0f / 255.0f) : 1.0f;
         else wt[c] = is_u8 ? (itu[c] / 255.0f) : itu[c];
     }
+}
+// the 4-pixel path: u8 RGB HWC, whole quads, a source readable as 32-bit words and a destination writable as float4
+bool prepare_x4_ok(const void* d_pixels, bool is_u8, bool chans_last, int chans, int64_t plane, const float* d_out) {
+    return is_u8 && chans_last && chans == 3 && plane % 4 == 0 && ((uintptr_t)d_pixels % 4) == 0 && ((uintptr_t)d_out % 16) == 0;
+}
+}  // namespace
+
+void prepare_image(const void* d_pixels, bool is_u8, bool chans_last, int h, int w, int chans, float* d_out,
+                   hipStream_t s) {
+    float wt[3];
+    prepare_weights(is_u8, chans, wt);
     const int64_t plane = (int64_t)h * w;
-    if (is_u8 && chans_last && chans == 3 && plane % 4 == 0 && ((uintptr_t)d_pixels % 4) == 0 &&
-        ((uintptr_t)d_out % 16) == 0) {
+    if (prepare_x4_ok(d_pixels, is_u8, chans_last, chans, plane, d_out)) {
         int64_t quads = plane / 4;
         int grid = (int)((quads + 255) / 256 < 4096 ? (quads + 255) / 256 : 4096);
         hipLaunchKernelGGL(prepare_image_rgb8_x4_kernel, dim3(grid), dim3(256), 0, s, (const uint32_t*)d_pixels,
@@ -91,6 +124,43 @@ void prepare_image(const void* d_pixels, bool is_u8, bool chans_last, int h, int
     }
 #undef DISPATCH_CH
 #undef LAUNCH
+}
+
+void prepare_image_batch(const void* const* d_pixels, float* const* d_out, int n, bool is_u8, bool chans_last, int h, int w,
+                         int chans, hipStream_t s) {
+    float wt[3];
+    prepare_weights(is_u8, chans, wt);
+    const int64_t plane = (int64_t)h * w;
+    bool x4 = true;
+    for (int i = 0; i < n; i++) x4 = x4 && prepare_x4_ok(d_pixels[i], is_u8, chans_last, chans, plane, d_out[i]);
+    for (int i0 = 0; i0 < n; i0 += PrepareTable::kPages) {   // a table's worth of pages per launch
+        const int m = n - i0 < (int)PrepareTable::kPages ? n - i0 : (int)PrepareTable::kPages;
+        PrepareTable t{};
+        for (int i = 0; i < m; i++) { t.src[i] = d_pixels[i0 + i]; t.dst[i] = d_out[i0 + i]; }
+        if (x4) {
+            const int64_t quads = plane / 4;
+            const int gx = (int)((quads + 255) / 256 < 4096 ? (quads + 255) / 256 : 4096);
+            hipLaunchKernelGGL(prepare_image_rgb8_x4_batch_kernel, dim3(gx, m), dim3(256), 0, s, t, quads, wt[0], wt[1], wt[2]);
+            continue;
+        }
+        int gx = (int)((plane + 255) / 256 < 8192 ? (plane + 255) / 256 : 8192);
+        if (gx < 1) gx = 1;
+#define LAUNCH(U8, CL, CH) \
+    hipLaunchKernelGGL((prepare_image_batch_kernel<U8, CL, CH>), dim3(gx, m), dim3(256), 0, s, t, plane, wt[0], wt[1], wt[2])
+#define DISPATCH_CH(U8, CL)                  \
+    switch (chans) {                         \
+        case 1: LAUNCH(U8, CL, 1); break;    \
+        case 3: LAUNCH(U8, CL, 3); break;    \
+        default: LAUNCH(U8, CL, 4); break;   \
+    }
+        if (is_u8) {
+            if (chans_last) { DISPATCH_CH(true, true) } else { DISPATCH_CH(true, false) }
+        } else {
+            if (chans_last) { DISPATCH_CH(false, true) } else { DISPATCH_CH(false, false) }
+        }
+#undef DISPATCH_CH
+#undef LAUNCH
+    }
 }
 
 // ---------------------------------------------------------------------------

@@ -742,7 +742,8 @@ float* HipModel::run_device(Workspace& ws, const float* d_in, int n, int h, int 
 // ---------------------------------------------------------------------------
 float* HipModel::run_prefix_ragged(Workspace& ws, hipStream_t exec, const std::vector<PackedGroup>& groups,
                                    const PackedPlan& plan, int h, int ts, StageTimers* timers, int* feat_c,
-                                   const std::function<void()>& before_launch, const OpRange* range) const {
+                                   const std::function<void()>& before_launch, const OpRange* range,
+                                   hipEvent_t* stack_done) const {
     // supported stack: CONV 3x3 (Cin == 1 directly followed by MAXPOOL 2x2, or Cin % 32 == 0), MAXPOOL, AVGPOOL,
     // each consuming the previous op's output
     const int G = (int)groups.size();
@@ -871,7 +872,9 @@ float* HipModel::run_prefix_ragged(Workspace& ws, hipStream_t exec, const std::v
     ws.upload(d64, meta64.data(), meta64.size() * sizeof(int64_t));
     ws.upload(d32, meta32.data(), meta32.size() * sizeof(int32_t));
     if (before_launch) before_launch();   // everything above is host work and uploads on the request's own stream
-    if (exec != ws.s()) {  // inputs (crops, plan, metadata) were produced on the request's stream
+    if (exec != ws.s()) {  // inputs (crops, plan, metadata) were produced on the request's stream: light-lane work, runnable
+                           // as queued, so the conv lane may wait for it on the device (the same wait on the host, ahead of
+                           // heavy_phase, measured 0.3 % lower: profiles/stream_budget_cost.txt)
         hipEvent_t ready = ws.make_event();
         OCRS_HIP(hipEventRecord(ready, ws.s()));
         OCRS_HIP(hipStreamWaitEvent(exec, ready, 0));
@@ -1045,10 +1048,13 @@ float* HipModel::run_prefix_ragged(Workspace& ws, hipStream_t exec, const std::v
         }
     }
     if (tok >= 0) timers->end(tok, st);
-    if (exec != ws.s()) {  // the request's stream continues once the conv stack has drained
+    if (exec != ws.s()) {  // the request continues once the conv stack has drained
         hipEvent_t done = ws.make_event();
         OCRS_HIP(hipEventRecord(done, exec));
-        OCRS_HIP(hipStreamWaitEvent(ws.s(), done, 0));
+        // A lane shared with other calls never has a wait for the conv lane parked in it (stream_plan.hpp): the caller's
+        // host thread waits for `done`, once it has let go of heavy_phase, and enqueues what follows when it wakes.
+        if (stack_done && !ws.stream.may_park_waits()) *stack_done = done;
+        else OCRS_HIP(hipStreamWaitEvent(ws.s(), done, 0));
     }
     *feat_c = curC;
     return X;
@@ -1135,22 +1141,24 @@ int HipModel::run_recognition_packed(Workspace& ws, const std::vector<PackedGrou
         // the request's geometry has been worked out and its metadata uploads are queued.
         std::unique_lock<std::mutex> heavy(ctx().heavy_phase, std::defer_lock);
         const hipStream_t conv = ws.stream.conv_stream();   // the device's conv-stack stream
+        hipEvent_t stack_done = nullptr;
         try {
-            X = run_prefix_ragged(ws, conv, groups, plan, h, ts, timers, &C0, [&] { heavy.lock(); }, range);
+            X = run_prefix_ragged(ws, conv, groups, plan, h, ts, timers, &C0, [&] { heavy.lock(); }, range, &stack_done);
         } catch (...) {
             // Kernels of this request may already be queued on the shared stream, reading and writing scratch
-            // that ~Workspace hands back to the pool after draining only the request's OWN stream: make that
-            // stream wait for them first (best effort, no throw on the error path).
+            // that ~Workspace hands back to the pool after waiting only for what the request queued on its OWN
+            // stream: wait for them first (best effort, no throw on the error path) — on the host, with heavy_phase
+            // released, so that nothing is parked in a lane that other calls share.
             hipEvent_t e = nullptr;
-            if (hipEventCreateWithFlags(&e, hipEventDisableTiming) == hipSuccess) {
-                ws.events.push_back(e);
-                if (hipEventRecord(e, conv) != hipSuccess || hipStreamWaitEvent(ws.s(), e, 0) != hipSuccess)
-                    (void)hipStreamSynchronize(conv);
-            } else {
-                (void)hipStreamSynchronize(conv);
-            }
+            const bool recorded = hipEventCreateWithFlags(&e, hipEventBlockingSync | hipEventDisableTiming) == hipSuccess &&
+                                  hipEventRecord(e, conv) == hipSuccess;
+            if (e) ws.events.push_back(e);
+            if (heavy.owns_lock()) heavy.unlock();
+            if (!recorded || wait_event(e) != hipSuccess) (void)hipStreamSynchronize(conv);
             throw;
         }
+        if (heavy.owns_lock()) heavy.unlock();
+        if (stack_done) ws.host_wait(stack_done);
     }
     if (range && first <= ts) {
         if (!X) fail(OCRS_ERR_INVALID_ARGUMENT, "op range: this model's conv stack has no ragged form");
@@ -1229,6 +1237,7 @@ int HipModel::run_recognition_packed(Workspace& ws, const std::vector<PackedGrou
                 uint32_t* d_sync = ws.alloc_n<uint32_t>(k::gru_persistent_sync_words(M));
                 double fl = 0.0;
                 for (int step = 0; step < plan.Tmax; step++) fl += 2.0 * 2 * plan.active[step] * 3.0 * H * H;
+                hipEvent_t rec_done = nullptr;
                 {
                     DeviceContext& dc = ctx();
                     std::lock_guard<std::mutex> g(dc.rec_phase);
@@ -1243,8 +1252,12 @@ int HipModel::run_recognition_packed(Workspace& ws, const std::vector<PackedGrou
                     if (ran_persistent && plan.h_status && gru_layer < 8)
                         ws.download(plan.h_status + gru_layer, d_sync + k::gru_persistent_sync_words(M) - 1, sizeof(uint32_t), rs);
                     OCRS_HIP(hipEventRecord(done, rs));
-                    OCRS_HIP(hipStreamWaitEvent(st, done, 0));
+                    // the rest of the request follows the recurrence: a wait parked in the request's own stream, or on a
+                    // lane shared with other calls a wait of the host thread (below, rec_phase released)
+                    if (rs == st || ws.stream.may_park_waits()) OCRS_HIP(hipStreamWaitEvent(st, done, 0));
+                    else rec_done = done;
                 }
+                if (rec_done) ws.host_wait(rec_done);
             }
             if (ran_persistent) {
                 // done

@@ -147,9 +147,13 @@ struct HipModel : ModelBase {
     // (the caller takes the shared stream's lock there).
     // range: launches only ops [range->first, range->last] (range->last < ts: returns that op's output, ragged, in a buffer
     // of `ws`); the ops before it are planned, not run.
+    // stack_done: where ws's stream is a lane shared with other calls, no wait for `exec` is parked in it: *stack_done is
+    // then the event recorded behind the stack, for the caller's host thread to wait for once it holds no lock
+    // (stream_plan.hpp); otherwise *stack_done is left alone and ws's stream waits for the stack itself.
     float* run_prefix_ragged(Workspace& ws, hipStream_t exec, const std::vector<PackedGroup>& groups,
                              const PackedPlan& plan, int h, int ts, StageTimers* timers, int* feat_c,
-                             const std::function<void()>& before_launch = nullptr, const OpRange* range = nullptr) const;
+                             const std::function<void()>& before_launch = nullptr, const OpRange* range = nullptr,
+                             hipEvent_t* stack_done = nullptr) const;
 };
 
 }  // namespace ocrs
