@@ -108,7 +108,7 @@ struct DeviceContext {
     const int device;
     DevicePool pool;
     HostPool host_pool;
-    // One stream per device for the throughput-bound conv stacks of all in-flight requests (model.cpp), and one
+    // One stream per device for the throughput-bound conv stacks of all in-flight requests (model_packed.cpp), and one
     // for the persistent GRU recurrences (kernels_gru.hip): their workgroups wait on each other, so they are
     // serialised on the device; both at the highest queue priority (the conv lane and the recurrence lane of
     // stream_plan.hpp).  The *_phase mutexes keep "record event, make the shared stream wait, launch, record" atomic

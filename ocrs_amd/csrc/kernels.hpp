@@ -243,10 +243,9 @@ struct RaggedView {          // device pointers live in one metadata upload; pas
     const int32_t* W;        // [G] image width at this layer
     const int32_t* n;        // [G] images per group
     const int64_t* poff;     // [G+1] pixel offset of each group in the buffer
-    const int32_t* toff128;  // [G+1] cumulative 128-pixel tile counts
     const int32_t* toff256;  // [G+1] cumulative 256-pixel tile counts
     const int32_t* loff;     // [G+1] cumulative image (line) counts
-    int ntiles128, ntiles256;
+    int ntiles256;
     const int32_t* toff2d;   // [G+1] cumulative TH x TW patch counts (conv3x3_ragged), TH = 128 / tw
     int ntiles2d, tw;
     // the same with the patches tiling the whole group's strip of images (flat column = img * Wp + x; Wp = W, or W

@@ -8,7 +8,7 @@ ReLU flags, the pool that makes the decoder's low-resolution input and the tenso
 
   encoder (cs -> cmid -> cout):   [lift 1 -> cs]  dw3 -> pw -> dw3 -> pw -> y -> MaxPool 2x2 -> ypool
                                   two graphs from the same weights: out = ypool, and out = y with the pool kept as a consumer
-                                  (both fuse with the pool: model.cpp's matcher takes the pool whoever else reads y)
+                                  (both fuse with the pool: model_load.cpp's matcher takes the pool whoever else reads y)
   decoder (cs, cx -> cmid -> cout):  skip = lift 1 -> cs;  x1 = MaxPool(kh, kw)(lift 1 -> cx);
                                   ConvT2(x1) -> PADCAT(skip, up) -> dw3 -> pw -> dw3 -> pw -> y [-> conv 1x1 -> 1 [-> sigmoid]]
 

@@ -292,3 +292,33 @@ def test_non_finite_page_and_crop_do_not_leak_into_the_batch():
         return None if line is None else [(c.char, tuple(c.rect)) for c in line._chars]
     for i, ln in enumerate(lines):
         assert norm(batch[i]) == norm(eng.recognize_text(binp, [ln])[0]), i
+
+
+# ---------------------------------------------------------------- Model.run(timing=True)
+@pytest.mark.parametrize("det_fuse", [1, 0])
+def test_timed_run_prints_one_line_per_op_and_computes_the_same(det_fuse, capfd):
+    """The print_timing branch of HipModel::run_device (model.cpp): an event behind every op, ops covered by a fused
+    DoubleConv launch (det_fuse = 1) included, then one line per graph op in op order and a `total` line on the process's
+    stdout.  The outputs equal those of an untimed run."""
+    import ctypes
+    dbuf = M.detection_model_bytes((160, 128), (8, 16, 32, 32))
+    model = Model.load_bytes(dbuf)
+    x = _image(np.random.default_rng(160), 1, 160, 128) * np.float32(0.25)
+    libc = ctypes.CDLL(None)
+    try:
+        _lib.set_option("det_fuse", det_fuse)
+        plain = model.run(x)
+        libc.fflush(None)
+        capfd.readouterr()
+        timed = model.run(x, timing=True)
+        libc.fflush(None)   # the table goes through C stdio
+        out = capfd.readouterr().out
+    finally:
+        _lib.set_option("det_fuse", 1)
+    assert np.array_equal(timed, plain, equal_nan=True)
+    names = [mf.OP_NAMES[op["type"]] for op in OracleGraph(dbuf).ops]
+    lines = out.splitlines()
+    assert len(lines) == len(names) + 1, out
+    for line, name in zip(lines, names):
+        assert line.split()[0] == name and line.endswith("ms"), (line, name)
+    assert lines[-1].split()[0] == "total" and lines[-1].endswith("ms"), lines[-1]

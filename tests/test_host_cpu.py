@@ -239,7 +239,7 @@ def test_no_gpu_means_a_loud_error_not_a_cpu_fallback(lib):
 
 def test_malformed_model_files_are_rejected_at_load(lib):
     """A stale or corrupted .ocrsm must fail with OCRS_ERR_IO at load (before any device work), not index out of
-    bounds later: slot numbers, weight-tensor sizes and blob ranges are validated (model.cpp HipModel::load)."""
+    bounds later: slot numbers, weight-tensor sizes and blob ranges are validated (model_load.cpp HipModel::load)."""
     import struct
     import models_util as M
     from ocrs_amd import Model
