@@ -176,6 +176,12 @@ resize_pages_kernel(const float* const* __restrict__ src_ptrs, int sh, int sw, i
     const int n = blockIdx.z;
     if (x >= dw) return;
     const float* __restrict__ src = src_ptrs[n];
+    if (vh == dh && vw == dw) {
+        // a same-size resize_image is a copy (detection.rs:167): at weight 0 the formula's 0 * tr makes a NaN
+        // of a pixel whose right or lower neighbour is NaN or Inf, a NaN of an Inf pixel, and +0.0 of -0.0
+        dst[((int64_t)n * dh + y) * dw + x] = (y < sh && x < sw) ? src[(int64_t)y * sw + x] : -0.5f;
+        return;
+    }
     int y0, y1, x0, x1;
     float wy, wx;
     resize_axis(y, vh, dh, y0, y1, wy);
@@ -194,9 +200,9 @@ void resize_pages_to_model(const float* const* d_src_ptrs, int n, int sh, int sw
     hipLaunchKernelGGL(resize_pages_kernel, grid, dim3(256), 0, s, d_src_ptrs, sh, sw, vh, vw, d_dst, dh, dw);
 }
 
-// prob [n, mh, mw] sliced to [sh, sw], resized to [h, w], thresholded with a
-// strict '>' (detection.rs:110,187-194).  4 output pixels per thread so the u8
-// mask is written as one 32-bit word.
+// prob [n, mh, mw] sliced to [sh, sw], resized to [h, w] (copied where that is its size already: the oracle's choice,
+// oracle/pipeline.py detect_text_pixels), thresholded with a strict '>' (detection.rs:110,187-194).
+// 4 output pixels per thread so the u8 mask is written as one 32-bit word.
 // Algorithmic bytes per page: 4*sh*sw read + h*w (mask) [+ 4*h*w map] written.
 // LABELS (r6): the kernel also writes the INITIAL LABELS of the component stage (kernels_ccl.hip ccl_init4_kernel: the start of
 // the horizontal run of equal mask pixels inside the wave's 256-pixel segment) — the thread holds its four mask pixels in a
@@ -215,6 +221,7 @@ resize_threshold_kernel(const float* __restrict__ prob, int mh, int mw, int sh, 
     if (!LABELS && !inb) return;
     if (LABELS && xq == 0 && y == 0) { zero_a[n] = 0; zero_b[n] = 0; }
     const float* __restrict__ src = prob + (int64_t)n * mh * mw;
+    const bool copy = sh == h && sw == w;   // a same-size resize is a copy, as on the way in (resize_pages_kernel)
     int y0, y1;
     float wy;
     resize_axis(y, sh, h, y0, y1, wy);
@@ -225,12 +232,16 @@ resize_threshold_kernel(const float* __restrict__ prob, int mh, int mw, int sh, 
         int x = x_base + i;
         float v = 0.0f;
         if (x < w) {
-            int x0, x1;
-            float wx;
-            resize_axis(x, sw, w, x0, x1, wx);
-            float tl = src[(int64_t)y0 * mw + x0], tr = src[(int64_t)y0 * mw + x1];
-            float bl = src[(int64_t)y1 * mw + x0], br = src[(int64_t)y1 * mw + x1];
-            v = bilerp(tl, tr, bl, br, wx, wy);
+            if (copy) {
+                v = src[(int64_t)y * mw + x];
+            } else {
+                int x0, x1;
+                float wx;
+                resize_axis(x, sw, w, x0, x1, wx);
+                float tl = src[(int64_t)y0 * mw + x0], tr = src[(int64_t)y0 * mw + x1];
+                float bl = src[(int64_t)y1 * mw + x0], br = src[(int64_t)y1 * mw + x1];
+                v = bilerp(tl, tr, bl, br, wx, wy);
+            }
             if (v > thr) bits |= 1u << (8 * i);
         }
         vals[i] = v;
