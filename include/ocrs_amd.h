@@ -573,6 +573,107 @@ OCRS_API ocrs_status ocrs_engine_warp_pages(const ocrs_engine* e, const ocrs_pag
 OCRS_API ocrs_status ocrs_deskew_map(int h, int w, double angle_deg, int expand, int out_hw[2], float m[6]);
 OCRS_API ocrs_status ocrs_unwarp_rects(float* rects6, size_t n, const float m[6]);
 
+/* ------------------------------------------------------------------------
+ * Perspective correction (no reference counterpart, opt-in).  A sheet photographed on a desk is a keystone,
+ * not a rotation: its four edges have four angles, and no affine map straightens it.  These calls find the sheet's outline
+ * on a resident page without a detector, make the straightened sheet as a new resident page through a projective map, and
+ * map what was found on it back to the frame of the photo.  tests/perspective_ref.py restates every definition; the library
+ * equals it bit for bit.  What the outline finds on real photographs is uncalibrated: only synthetic photos exist here.
+ *
+ * ocrs_engine_edge_peaks: out_peaks[(((i * 2 + family) * 2 + sign) * n_angles + a) * 16 + k] for n pages of any sizes in
+ * one launch (plus one small launch that takes the maxima).  sc_table as for ocrs_engine_skew_scores.  For a page of H x W
+ * and min_step in 1 .. 256:
+ *   q(x, y)   the bin of Page normalisation above; a NaN is not counted
+ *   family 0  (H, near-horizontal lines) g(x, y) = q(x, y + 1) - q(x, y); 0 on the last row and beside a NaN.
+ *             bin = (x S + y C - t0) >> 16, t0 = min(0, (W - 1) S) + min(0, (H - 1) C)
+ *   family 1  (V, near-vertical lines) family 0 of the transposed page: g = q(x + 1, y) - q(x, y), bin = (y S + x C - t0T)
+ *             >> 16, t0T = min(0, (H - 1) S) + min(0, (W - 1) C)
+ *   sign      0 (`+`): g >= min_step; 1 (`-`): g <= -min_step.  Each such pixel adds 1 (a count, not |g|: with |g| the
+ *             many strong edges of text outweigh the one long edge of the sheet) to P[family][sign][a][bin]
+ *   peaks     a profile row has H + W bins, cut into 16 bands [k (H + W) / 16, (k + 1) (H + W) / 16) (integer division);
+ *             per band the largest count and the smallest bin that has it, packed (count << 32) | (0xFFFFFFFF - bin); 0
+ *             when the band is empty or counts nothing
+ * All integers: the result does not depend on schedule, batch or launch shape.  OCRS_ERR_INVALID_ARGUMENT for n_angles < 1
+ * (or > 65535), an |S| or |C| above 65536, min_step outside 1 .. 256 and a page side above 4096; OCRS_ERR_CAPACITY for more
+ * than 65535 pages or more than 2 GiB of profiles (16 n_angles (H + W) bytes per page) in one call.
+ *
+ * ocrs_outline_choose (host only, double, no libm trigonometry): the outline among the peaks of a work_h x work_w page
+ * taken from a page_h x page_w page.  At most 4095 angles, the most ocrs_engine_find_outline's own table can hold (the pair search is
+ * quadratic in the peaks that count: 16 per angle, family and sign); more is OCRS_ERR_INVALID_ARGUMENT.  A peak counts when count >= ceil(min_cover L), L = work_w (family 0) or work_h
+ * (family 1).  Its line is s x + c y = rho + 0.5 c (family 1: s y + c x) with s = S / 65536, c = C / 65536, rho = (bin
+ * 65536 + 32768 + t0) / 65536: the edge lies between the two pixels of the difference.  Its position is its y at x =
+ * (work_w - 1) / 2 (family 1: its x at y = (work_h - 1) / 2); a peak whose position is not finite is dropped.  Each sign
+ * order is a hypothesis: `+` first (polarity 0) reads top and left as `+` edges, bottom and right as `-` edges: a sheet
+ * lighter than the desk.  Per family the pair (first, second) of largest count1 + count2 with position2 - position1 >=
+ * min_span (work_h - 1) (family 1: work_w - 1) is taken, ties to the lower (angle index, bin) of the first line, then of
+ * the second; both families share the order, the order with the larger sum over the four lines wins, a tie goes to `+`
+ * first.  The corners TL, TR, BR, BL are the four intersections, moved to the page's frame with (p + 0.5) (page / work) -
+ * 0.5 per axis and rounded once to float32; they may lie outside the page.  found = 0 (and every other field but the work
+ * size 0) when a family has no pair, a corner is not finite, the quad is not convex in this order (a consecutive cross
+ * product <= 0, y down) or its area is under min_area page_h page_w.
+ *
+ * ocrs_engine_find_outline: (1) a page whose longer side exceeds work_max_side is shrunk with OCRS_RESAMPLE_AREA, as
+ * ocrs_engine_estimate_skew does; (2) the peaks at the angles k step_deg, k = -K .. K, K = floor(max_deg / step_deg)
+ * (ocrs_skew_table(-K, 2 K + 1, step_deg)); (3) ocrs_outline_choose.  params == NULL: ocrs_outline_params_default
+ * (work_max_side 512, max_deg 15, step_deg 0.5, min_step 8, min_cover 0.25, min_span 0.25, min_area 0.1).
+ * ocrs_outline_params_check (host only) refuses work_max_side outside 1 .. 4096, min_step outside 1 .. 256, max_deg outside
+ * (0, 45], a step that is not finite and positive or that max_deg holds fewer than 1 or more than 2047 of, min_cover or
+ * min_span outside (0, 1], min_area outside [0, 1].
+ *
+ * ocrs_quad_map (host only): corners8 = TL, TR, BR, BL as (x, y) in the page's pixel-index frame (the page's own outline
+ * is (-0.5, -0.5), (W - 0.5, -0.5), (W - 0.5, H - 0.5), (-0.5, H - 0.5) and gives the identity map).  W' = floor(max(|TR -
+ * TL|, |BR - BL|) + 0.5) and H' likewise from |BL - TL| and |BR - TR|, each kept within 1 .. 65535; out_hw = {H', W'}.  m =
+ * Heckbert's square-to-quad coefficients with u = fx / W', v = fy / H': dx1 = x1 - x2, dx2 = x3 - x2, sx = x0 - x1 + x2 -
+ * x3 (y likewise), det = dx1 dy2 - dy1 dx2, g = (sx dy2 - sy dx2) / det, h = (dx1 sy - dy1 sx) / det; m0 = x0, m1 = (x1 -
+ * x0 + g x1) / W', m2 = (x3 - x0 + h x3) / H', m3 = y0, m4 = (y1 - y0 + g y1) / W', m5 = (y3 - y0 + h y3) / H', m6 = g / W',
+ * m7 = h / H'.  In double, each coefficient rounded once to float32.  OCRS_ERR_INVALID_ARGUMENT for det == 0 and for a
+ * corner, a det or a coefficient that is not finite.
+ *
+ * ocrs_engine_project_page[s]: ocrs_engine_warp_page[s] with a projective map of eight coefficients.  float32, every
+ * operation rounded on its own: fx = ox + 0.5f, fy = oy + 0.5f; nx = (m0 + m1 fx) + m2 fy, ny = (m3 + m4 fx) + m5 fy, dn =
+ * (1.0f + m6 fx) + m7 fy.  When dn is finite and > 0: X = nx / dn, Y = ny / dn (correctly rounded divisions), then the taps,
+ * `fill` and the lerps of ocrs_engine_warp_page; otherwise the pixel is `fill`.  With m6 = m7 = 0 the output has the bits
+ * of ocrs_engine_warp_page.  Coefficients that are not finite: OCRS_ERR_INVALID_ARGUMENT.
+ *
+ * ocrs_unproject_rects / ocrs_unproject_chars (host only, in place): results found on a page projected with m, in the
+ * frame of its source.  In double from the float32 coefficients.  Rects: the centre (x + 0.5, y + 0.5) goes through the
+ * map; with J = [(m1 - m6 X) / dn, (m2 - m7 X) / dn; (m4 - m6 Y) / dn, (m5 - m7 Y) / dn], the map's Jacobian there: up' =
+ * J up / |J up| (up stays when |J up| is 0 or not finite), h' = h |J up|, w' = w |J (-up.y, up.x)|; each result rounded to
+ * float32.  A rect with a value that is not finite, or whose centre has dn <= 0 (or not finite), passes through as it is.
+ * Char boxes: the four corners go through the map; left and top are the floor of the minimum, right and bottom the ceil of
+ * the maximum (saturating at int32); a box with a corner whose dn <= 0 passes through as it is. */
+typedef struct ocrs_outline_params {
+    double max_deg;         /* the angles cover -max_deg .. +max_deg; (0, 45] */
+    double step_deg;        /* > 0; the angles are its multiples */
+    double min_cover;       /* (0, 1]: a line's edge pixels, as a share of the work page's side along it */
+    double min_span;        /* (0, 1]: the distance between opposite sides, as a share of the work page's side across them */
+    double min_area;        /* [0, 1]: the quad's area, as a share of the page's */
+    int32_t work_max_side;  /* 1 .. 4096 */
+    int32_t min_step;       /* 1 .. 256: bins between neighbouring pixels that make an edge */
+} ocrs_outline_params;
+typedef struct ocrs_outline_info {
+    int32_t found;          /* 1: corners holds an outline */
+    int32_t polarity;       /* 0: `+` first, the sheet is lighter than the desk; 1: `-` first */
+    float corners[8];       /* TL, TR, BR, BL as (x, y), the page's pixel-index frame */
+    uint32_t counts[4];     /* the edge pixels of top, bottom, left, right */
+    int32_t angles[4];      /* their angles, as indices k + K into the table */
+    int32_t work_h, work_w; /* the size the peaks were taken at */
+} ocrs_outline_info;
+OCRS_API ocrs_status ocrs_outline_params_default(ocrs_outline_params* out);
+OCRS_API ocrs_status ocrs_outline_params_check(const ocrs_outline_params* params);
+OCRS_API ocrs_status ocrs_engine_edge_peaks(const ocrs_engine* e, const ocrs_page* const* pages, size_t n, const int32_t* sc_table,
+                                            size_t n_angles, int min_step, uint64_t* out_peaks);
+OCRS_API ocrs_status ocrs_outline_choose(const uint64_t* peaks, const int32_t* sc_table, size_t n_angles, int work_h, int work_w,
+                                         int page_h, int page_w, const ocrs_outline_params* params, ocrs_outline_info* out);
+OCRS_API ocrs_status ocrs_engine_find_outline(const ocrs_engine* e, const ocrs_page* page, const ocrs_outline_params* params,
+                                              ocrs_outline_info* out);
+OCRS_API ocrs_status ocrs_quad_map(const float corners8[8], int out_hw[2], float m[8]);
+OCRS_API ocrs_status ocrs_engine_project_page(const ocrs_engine* e, const ocrs_page* page, int out_h, int out_w, const float m[8],
+                                              float fill, ocrs_page** out);
+OCRS_API ocrs_status ocrs_engine_project_pages(const ocrs_engine* e, const ocrs_page* const* pages, size_t n, const int* out_hw,
+                                               const float* m, const float* fill, ocrs_page** out);
+OCRS_API ocrs_status ocrs_unproject_rects(float* rects6, size_t n, const float m[8]);
+
 /* OcrEngine::detection_threshold (lib.rs:282-287). */
 OCRS_API float ocrs_engine_detection_threshold(const ocrs_engine* e);
 
@@ -763,6 +864,8 @@ OCRS_API ocrs_status ocrs_unrotate_rects(float* rects6, size_t n, int page_h, in
 OCRS_API ocrs_status ocrs_unrotate_chars(ocrs_text_char* chars, size_t n, int page_h, int page_w, int k);
 /* "Page deskew" above: its char boxes (declared here, after ocrs_text_char). */
 OCRS_API ocrs_status ocrs_unwarp_chars(ocrs_text_char* chars, size_t n, const float m[6]);
+/* "Perspective correction" above: its char boxes. */
+OCRS_API ocrs_status ocrs_unproject_chars(ocrs_text_char* chars, size_t n, const float m[8]);
 OCRS_API ocrs_status ocrs_orientation_vote(const float* rects6, size_t n, double out[2]);
 OCRS_API ocrs_status ocrs_engine_detect_orientation(const ocrs_engine* e, const ocrs_page* page, size_t max_lines, int* quarter_turns,
                                                     double vote[2], double score[4], uint32_t n_chars[4]);

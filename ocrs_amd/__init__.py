@@ -574,6 +574,119 @@ def unwarp_lines(text_lines, m):
     return out
 
 
+class Outline:
+    """ocrs_engine_find_outline's outputs: found, corners (float32 [4, 2]: TL, TR, BR, BL as (x, y) in the
+    page's pixel-index frame; zeros when nothing was found), polarity (0: the sheet is lighter than the desk, 1: darker),
+    counts and angles (of top, bottom, left, right: edge pixels, index into the angle table), work_hw (the size the peaks
+    were taken at)."""
+    __slots__ = ("found", "corners", "polarity", "counts", "angles", "work_hw")
+
+    def __repr__(self):
+        return "Outline(found=%r, corners=%r, polarity=%r, counts=%r)" % (self.found, self.corners.tolist(), self.polarity, self.counts)
+
+
+def _outline_of(info):
+    o = Outline()
+    o.found, o.polarity = bool(info.found), int(info.polarity)
+    o.corners = np.array(list(info.corners), np.float32).reshape(4, 2)
+    o.counts, o.angles = tuple(int(v) for v in info.counts), tuple(int(v) for v in info.angles)
+    o.work_hw = (int(info.work_h), int(info.work_w))
+    return o
+
+
+_OUTLINE_FIELDS = ("work_max_side", "max_deg", "step_deg", "min_step", "min_cover", "min_span", "min_area")
+
+
+def _outline_struct(**params):
+    p = _lib.OutlineParams()
+    check(lib().ocrs_outline_params_default(C.byref(p)))
+    for k, v in params.items():
+        if k not in _OUTLINE_FIELDS:
+            raise TypeError("outline: no parameter %r (one of %s)" % (k, ", ".join(_OUTLINE_FIELDS)))
+        if v is not None:
+            setattr(p, k, int(v) if k in ("work_max_side", "min_step") else float(v))
+    return p
+
+
+def outline_params(**params):
+    """ocrs_outline_params as a dict: ocrs_outline_params_default (work_max_side 512, max_deg 15, step_deg
+    0.5, min_step 8, min_cover 0.25, min_span 0.25, min_area 0.1) with the given fields replaced, checked by
+    ocrs_outline_params_check (host only)."""
+    p = _outline_struct(**params)
+    check(lib().ocrs_outline_params_check(C.byref(p)))
+    return {k: (int if k in ("work_max_side", "min_step") else float)(getattr(p, k)) for k in _OUTLINE_FIELDS}
+
+
+def outline_choose(peaks, sc_table, work_hw, page_hw, **params):
+    """ocrs_outline_choose (host only): the outline among the peaks (uint64 [2, 2, A, 16]: OcrEngine.edge_peaks) of a
+    work_hw = (height, width) page taken from a page_hw page -> Outline."""
+    t = np.ascontiguousarray(sc_table, np.int32).reshape(-1, 2)
+    pk = np.ascontiguousarray(peaks, np.uint64).reshape(-1)
+    if pk.size != 4 * len(t) * 16:
+        raise ValueError("outline_choose: peaks are uint64 [2, 2, A, 16]")
+    p, info = _outline_struct(**params), _lib.OutlineInfo()
+    check(lib().ocrs_outline_choose(pk.ctypes.data_as(C.POINTER(C.c_uint64)), t.ctypes.data_as(C.POINTER(C.c_int32)), C.c_size_t(len(t)),
+                                    C.c_int(int(work_hw[0])), C.c_int(int(work_hw[1])), C.c_int(int(page_hw[0])), C.c_int(int(page_hw[1])),
+                                    C.byref(p), C.byref(info)))
+    return _outline_of(info)
+
+
+def page_corners(page_hw):
+    """The outline of a page_hw = (height, width) page itself, float32 [4, 2]: quad_map of it is the identity map."""
+    h, w = float(page_hw[0]), float(page_hw[1])
+    return np.array([[-0.5, -0.5], [w - 0.5, -0.5], [w - 0.5, h - 0.5], [-0.5, h - 0.5]], np.float32)
+
+
+def quad_map(corners):
+    """ocrs_quad_map (host only): the projective map that shows the quad corners = TL, TR, BR, BL as (x, y) (the page's
+    pixel-index frame) as an upright page -> ((out_h, out_w), m float32 [8])."""
+    c = np.ascontiguousarray(corners, np.float32).reshape(-1)
+    if c.size != 8:
+        raise ValueError("a quad is four corners")
+    hw = (C.c_int * 2)()
+    m = np.zeros(8, np.float32)
+    check(lib().ocrs_quad_map(c.ctypes.data_as(C.POINTER(C.c_float)), hw, m.ctypes.data_as(C.POINTER(C.c_float))))
+    return (int(hw[0]), int(hw[1])), m
+
+
+def _map8_arg(m):
+    a = np.ascontiguousarray(m, np.float32).reshape(-1)
+    if a.size != 8:
+        raise ValueError("a projective map is eight coefficients")
+    return a
+
+
+def unproject_rects(rects, m):
+    """ocrs_unproject_rects (host only): word rects found on a page projected with m -> the same rects in the frame of the
+    projection's source, float32 [n, 6] (a copy)."""
+    a, mm = _rects_to_array(rects).copy(), _map8_arg(m)
+    check(lib().ocrs_unproject_rects(a.ctypes.data_as(C.POINTER(C.c_float)), C.c_size_t(len(a)), mm.ctypes.data_as(C.POINTER(C.c_float))))
+    return a
+
+
+def unproject_boxes(boxes, m):
+    """ocrs_unproject_chars on bare boxes: int32 [n, 4] (top, left, bottom, right) on a page projected with m -> in its source's frame."""
+    b, mm = np.asarray(boxes, np.int32).reshape(-1, 4), _map8_arg(m)
+    arr = (_lib.TextCharC * max(len(b), 1))()
+    for i, (t, l, bo, r) in enumerate(b.tolist()):
+        arr[i] = _lib.TextCharC(0, t, l, bo, r)
+    check(lib().ocrs_unproject_chars(arr, C.c_size_t(len(b)), mm.ctypes.data_as(C.POINTER(C.c_float))))
+    return np.array([[arr[i].top, arr[i].left, arr[i].bottom, arr[i].right] for i in range(len(b))], np.int32).reshape(-1, 4)
+
+
+def unproject_lines(text_lines, m):
+    """recognize_text's output on a page projected with m -> new TextLines (None stays None) whose char boxes are in the
+    frame of the projection's source (ocrs_unproject_chars); text, log-probs and scores are kept."""
+    out = []
+    for t in text_lines:
+        if t is None:
+            out.append(None)
+            continue
+        boxes = unproject_boxes([c.rect for c in t.chars()], m)
+        out.append(TextLine([TextChar(c.char, tuple(int(v) for v in b), c.logp) for c, b in zip(t.chars(), boxes)], t.score))
+    return out
+
+
 def _work_hw(work_size):
     """None = the page's own size (0, 0)."""
     return (0, 0) if work_size is None else (int(work_size[0]), int(work_size[1]))
@@ -835,6 +948,59 @@ class OcrEngine:
             return inp, deskew_map(hw, 0.0, expand=False)[1], angle
         out_hw, m = deskew_map(hw, angle, expand=expand)
         return self.warp(inp, m, out_hw, fill=fill), m, angle
+
+    # ---- perspective correction
+    def edge_peaks(self, inputs, sc_table, min_step=8):
+        """ocrs_engine_edge_peaks: the directed edge peaks of pages of any sizes (a side at most 4096) at the angles of
+        sc_table (int32 [A, 2]: skew_table) -> uint64 [n, 2 families, 2 signs, A, 16], in one launch."""
+        n = len(inputs)
+        t = np.ascontiguousarray(sc_table, np.int32).reshape(-1, 2)
+        out = np.zeros((n, 2, 2, len(t), 16), np.uint64)
+        check(lib().ocrs_engine_edge_peaks(self._h, _page_array(inputs), C.c_size_t(n), t.ctypes.data_as(C.POINTER(C.c_int32)),
+                                           C.c_size_t(len(t)), C.c_int(int(min_step)), out.ctypes.data_as(C.POINTER(C.c_uint64))))
+        return out
+
+    def find_outline(self, inp, **params):
+        """ocrs_engine_find_outline -> Outline: the four corners of the sheet a photo shows (params: outline_params'
+        keywords).  Uncalibrated on real photographs."""
+        p, info = _outline_struct(**params), _lib.OutlineInfo()
+        check(lib().ocrs_engine_find_outline(self._h, inp._h, C.byref(p), C.byref(info)))
+        return _outline_of(info)
+
+    def project(self, inp, m, out_hw, fill=0.5):
+        """ocrs_engine_project_page: the page seen through the projective map m (eight coefficients: output pixel -> page
+        position) as a new resident page of out_hw = (height, width); a tap outside the page is `fill`."""
+        return self.project_batch([inp], [m], [out_hw], [fill])[0]
+
+    def project_batch(self, inputs, ms, out_hws, fills=0.5):
+        """ocrs_engine_project_pages: pages of any sizes, each with its own map, size and fill (or one fill for all), in
+        one launch."""
+        n = len(inputs)
+        if not isinstance(fills, (list, tuple, np.ndarray)):
+            fills = [fills] * n
+        if len(ms) != n or len(out_hws) != n or len(fills) != n:
+            raise ValueError("project_batch: one map, one size and one fill per page")
+        mm = np.ascontiguousarray(np.concatenate([_map8_arg(m) for m in ms]) if n else np.zeros(0), np.float32)
+        hw = (C.c_int * (2 * n))(*[int(v) for s in out_hws for v in (s[0], s[1])])
+        fl = np.ascontiguousarray(np.asarray(fills, np.float32).reshape(-1))
+        out = (C.c_void_p * n)()
+        check(lib().ocrs_engine_project_pages(self._h, _page_array(inputs), C.c_size_t(n), hw, mm.ctypes.data_as(C.POINTER(C.c_float)),
+                                              fl.ctypes.data_as(C.POINTER(C.c_float)), out))
+        return _new_inputs(out, n)
+
+    def straighten(self, inp, corners=None, fill=0.5):
+        """The sheet a photo shows, upright -> (page, m, outline).  corners: TL, TR, BR, BL as (x, y) (None: what
+        find_outline finds; outline is then its Outline, else None).  m is the map of the projection (quad_map):
+        unproject_rects / unproject_lines with it bring results back to inp's frame.  When nothing is found inp itself
+        comes back, with the identity map."""
+        outline = None
+        if corners is None:
+            outline = self.find_outline(inp)
+            if not outline.found:
+                return inp, quad_map(page_corners(inp.shape[-2:]))[1], outline
+            corners = outline.corners
+        out_hw, m = quad_map(corners)
+        return self.project(inp, m, out_hw, fill=fill), m, outline
 
     # ---- working resolution (DESIGN.md §7.3)
     def resize(self, inp, size, filter="auto"):
@@ -1139,7 +1305,8 @@ class OcrEngine:
         return float(lib().ocrs_engine_detection_threshold(self._h))
 
     # ---- lib.rs:290-300
-    def get_text(self, inp, rectify=False, orientation=None, work_size=None, normalize=None, deskew=None, deskew_fill=0.5):
+    def get_text(self, inp, rectify=False, orientation=None, work_size=None, normalize=None, deskew=None, deskew_fill=0.5,
+                 perspective=None, perspective_fill=0.5):
         """rectify=True: the same sequence (detect_words, find_text_lines, recognize_text) with rectified crops.
         orientation: None reads the page as given; an int turns it by that many quarter turns counter-clockwise first
         (rotate); "auto" by what detect_orientation finds.
@@ -1149,7 +1316,13 @@ class OcrEngine:
         (DESIGN.md §7.4).  Applied first; the turn, the work size and the crops are then those of the normalised page.
         deskew: None reads the page as given; a number straightens a skew of that many degrees first, "auto" one of what
         estimate_skew finds (deskew(); under 0.2 degrees the page is left alone).  Applied after
-        normalisation, which puts paper at +0.5, the default deskew_fill, and after the turn."""
+        normalisation, which puts paper at +0.5, the default deskew_fill, and after the turn.
+        perspective: None reads the page as given; "auto" reads the sheet find_outline finds, four corners (TL, TR, BR, BL
+        as (x, y)) the sheet they span (straighten()).  Applied first, before normalisation: the desk is cut
+        away before normalisation looks at the paper.  get_text returns text alone; callers that want boxes run the steps
+        themselves and bring them back last with unproject_rects / unproject_lines."""
+        if perspective is not None:
+            inp = self.straighten(inp, None if isinstance(perspective, str) and perspective == "auto" else perspective, fill=perspective_fill)[0]
         if normalize is not None and normalize is not False:
             inp = self.normalize(inp, **({} if normalize is True else dict(normalize)))
         if orientation is not None:

@@ -88,6 +88,8 @@ DECLARED_SYMBOLS = [
     "ocrs_normalize_params_default", "ocrs_normalize_params_check", "ocrs_engine_normalize_page", "ocrs_engine_normalize_pages",
     "ocrs_skew_params_default", "ocrs_skew_params_check", "ocrs_skew_table", "ocrs_engine_skew_scores", "ocrs_engine_estimate_skew",
     "ocrs_engine_warp_page", "ocrs_engine_warp_pages", "ocrs_deskew_map", "ocrs_unwarp_rects", "ocrs_unwarp_chars",
+    "ocrs_outline_params_default", "ocrs_outline_params_check", "ocrs_engine_edge_peaks", "ocrs_outline_choose", "ocrs_engine_find_outline",
+    "ocrs_quad_map", "ocrs_engine_project_page", "ocrs_engine_project_pages", "ocrs_unproject_rects", "ocrs_unproject_chars",
 ]
 
 ABI_VERSION = 6   # include/ocrs_amd.h OCRS_ABI_VERSION
@@ -117,6 +119,16 @@ class SkewParams(C.Structure):   # include/ocrs_amd.h ocrs_skew_params
 class SkewInfo(C.Structure):   # include/ocrs_amd.h ocrs_skew_info
     _fields_ = [("angle_deg", C.c_double), ("best_score", C.c_uint64), ("second_score", C.c_uint64), ("fine_score", C.c_uint64),
                 ("work_h", C.c_int32), ("work_w", C.c_int32), ("coarse_index", C.c_int32), ("fine_index", C.c_int32)]
+
+
+class OutlineParams(C.Structure):   # include/ocrs_amd.h ocrs_outline_params
+    _fields_ = [("max_deg", C.c_double), ("step_deg", C.c_double), ("min_cover", C.c_double), ("min_span", C.c_double), ("min_area", C.c_double),
+                ("work_max_side", C.c_int32), ("min_step", C.c_int32)]
+
+
+class OutlineInfo(C.Structure):   # include/ocrs_amd.h ocrs_outline_info
+    _fields_ = [("found", C.c_int32), ("polarity", C.c_int32), ("corners", C.c_float * 8), ("counts", C.c_uint32 * 4), ("angles", C.c_int32 * 4),
+                ("work_h", C.c_int32), ("work_w", C.c_int32)]
 
 
 _lib = None

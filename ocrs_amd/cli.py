@@ -89,6 +89,15 @@ def main(argv=None):
     ap.add_argument("--deskew-fill", type=float, default=None, metavar="X",
                     help="with --deskew: the grey level around the straightened page, -0.5 black .. 0.5 white (default 0.5, the "
                          "paper of a page that went through --normalize)")
+    ap.add_argument("--perspective", nargs="?", const="auto", default=None, metavar="auto|x0,y0,...,x3,y3",
+                    help="straighten a sheet photographed at an angle, on the GPU, before anything else looks at it: eight numbers "
+                         "are the sheet's corners in the file, top-left, top-right, bottom-right, bottom-left as x,y; auto (the "
+                         "default) finds the sheet's outline against the desk (when none is found the page is read as given).  "
+                         "Boxes are reported in the frame of the file as given; the JSON gains \"outline\" (no reference "
+                         "counterpart; uncalibrated on real photographs: DESIGN.md 7.7)")
+    ap.add_argument("--perspective-fill", type=float, default=None, metavar="X",
+                    help="with --perspective: the grey level where the straightened sheet reaches beyond the photo, -0.5 black .. "
+                         "0.5 white (default 0.5)")
     ap.add_argument("-o", "--output")
     ap.add_argument("--debug", action="store_true")
     ap.add_argument("--text-map", action="store_true", help="write text-map.png (detect_text_pixels)")
@@ -107,6 +116,15 @@ def main(argv=None):
         ap.error("--normalize-tile and --normalize-polarity are only valid with --normalize")
     if args.deskew_fill is not None and args.deskew is None:
         ap.error("--deskew-fill is only valid with --deskew")
+    if args.perspective_fill is not None and args.perspective is None:
+        ap.error("--perspective-fill is only valid with --perspective")
+    if args.perspective is not None and args.perspective != "auto":
+        try:
+            args.perspective = [float(v) for v in args.perspective.split(",")]
+        except ValueError:
+            ap.error("--perspective takes auto or eight numbers x0,y0,...,x3,y3")
+        if len(args.perspective) != 8 or not all(np.isfinite(args.perspective)):
+            ap.error("--perspective takes auto or eight numbers x0,y0,...,x3,y3")
     if args.deskew is not None and args.deskew != "auto":
         try:
             args.deskew = float(args.deskew)
@@ -141,6 +159,22 @@ def main(argv=None):
         img = load_image(args.image)
         shape_hw = img.shape[:2]
         inp = engine.prepare_input(ImageSource.from_tensor(img, DimOrder.Hwc))
+    outline, quad_m = None, None
+    if args.perspective is not None:   # from here on the straightened sheet is the page; results are mapped back last
+        corners = None if args.perspective == "auto" else np.array(args.perspective, np.float32).reshape(4, 2)
+        try:
+            flat, m, found = engine.straighten(inp, corners, fill=0.5 if args.perspective_fill is None else args.perspective_fill)
+        except OcrsError as e:
+            if e.status != 1 or corners is None:   # OCRS_ERR_INVALID_ARGUMENT: corners that span no area
+                raise
+            ap.error("--perspective: %s" % e)
+        if found is not None and args.debug:
+            print("Outline: %s, corners %s, polarity %d, edge pixels %s (taken at %dx%d)"
+                  % ("found" if found.found else "none", found.corners.tolist(), found.polarity, list(found.counts), found.work_hw[1], found.work_hw[0]))
+        outline = {"found": flat is not inp, "corners": (corners if found is None else found.corners).tolist()}
+        if flat is not inp:
+            inp, quad_m = flat, m
+    turn_hw = inp.shape[-2:]   # the frame the turn's results come back to
     norm_info = None
     if args.normalize:   # from here on the normalised page is the page; coordinates do not move
         inp, norm_info = engine.normalize(inp, tile=64 if args.normalize_tile is None else args.normalize_tile,
@@ -211,12 +245,17 @@ def main(argv=None):
             word_boxes = [[(unwarp_rects([r], skew_map)[0], s, n) for r, s, n in boxes] for boxes in word_boxes]
     if turns is not None:
         from . import unrotate_lines, unrotate_rects
-        texts = unrotate_lines(texts, tuple(shape_hw), turns)
+        texts = unrotate_lines(texts, tuple(turn_hw), turns)
         if word_boxes is not None:
-            word_boxes = [[(unrotate_rects([r], tuple(shape_hw), turns)[0], s, n) for r, s, n in boxes] for boxes in word_boxes]
+            word_boxes = [[(unrotate_rects([r], tuple(turn_hw), turns)[0], s, n) for r, s, n in boxes] for boxes in word_boxes]
+    if quad_m is not None:
+        from . import unproject_lines, unproject_rects
+        texts = unproject_lines(texts, quad_m)
+        if word_boxes is not None:
+            word_boxes = [[(unproject_rects([r], quad_m)[0], s, n) for r, s, n in boxes] for boxes in word_boxes]
     if args.json:
         content = output.format_json_output(args.image, tuple(shape_hw), texts, confidence=args.confidence, word_boxes=word_boxes,
-                                            orientation=None if turns is None else 90 * turns, normalize=norm_info, skew=skew)
+                                            orientation=None if turns is None else 90 * turns, normalize=norm_info, skew=skew, outline=outline)
     else:
         content = output.format_text_output(texts)
     if args.output:

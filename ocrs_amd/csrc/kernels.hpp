@@ -400,6 +400,33 @@ int64_t warp_blocks(int dh, int dw);   // blocks an output of this size takes (h
 // Pages of any mix of sizes and maps in one launch; total_blocks = the sum of warp_blocks() over the pages.
 void warp_pages(const WarpDesc* d_descs, int n_pages, int total_blocks, hipStream_t s);
 
+// ---- kernels_perspective.hip -------------------------------
+struct EdgeDesc {        // one page whose edge peaks are taken
+    const float* src;    // [h, w]
+    uint32_t* prof;      // [2 families, 2 signs, n_angles, nb] the page's edge counts; zero when the launch starts
+    unsigned long long* peaks;   // [2 families, 2 signs, n_angles, 16]
+    int32_t h, w;        // each 1 .. 4096
+    int32_t nb;          // h + w: dwords per profile
+    int32_t block0;      // first block of this page: the sum of edge_tiles() of the pages before it
+};
+int64_t edge_tiles(int h, int w);   // blocks a page of this size takes (host)
+// Pages of any mix of sizes, two launches on `s`; total_tiles = the sum of edge_tiles() over the pages.  d_sc_table: int32
+// [n_angles, 2] (S, C), each within +-65536.  min_step 1 .. 256.  n_pages <= 65535 (the peak kernel's grid.y), n_angles <= 65535.
+void edge_peaks(const EdgeDesc* d_descs, int n_pages, int total_tiles, const int32_t* d_sc_table, int n_angles, int min_step, hipStream_t s);
+struct ProjDesc {        // one page to project: dst [dh, dw] from src [sh, sw]
+    const float* src;
+    float* dst;          // never overlaps src
+    int32_t sh, sw, dh, dw;   // each 1 .. 65535
+    int32_t block0;      // first block of this page: the sum of project_blocks() of the pages before it
+    int32_t vec;         // dw % 4 == 0 and dst 16-byte aligned, so 16-byte stores are safe
+    float m[8];          // X = ((m0 + m1 fx) + m2 fy) / dn, Y = ((m3 + m4 fx) + m5 fy) / dn, dn = (1 + m6 fx) + m7 fy
+    float fill;          // a tap outside the page, and a pixel whose dn is not finite and positive
+    int32_t pad_;
+};
+int64_t project_blocks(int dh, int dw);   // blocks an output of this size takes (host)
+// Pages of any mix of sizes and maps in one launch; total_blocks = the sum of project_blocks() over the pages.
+void project_pages(const ProjDesc* d_descs, int n_pages, int total_blocks, hipStream_t s);
+
 // kernels_peaks.hip
 void measure_peaks(double* mfma_tflops, double* copy_gbps);
 

@@ -45,7 +45,7 @@ def timed(call, reps):
     return statistics.median(times), min(times)
 
 
-def kernel_durations(trace_dir):
+def kernel_durations(trace_dir, kernels=KERNELS):
     """kernel -> per-launch durations in us in launch order, from a rocprofv3 output directory (kernel-trace CSV, or the
     rocpd database)."""
     import sqlite3
@@ -63,7 +63,7 @@ def kernel_durations(trace_dir):
             name_col = "kernel_name" if "kernel_name" in scols else "display_name"
             rows += list(db.execute("select s.%s, d.start, d.end from %s d join %s s on d.kernel_id = s.id" % (name_col, kd, ks)))
     rows.sort(key=lambda r: r[1])
-    return {name: [(en - st) / 1e3 for n, st, en in rows if name in n] for name in KERNELS}
+    return {name: [(en - st) / 1e3 for n, st, en in rows if name in n] for name in kernels}
 
 
 def traced(reps):
