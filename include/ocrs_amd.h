@@ -111,6 +111,17 @@ OCRS_API ocrs_status ocrs_coalescer_selftest(int n_threads, int requests_per_thr
  *   3 calls on light lane arg, 4 the budget, 5 the number of light lanes. */
 OCRS_API ocrs_status ocrs_stream_plan_selftest(int budget, const int32_t* ops, size_t n_ops, int32_t* out);
 
+/* Test hook (host only, no GPU work) for the two host decisions behind "conv_rows" = 2 (ocrs_engine_set_option).  For a 3x3 conv with
+ * the n_w weights w, the n_bias biases and a fused ReLU or none, and a 4 x 32 patch at image row y0 of an image h rows high
+ * (both multiples of 4) with cin input channels (a multiple of 32):
+ *   out[0]      1 = dropping the matrix-core work of tap rows outside the image changes no bit of this layer's output
+ *               (every weight finite, and a ReLU follows or no bias is -0.0), 0 = the layer keeps that work
+ *   out[1..2]   the K loop's 16-deep chunks [0, out[1]) leave out patch row 0, chunks [out[2], 9 cin / 16) patch row 3
+ *   out[3..5]   per phase of the K loop (taps 0..2, 3..5, 6..8): the patch row that is left out, -1 = none.
+ * With out[0] = 0 nothing is left out. */
+OCRS_API ocrs_status ocrs_conv_rows_selftest(const float* w, size_t n_w, const float* bias, size_t n_bias, int relu, int y0, int h,
+                                             int cin, int32_t out[6]);
+
 /* Integer tuning options (no reference counterpart: RTen's equivalents are compile-time).  They select between kernels
  * that compute the SAME bits — results never depend on an option; the tests run the alternatives against each other.
  *
@@ -292,7 +303,13 @@ OCRS_API void ocrs_engine_free(ocrs_engine* e);
 OCRS_API ocrs_status ocrs_engine_device(const ocrs_engine* e, int* device);
 /* This engine's copy of a tuning option (see ocrs_set_option for the list and the scoping rule).  Also accepted, by
  * field name: "coalesce", "coalesce_pages", "coalesce_window_us", "layout_threads", "rec_max_pixels" (the values as
- * stored: coalesce 0 = off); "numerics" can be read but is fixed when the engine is created. */
+ * stored: coalesce 0 = off); "numerics" can be read but is fixed when the engine is created.
+ * One more name belongs to an engine alone (no process default, no environment variable, not listed by ocrs_option_name):
+ *   "conv_rows"       exact recognition 3x3 convs with 128-column blocks (Cout a multiple of 128, image height a multiple of 4);
+ *                     the same bits at every value.  2 (every new engine's value) = each of a block's four waves owns all four
+ *                     image rows of a 4 x 32 patch and a quarter of the columns, and where the model allows (every weight
+ *                     finite; a ReLU behind the conv or no -0.0 bias) the rows above and below the image cost no matrix-core
+ *                     work; 1 = the same waves, every multiplication kept; 0 = blocks of 2 x 2 waves */
 OCRS_API ocrs_status ocrs_engine_set_option(ocrs_engine* e, const char* name, long value);
 OCRS_API ocrs_status ocrs_engine_get_option(const ocrs_engine* e, const char* name, long* value);
 

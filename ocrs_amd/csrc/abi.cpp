@@ -7,6 +7,7 @@
 #include <atomic>
 #include "abi_util.hpp"
 #include "coalesce_selftest.hpp"
+#include "conv_rows.hpp"
 #include "engine.hpp"
 #include "host_pool.hpp"
 #include "jpeg.hpp"
@@ -84,6 +85,24 @@ ocrs_status ocrs_stream_plan_selftest(int budget, const int32_t* ops, size_t n_o
                 case 5: out[i] = plan.light_lanes(); break;
                 default: fail(OCRS_ERR_INVALID_ARGUMENT, "unknown op %d", (int)op);
             }
+        }
+    });
+}
+
+// Host-only test hook for conv_rows.hpp (the kernel that follows these decisions needs a GPU).
+ocrs_status ocrs_conv_rows_selftest(const float* w, size_t n_w, const float* bias, size_t n_bias, int relu, int y0, int h, int cin,
+                                    int32_t out[6]) {
+    return guarded([&] {
+        if (!out || (n_w > 0 && !w) || (n_bias > 0 && !bias) || h < kConvRowsPatchH || h % kConvRowsPatchH != 0 || y0 < 0 || y0 >= h ||
+            y0 % kConvRowsPatchH != 0 || cin < 2 * kConvRowsChunk || cin % (2 * kConvRowsChunk) != 0)
+            fail(OCRS_ERR_INVALID_ARGUMENT, "bad argument");
+        out[0] = conv_rows_skip_exact(w, n_w, bias, n_bias, relu != 0) ? 1 : 0;
+        const RowPhases ph = conv_row_phases(y0, h, cin, out[0] != 0);
+        out[1] = ph.c_top;
+        out[2] = ph.c_bot;
+        for (int phase = 0; phase < 3; phase++) {   // the chunks of taps 3 phase .. 3 phase + 2
+            const int c = 3 * phase * (cin / kConvRowsChunk);
+            out[3 + phase] = c < ph.c_top ? 0 : c >= ph.c_bot ? kConvRowsPatchH - 1 : -1;
         }
     });
 }

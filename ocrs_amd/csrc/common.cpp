@@ -537,11 +537,13 @@ long option_long(Option o) {
     return g_opts[o].load(std::memory_order_relaxed);
 }
 int option(Option o) { return (int)option_long(o); }
+int conv_rows_setting() { return t_tuning ? (int)__atomic_load_n(&t_tuning->conv_rows, __ATOMIC_RELAXED) : (int)kConvRowsDefault; }
 
 Tuning default_tuning() {
     std::call_once(g_opts_once, init_options);
     Tuning t;
     for (int i = 0; i < OPT_COUNT; i++) t.v[i] = g_opts[i].load(std::memory_order_relaxed);
+    t.conv_rows = kConvRowsDefault;
     return t;
 }
 
@@ -562,6 +564,11 @@ int set_option(const char* name, long value) {
 }
 
 int set_option(Tuning& t, const char* name, long value) {
+    if (name && strcmp(name, "conv_rows") == 0) {   // an engine's setting, not a process option (common.hpp)
+        if (value < 0 || value > 2) return 2;
+        __atomic_store_n(&t.conv_rows, value, __ATOMIC_RELAXED);
+        return 0;
+    }
     const int i = find_option(name, OPT_COUNT);   // an engine's copy: also the configuration fields, by their field names
     if (i < 0) return 1;
     if (i == OPT_STREAM_BUDGET) return 4;         // a device's plan serves every engine on it: the process option only
@@ -571,6 +578,10 @@ int set_option(Tuning& t, const char* name, long value) {
 }
 
 bool get_option(const Tuning& t, const char* name, long* value) {
+    if (name && strcmp(name, "conv_rows") == 0) {
+        *value = __atomic_load_n(&t.conv_rows, __ATOMIC_RELAXED);
+        return true;
+    }
     // "numerics" is listed by neither ocrs_option_name nor set_option (fixed at creation) but can be read
     const int i = name && strcmp(name, "numerics") == 0 ? (int)OPT_NUMERICS : find_option(name, OPT_COUNT);
     if (i < 0) return false;

@@ -207,7 +207,12 @@ enum Option { OPT_GRU_MODE = 0, OPT_GRU_GATES, OPT_GRU_LOCAL, OPT_DET_FUSE, OPT_
               OPT_COALESCE, OPT_COALESCE_PAGES, OPT_COALESCE_WINDOW_US,   // ocrs_engine_params.coalesce*
               OPT_LAYOUT_THREADS, OPT_REC_MAX_PIXELS,                     // ocrs_engine_params.layout_threads / rec_max_pixels
               OPT_COUNT };
-struct Tuning { long v[OPT_COUNT]; };
+// conv_rows is an engine's setting only, outside the table of process options (no default to change, no environment variable):
+// ocrs_engine_set_option / _get_option take it by name.  0 = the exact 128-column recognition convs run blocks of 2 x 2 waves,
+// 1 = row-owning waves, 2 (every engine's initial value) = those without the matrix-core work of out-of-image tap rows.
+constexpr long kConvRowsDefault = 2;
+struct Tuning { long v[OPT_COUNT]; long conv_rows; };
+int conv_rows_setting();                                   // the calling thread's engine's, or the initial value outside an engine call
 Tuning default_tuning();                                   // the process defaults as they are now
 // 0 = set (or a retired name: accepted, ignored), 1 = unknown name, 2 = value outside the option's range,
 // 3 = "stream_budget" while a call is in flight on some device, 4 = "stream_budget" on an engine (it is a device's)

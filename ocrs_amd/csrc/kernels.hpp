@@ -253,6 +253,12 @@ struct RaggedView {          // device pointers live in one metadata upload; pas
     const int32_t* toff2d_flat;
     const int32_t* toff2d_flat2;
     int ntiles2d_flat, ntiles2d_flat2;
+    // the 4 x 32 tables whatever tw says: the row-owning form of conv3x3_ragged (an engine's "conv_rows") tiles no other shape
+    const int32_t* toff2d_32;
+    const int32_t* toff2d_flat_32;
+    const int32_t* toff2d_flat2_32;
+    int ntiles2d_32, ntiles2d_flat_32, ntiles2d_flat2_32;   // 0 when H % 4 != 0
+    int64_t max_tile_px32_;  // max_tile_px_ for 32-column flat tiles (host)
     const int32_t* toff2d_gap;   // 8 x 16 patches over the strip with >= 1 empty column between images (conv12_fused_ragged)
     int ntiles2d_gap;
     int64_t max_tile_px_;    // most pixels in the images one flat tile touches (host)
@@ -277,8 +283,10 @@ bool conv12_fused_ragged(const float* x, const RaggedView& in0, const RaggedView
 void conv12_split_weights(const float* w2_host /* [288][64] */, std::vector<uint16_t>* out);   // host
 // returns false if the shape is not supported (caller falls back to the per-group path)
 // wsplit: the weights cut into bf16 terms (split_mfma.hpp split_weights) or null; used when the calling engine's numerics are not exact
+// skip_exact: dropping the MFMAs of out-of-image tap rows leaves every bit as it is (conv_rows.hpp; "conv_rows" = 2 then does)
 bool conv3x3_ragged(const float* x, const RaggedView& rv, int cin, const float* wt, const float* bias, int cout, int relu,
-                    int ph, int pw, float* y, const RaggedView& out, hipStream_t s, const uint16_t* wsplit = nullptr);
+                    int ph, int pw, float* y, const RaggedView& out, hipStream_t s, const uint16_t* wsplit = nullptr,
+                    bool skip_exact = false);
 void split_weights(const float* w_host, int K, int N, int ldw, std::vector<uint16_t>* out);   // host; N % 128 == 0, K % 16 == 0 (split_mfma.hpp)
 
 // ---- kernels_lines.hip ----------------------------------------------------

@@ -9,8 +9,10 @@
 // is exactly that of the per-group kernels (same fmaf chains, same order), so results
 // are bit-identical.
 #include <algorithm>
+#include <type_traits>
 
 #include "common.hpp"
+#include "conv_rows.hpp"
 #include "kernels.hpp"
 #include "split_mfma.hpp"
 
@@ -274,21 +276,28 @@ void to_seq_packed_ragged(const float* x, const RaggedView& in, int c, const int
 // ---------------------------------------------------------------------------
 constexpr int RG_BM = 128, RG_BK = 16, RG_LDA = RG_BM + 1;
 constexpr int CONV_WAVES = 4;   // blocks per CU of the exact kernels (128 VGPRs)
+static_assert(RG_BK == kConvRowsChunk && RG_BM / 32 == kConvRowsPatchH, "conv_rows.hpp describes this kernel's K loop");
 // FLAT: the patches of a group tile the strip of ALL its images side by side (flat column c = img * Wp + x, Wp = W
 // rounded up to PW) instead of each image on its own, so only the last patch of a GROUP is ragged, not the last
 // patch of every image (group widths are multiples of 50: W / 4 = 87, 112, 137 ... wasted 7 % of the MFMA rows).
 // SPLIT = 3 / 2 (the engine's relaxed / reduced numerics, BN = 128 only): the same patches, activation loads and epilogue,
 // the contraction on the bf16 matrix cores with both operands cut into SPLIT bf16 terms — split_mfma.hpp has the arithmetic,
 // the LDS layout and the pipeline.  Bw is then the weights' split image (split_weights).
-template <int BN, int TW, int PH, int PW, bool FLAT, int SPLIT = 0>   // SPLIT: 0 exact; 3 / 2 = bf16 planes per operand (relaxed / reduced numerics)
+// ROWS = 1 (exact, BN = 128, 4 x 32 patches): the block's 128 columns are split over the four waves instead of 2 x 2 —
+// wave w owns all four image rows of the patch x columns 32 w .. 32 w + 31, one accumulator per image row.  The taps of a
+// row above the image (ky = 0 for image row 0) or below it (ky = 2 for row H - 1) have an all-zero A operand; with `skip`
+// set (the host says when that is exact: conv_rows.hpp) the accumulator of that image row takes no MFMA in those chunks —
+// the same MFMAs in every wave, so the chunk barrier stays balanced and the block itself runs fewer matrix-core cycles.
+template <int BN, int TW, int PH, int PW, int ROWS, bool FLAT, int SPLIT = 0>   // SPLIT: 0 exact; 3 / 2 = bf16 planes per operand (relaxed / reduced numerics)
 __global__ void __launch_bounds__(256, SPLIT == 3 ? 2 : SPLIT == 2 ? 3 : CONV_WAVES)   // (split: 72 / 48 KB of LDS per block)
 conv3x3_ragged_kernel(const float* __restrict__ X, RaggedView rv, int cin, const float* __restrict__ Bw,
                       const float* __restrict__ bias, int cout, int relu, float* __restrict__ Y,
-                      const int64_t* __restrict__ out_poff) {
+                      const int64_t* __restrict__ out_poff, int skip) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     constexpr int NTW = BN / 64;
     constexpr int TH = RG_BM / TW;
     static_assert(TW == 32 || TW == 16, "patch width");
+    static_assert(!ROWS || (SPLIT == 0 && BN == 128 && TW == 32), "row-owning waves: exact, 128 columns, 4 x 32 patches");
     static_assert(!SPLIT || (BN == 128 && RG_BK == 16), "split mode: 128-column blocks, 16-deep chunks");
     constexpr int NP = SPLIT ? SPLIT : 1;               // bf16 planes per operand
     // exact: As [2][BK][LDA] fp32, Bs [2][BK][BN] fp32.  split: As [2][NP planes][128 rows][16 bf16], Bs [4][NP][128 columns][16]
@@ -307,10 +316,11 @@ conv3x3_ragged_kernel(const float* __restrict__ X, RaggedView rv, int cin, const
     // FLAT: column strip of the whole group; the tile starts in image img0 at column xf0 and may run into the next ones
     const int Wp = FLAT ? (PW == 2 ? (W + 1) & ~1 : W) : W;
     const int nimg = FLAT ? rv.n[g] : 1;
-    int rb, img, x0, span = 1;
+    int rb, img, x0, span = 1, cidx;   // cidx: the patch column the tile lies in
     if (FLAT) {
         rb = tile % tiles_h;
-        const int c0 = (tile / tiles_h) * TW;
+        cidx = tile / tiles_h;
+        const int c0 = cidx * TW;
         img = c0 / Wp;
         x0 = c0 - img * Wp;
         span = min(nimg - img, (x0 + TW - 1) / Wp + 1);
@@ -321,6 +331,20 @@ conv3x3_ragged_kernel(const float* __restrict__ X, RaggedView rv, int cin, const
         rb = t2 % tiles_h;
         img = t2 / tiles_h;
         x0 = cb * TW;
+        cidx = cb;
+    }
+    if constexpr (ROWS != 0) {
+        // With the skip a top or bottom block is shorter than a middle one.  Workgroups seem to be dealt to an XCD's shader
+        // engines round robin, and with tiles_h = 4 tile t's patch row t % 4 put all middle blocks on two of them: the H = 16
+        // layers then took as long with the skip as without.  Rotating the patch row by the patch column (a bijection within
+        // the column: the same tiles in another order) gives every engine the same mix.
+        rb = (rb + cidx) % tiles_h;
+        // the same in every lane, but the divisions above leave them in vector registers, where they stay until the epilogue:
+        // registers the K loop of this form has none to spare for
+        rb = __builtin_amdgcn_readfirstlane(rb);
+        img = __builtin_amdgcn_readfirstlane(img);
+        x0 = __builtin_amdgcn_readfirstlane(x0);
+        span = __builtin_amdgcn_readfirstlane(span);
     }
     const int y0 = rb * TH;
     const int n0 = blockIdx.y * BN;
@@ -433,10 +457,10 @@ conv3x3_ragged_kernel(const float* __restrict__ X, RaggedView rv, int cin, const
         }
     };
 
-    f32x16 acc[2][NTW];
+    f32x16 acc[2][NTW];   // ROWS: image row j of the patch is acc[j >> 1][j & 1]
 #pragma unroll
     for (int t = 0; t < NTW; t++) {
-        const int col = n0 + wn * (BN / 2) + t * 32 + l31;
+        const int col = ROWS ? n0 + wave * 32 + l31 : n0 + wn * (BN / 2) + t * 32 + l31;
         const float bv = col < cout ? bias[col] : 0.0f;
 #pragma unroll
         for (int r = 0; r < 16; r++) { acc[0][t][r] = bv; acc[1][t][r] = bv; }
@@ -461,8 +485,54 @@ conv3x3_ragged_kernel(const float* __restrict__ X, RaggedView rv, int cin, const
             }
         }
     };
+    // ROWS: per k-pair four A reads (one per image row), one B read, four MFMAs.  without = the image row whose accumulator
+    // sits the chunk out (-1: none); every accumulator still sees its own k in ascending order.
+    auto compute_rows = [&](int buf, auto without) {
+        constexpr int WO = decltype(without)::value;
+        const float* a = As + buf * RG_BK * RG_LDA + l31;
+        const float* b = Bs + buf * RG_BK * BN + wave * 32 + l31;
+#pragma unroll
+        for (int kp = 0; kp < RG_BK / 2; kp++) {
+            const int kr = 2 * kp + half;
+            const float bt = b[kr * BN];
+#pragma unroll
+            for (int j = 0; j < 4; j++) {
+                if (j == WO) continue;
+                acc[j >> 1][j & 1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[kr * RG_LDA + 32 * j], bt, acc[j >> 1][j & 1], 0, 0, 0);
+            }
+        }
+    };
     const int nchunks = K / RG_BK;  // even: cin % (2*RG_BK) == 0
-    if constexpr (SPLIT != 0) {
+    if constexpr (ROWS != 0) {
+        // chunks are tap-major and a tap is cin / RG_BK (even) chunks: taps 0..2 (ky = 0) are a prefix of the K loop, taps
+        // 6..8 (ky = 2) a suffix; a 4-row image is both top and bottom block
+        const RowPhases ph = conv_row_phases(y0, H, cin, skip != 0);
+        const int c_top = __builtin_amdgcn_readfirstlane(ph.c_top), c_bot = __builtin_amdgcn_readfirstlane(ph.c_bot);
+        // three loop phases (a branch per chunk inside one loop made the register allocator spill ~180 accumulator registers)
+        auto chunk_pairs = [&](int cb, int ce, auto without) {   // the loop of the 2 x 2 form below, over chunks [cb, ce)
+            for (int c = cb; c < ce; c += 2) {
+                load_b((c + 1) * RG_BK, 1);
+                compute_rows(0, without);
+                commit(1, pa1);
+                __syncthreads();
+                const bool more = c + 2 < nchunks;
+                if (more) {
+                    load_a_pair((c + 2) * RG_BK);
+                    load_b((c + 2) * RG_BK, 0);
+                }
+                compute_rows(1, without);
+                if (more) commit(0, pa0);
+                __syncthreads();
+            }
+        };
+        load_a_pair(0);
+        load_b(0, 0);
+        commit(0, pa0);
+        __syncthreads();
+        chunk_pairs(0, c_top, std::integral_constant<int, 0>{});
+        chunk_pairs(c_top, c_bot, std::integral_constant<int, -1>{});
+        chunk_pairs(c_bot, nchunks, std::integral_constant<int, 3>{});
+    } else if constexpr (SPLIT != 0) {
         static_assert(AV == 2, "split::pipeline counts four activation loads per chunk pair");
         split::pipeline<NP>(nchunks,   // nchunks % 4 == 0 (cin % 64 == 0: the host checks)
                             [&](int k0, f32x4 (&d0)[AV], f32x4 (&d1)[AV]) { load_a_into(k0, d0, d1); },
@@ -507,7 +577,44 @@ conv3x3_ragged_kernel(const float* __restrict__ X, RaggedView rv, int cin, const
     // split::pipeline ends behind a drained barrier, the operand buffers are idle there too).  The pooled layers store half / a quarter as
     // much and get SLOWER through the tile (9.87-9.89 -> 10.23-10.28 ms, whether each half or both halves' outputs are staged
     // at once): they keep the direct form below.
-    if (PH == 1 && PW == 1 && n0 + BN <= cout && (cout & 3) == 0 && (((uintptr_t)Y) & 15) == 0) {
+    // ROWS: GEMM row 32 j + q is patch pixel (ty = j, tx = q); the staging tile is 32 pixels x 32 channels per image row.
+    // The lane's coordinates are worked out afresh here (mbcnt, the wave number through a scalar register): kept from the
+    // prologue they are registers the K loop has none to spare for, and the compiler parked them in scratch.
+    const int wave_e = ROWS ? __builtin_amdgcn_readfirstlane(wave) : wave;
+    const int lane_e = ROWS ? (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u)) : lane;
+    const int half_e = ROWS ? lane_e >> 5 : half, l31_e = ROWS ? lane_e & 31 : l31;
+    if constexpr (ROWS != 0) {
+        if (PH == 1 && PW == 1 && (((uintptr_t)Y) & 15) == 0) {   // (cout % 128 == 0: the host checks)
+            constexpr int WN = 32, LPR = WN / 4, RPI = 64 / LPR, NIT = 32 / RPI;
+            float* stage = lds + wave_e * (32 * WN);
+            const int srow = lane_e / LPR, sc4 = (lane_e % LPR) * 4;
+            int soff[NIT];
+#pragma unroll
+            for (int it = 0; it < NIT; it++) {
+                int x = x0 + it * RPI + srow, ir = 0;
+                if (FLAT) {
+#pragma unroll
+                    for (int k = 0; k < 3; k++) { const bool nx = x >= Wp; x -= nx ? Wp : 0; ir += nx; }
+                }
+                soff[it] = (x < W && (!FLAT || ir < span)) ? ((FLAT ? ir * Ho * Wo : 0) + x) * cout + n0 + wave_e * WN + sc4 : -1;
+            }
+#pragma unroll
+            for (int j = 0; j < 4; j++) {
+#pragma unroll
+                for (int r = 0; r < 16; r++) stage[((r & 3) + 8 * (r >> 2) + 4 * half_e) * WN + l31_e] = act(acc[j >> 1][j & 1][r]);
+                asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+#pragma unroll
+                for (int it = 0; it < NIT; it++) {
+                    if (soff[it] < 0) continue;
+                    *reinterpret_cast<f32x4*>(&C[soff[it] + (y0 + j) * Wo * cout]) =
+                        *reinterpret_cast<const f32x4*>(&stage[(it * RPI + srow) * WN + sc4]);
+                }
+                asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+            }
+            return;
+        }
+    }
+    if (!ROWS && PH == 1 && PW == 1 && n0 + BN <= cout && (cout & 3) == 0 && (((uintptr_t)Y) & 15) == 0) {
         constexpr int WN = BN / 2, LPR = WN / 4, RPI = 64 / LPR, NIT = 32 / RPI;
         static_assert(SPLIT != 0 || 4 * 32 * WN <= 2 * RG_BK * RG_LDA + 2 * RG_BK * BN, "staging must fit the operand tiles");   // split: 48 / 72 KB
         float* stage = lds + wave * (32 * WN);
@@ -550,12 +657,37 @@ conv3x3_ragged_kernel(const float* __restrict__ X, RaggedView rv, int cin, const
 #pragma unroll
         for (int jx = 0; jx < NX; jx++) {
             if (PW == 2 && (jx & 1)) { xo_off[jx] = -1; continue; }
-            const int q = (jx & 3) + 8 * (jx >> 2) + 4 * half;
+            const int q = (jx & 3) + 8 * (jx >> 2) + 4 * half_e;
             int x = x0 + (TW == 32 ? q : (q & 15)), ir = 0;
 #pragma unroll
             for (int k = 0; k < 3; k++) { const bool nx = x >= Wp; x -= nx ? Wp : 0; ir += nx; }
             xo_off[jx] = (x + (PW - 1) < W && ir < span) ? (ir * Ho * Wo + x / PW) * cout : -1;
         }
+    }
+    if constexpr (ROWS != 0) {   // vertical pooling partner: image row j ^ 1, same register; horizontal: r + 1
+        const int col = n0 + wave_e * 32 + l31_e;
+#pragma unroll
+        for (int j = 0; j < 4; j++) {
+            if (PH == 2 && (j & 1)) continue;
+#pragma unroll
+            for (int r = 0; r < 16; r++) {
+                if (PW == 2 && (r & 1)) continue;
+                const int x = x0 + (r & 3) + 8 * (r >> 2) + 4 * half_e;
+                if (FLAT ? xo_off[r] < 0 : x + (PW - 1) >= W) continue;
+                const f32x16& a0 = acc[j >> 1][j & 1];
+                const f32x16& a1 = acc[(j ^ 1) >> 1][(j ^ 1) & 1];
+                float m = act(a0[r]);
+                if (PW == 2) { const float v = act(a0[(r + 1) & 15]); m = v > m ? v : m; }
+                if (PH == 2) {
+                    { const float v = act(a1[r]); m = v > m ? v : m; }
+                    if (PW == 2) { const float v = act(a1[(r + 1) & 15]); m = v > m ? v : m; }
+                }
+                const int yo = (y0 + j) / PH;
+                if (FLAT) C[xo_off[r] + yo * Wo * cout + col] = m;
+                else C[((int64_t)yo * Wo + x / PW) * cout + col] = m;
+            }
+        }
+        return;
     }
 #pragma unroll
     for (int t = 0; t < NTW; t++) {
@@ -1071,11 +1203,25 @@ void split_weights(const float* w, int K, int N, int ldw, std::vector<uint16_t>*
         }
 }
 
-bool conv3x3_ragged(const float* x, const RaggedView& rv, int cin, const float* wt, const float* bias, int cout, int relu,
-                    int ph, int pw, float* y, const RaggedView& out, hipStream_t s, const uint16_t* wsplit) {
+bool conv3x3_ragged(const float* x, const RaggedView& rv_in, int cin, const float* wt, const float* bias, int cout, int relu,
+                    int ph, int pw, float* y, const RaggedView& out, hipStream_t s, const uint16_t* wsplit, bool skip_exact) {
     if ((cin % (2 * RG_BK)) != 0 || (cout % 4) != 0 || cout < 64) return false;
     if (!((ph == 1 && pw == 1) || (ph == 2 && (pw == 1 || pw == 2)))) return false;
     if ((ph == 2 || pw == 2) && !relu) return false;  // the fused pool assumes ReLU'd (non-negative, NaN-free order) inputs
+    // an engine's "conv_rows": the exact 128-column kernel with row-owning waves (1), dropping the edge-row MFMAs where the model
+    // allows (2).  It tiles 4 x 32 patches whatever shape the view chose for the 2 x 2 form.
+    const int rows_opt = conv_rows_setting();
+    const bool exact = !(wsplit && (cin % 64) == 0 && option(OPT_NUMERICS) != 0);
+    const bool rows = rows_opt != 0 && exact && (cout % 128) == 0 && rv_in.H % 4 == 0;
+    const int skip = rows && rows_opt == 2 && skip_exact ? 1 : 0;
+    RaggedView rv = rv_in;
+    if (rows) {
+        rv.tw = 32;
+        rv.toff2d = rv_in.toff2d_32; rv.ntiles2d = rv_in.ntiles2d_32;
+        rv.toff2d_flat = rv_in.toff2d_flat_32; rv.ntiles2d_flat = rv_in.ntiles2d_flat_32;
+        rv.toff2d_flat2 = rv_in.toff2d_flat2_32; rv.ntiles2d_flat2 = rv_in.ntiles2d_flat2_32;
+        rv.max_tile_px_ = rv_in.max_tile_px32_;
+    }
     if (rv.tw != 32 && rv.tw != 16) return false;
     if (rv.H % (RG_BM / rv.tw) != 0) return false;
     // flat tiling: 32-bit element offsets inside a tile's images, at most three image borders per patch row
@@ -1094,9 +1240,9 @@ bool conv3x3_ragged(const float* x, const RaggedView& rv, int cin, const float* 
     const dim3 grid(ntiles, (cout + (n64 ? 63 : 127)) / (n64 ? 64 : 128));
 #define OCRS_LAUNCH_SPLIT(TW_, PH_, PW_, FLAT_, NP_, SLOT_)                                                              \
     if (flat == FLAT_ && (numerics == 2 ? 2 : 3) == NP_) {                                                              \
-        allow_dynamic_lds(reinterpret_cast<const void*>(&conv3x3_ragged_kernel<128, TW_, PH_, PW_, FLAT_, NP_>), ok_[SLOT_]);   \
-        hipLaunchKernelGGL((conv3x3_ragged_kernel<128, TW_, PH_, PW_, FLAT_, NP_>), grid, dim3(256), lds, s, x, rv, cin, ws_, bias, \
-                           cout, relu, y, out.poff);                                                                    \
+        allow_dynamic_lds(reinterpret_cast<const void*>(&conv3x3_ragged_kernel<128, TW_, PH_, PW_, 0, FLAT_, NP_>), ok_[SLOT_]);   \
+        hipLaunchKernelGGL((conv3x3_ragged_kernel<128, TW_, PH_, PW_, 0, FLAT_, NP_>), grid, dim3(256), lds, s, x, rv, cin, ws_, bias, \
+                           cout, relu, y, out.poff, 0);                                                                 \
     }
 #define OCRS_LAUNCH_CONV(BN_, TW_, PH_, PW_)                                                                            \
     do {                                                                                                                \
@@ -1105,10 +1251,17 @@ bool conv3x3_ragged(const float* x, const RaggedView& rv, int cin, const float* 
             static std::atomic<uint64_t> ok_[4] = {};                                                                    \
             OCRS_LAUNCH_SPLIT(TW_, PH_, PW_, true, 3, 0) OCRS_LAUNCH_SPLIT(TW_, PH_, PW_, false, 3, 1)                     \
             OCRS_LAUNCH_SPLIT(TW_, PH_, PW_, true, 2, 2) OCRS_LAUNCH_SPLIT(TW_, PH_, PW_, false, 2, 3)                     \
-        } else if (flat) hipLaunchKernelGGL((conv3x3_ragged_kernel<BN_, TW_, PH_, PW_, true>), grid, dim3(256), lds, s, x, rv, \
-                                     cin, wt, bias, cout, relu, y, out.poff);                                           \
-        else hipLaunchKernelGGL((conv3x3_ragged_kernel<BN_, TW_, PH_, PW_, false>), grid, dim3(256), lds, s, x, rv,     \
-                                cin, wt, bias, cout, relu, y, out.poff);                                                \
+        } else if (flat) hipLaunchKernelGGL((conv3x3_ragged_kernel<BN_, TW_, PH_, PW_, 0, true>), grid, dim3(256), lds, s, x, rv, \
+                                     cin, wt, bias, cout, relu, y, out.poff, 0);                                        \
+        else hipLaunchKernelGGL((conv3x3_ragged_kernel<BN_, TW_, PH_, PW_, 0, false>), grid, dim3(256), lds, s, x, rv,  \
+                                cin, wt, bias, cout, relu, y, out.poff, 0);                                             \
+    } while (0)
+#define OCRS_LAUNCH_ROWS(PH_, PW_)                                                                                      \
+    do {                                                                                                                \
+        if (flat) hipLaunchKernelGGL((conv3x3_ragged_kernel<128, 32, PH_, PW_, 1, true>), grid, dim3(256), lds, s, x, rv, cin, wt, \
+                                     bias, cout, relu, y, out.poff, skip);                                              \
+        else hipLaunchKernelGGL((conv3x3_ragged_kernel<128, 32, PH_, PW_, 1, false>), grid, dim3(256), lds, s, x, rv, cin, wt, \
+                                bias, cout, relu, y, out.poff, skip);                                                   \
     } while (0)
 #define OCRS_DISPATCH_POOL(BN_, TW_)                              \
     do {                                                          \
@@ -1116,12 +1269,17 @@ bool conv3x3_ragged(const float* x, const RaggedView& rv, int cin, const float* 
         else if (pw == 1) OCRS_LAUNCH_CONV(BN_, TW_, 2, 1);       \
         else OCRS_LAUNCH_CONV(BN_, TW_, 2, 2);                    \
     } while (0)
-    if (n64) {
+    if (rows) {
+        if (ph == 1) OCRS_LAUNCH_ROWS(1, 1);
+        else if (pw == 1) OCRS_LAUNCH_ROWS(2, 1);
+        else OCRS_LAUNCH_ROWS(2, 2);
+    } else if (n64) {
         if (rv.tw == 32) OCRS_DISPATCH_POOL(64, 32); else OCRS_DISPATCH_POOL(64, 16);
     } else {
         if (rv.tw == 32) OCRS_DISPATCH_POOL(128, 32); else OCRS_DISPATCH_POOL(128, 16);
     }
 #undef OCRS_DISPATCH_POOL
+#undef OCRS_LAUNCH_ROWS
 #undef OCRS_LAUNCH_CONV
 #undef OCRS_LAUNCH_SPLIT
     return true;

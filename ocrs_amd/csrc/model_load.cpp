@@ -1,5 +1,6 @@
 // Model files: HipModel::load (validate on the host, build and upload the weight slab, mark what run_device fuses),
 // shape inference, and the caller-implemented model.
+#include "conv_rows.hpp"
 #include "model_exec.hpp"
 
 namespace ocrs {
@@ -221,6 +222,16 @@ void upload_split_images(HipModel& m, const ParsedFile& pf, const std::vector<Fi
     }
 }
 
+// Option "conv_rows": which 3x3 convs may drop the matrix-core work of tap rows outside the image without changing a bit.
+void mark_skip_exact(HipModel& m, const ParsedFile& pf) {
+    for (size_t i = 0; i < m.ops.size(); i++) {
+        GraphOp& op = m.ops[i];
+        if (op.type != OP_CONV || op.kh != 3 || op.kw != 3) continue;
+        const FileOp& f = pf.fops[i];
+        op.skip_exact = conv_rows_skip_exact(pf.blob + f.w[0].off, f.w[0].cnt, pf.blob + f.w[1].off, f.w[1].cnt, op.relu != 0);
+    }
+}
+
 // Pairs of neighbouring ops that run_device executes as one launch.
 void mark_fusions(HipModel& m) {
     std::vector<GraphOp>& ops = m.ops;
@@ -354,6 +365,7 @@ std::unique_ptr<HipModel> HipModel::load(const void* data, size_t len, int devic
     m->device = ctx().device;
     upload_slab(*m, pf, fixes);
     upload_split_images(*m, pf, fixes);
+    mark_skip_exact(*m, pf);
     mark_fusions(*m);
     find_double_conv_blocks(*m, pf);
     return m;

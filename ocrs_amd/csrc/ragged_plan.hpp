@@ -63,14 +63,20 @@ struct RaggedPlan {
         v.toff2d = d32 + t2d.off; v.ntiles2d = t2d.total;
         v.toff2d_flat = d32 + flat[0].off; v.ntiles2d_flat = flat[0].total;
         v.toff2d_flat2 = d32 + flat[1].off; v.ntiles2d_flat2 = flat[1].total;
+        const bool has32 = l.H % 4 == 0;
+        v.toff2d_32 = d32 + l.t32.off; v.ntiles2d_32 = has32 ? l.t32.total : 0;
+        v.toff2d_flat_32 = d32 + l.f32[0].off; v.ntiles2d_flat_32 = has32 ? l.f32[0].total : 0;
+        v.toff2d_flat2_32 = d32 + l.f32[1].off; v.ntiles2d_flat2_32 = has32 ? l.f32[1].total : 0;
         v.toff2d_gap = d32 + l.gap.off;
         v.ntiles2d_gap = l.H % 8 == 0 ? l.gap.total : 0;
         v.max_w = 0;
         v.max_tile_px_ = 0;
+        v.max_tile_px32_ = 0;
         v.min_w = INT32_MAX;
         for (int g = 0; g < G; g++) {
             const int64_t w = l.W[g], span = std::min<int64_t>(n[g], (v.tw - 1 + w - 1) / w + 1);
             v.max_tile_px_ = std::max(v.max_tile_px_, span * l.H * w);
+            v.max_tile_px32_ = std::max(v.max_tile_px32_, std::min<int64_t>(n[g], (32 - 1 + w - 1) / w + 1) * l.H * w);
             v.min_w = std::min(v.min_w, (int)w);
             v.max_w = std::max(v.max_w, (int)w);
         }
