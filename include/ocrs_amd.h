@@ -691,6 +691,65 @@ OCRS_API ocrs_status ocrs_engine_project_pages(const ocrs_engine* e, const ocrs_
                                                const float* m, const float* fill, ocrs_page** out);
 OCRS_API ocrs_status ocrs_unproject_rects(float* rects6, size_t n, const float m[8]);
 
+/* ------------------------------------------------------------------------
+ * Ruled-line removal (no reference counterpart, opt-in).  Forms, invoices, tables, ruled paper and
+ * underlined headings: a rule that touches or crosses a line of text ends up inside the word boxes and inside every
+ * recognition crop cut from them.  These calls make a new resident page on which the long thin rules are overwritten with
+ * the paper's level and every other pixel keeps its own 32-bit word (NaN payloads and -0.0 included); coordinates do not
+ * move, so nothing needs mapping back.  The source page is untouched; release both with ocrs_page_free in any order.  The
+ * page is dark ink on light paper (ocrs_engine_normalize_page makes it so) and its rules are axis-aligned (deskew first).
+ * What a trained detector or recogniser gains is uncalibrated.
+ *
+ * The definition (tests/rules_ref.py restates it and the library equals it bit for bit; integer and set arithmetic, so the
+ * result does not depend on schedule or batch).  open_h(X, n): the pixels of X in a maximal horizontal run of X of
+ * length >= n; open_v the same along columns; the page edge ends a run.  With L = min_length, T = max_thickness,
+ * M = margin:
+ *   ink        v < threshold, an ordinary float compare: NaN is not ink, -inf is.
+ *   candidates Ch = open_h(ink, L), Cv = open_v(ink, L); text = ink \ (Ch u Cv).
+ *   thickness  Rh = Ch \ open_v(Ch, T + 1), Rv = Cv \ open_h(Cv, T + 1): a solid dark block is not a rule.
+ *   crossings  a pixel of Rh is kept when the vertical run of Rh through it has a text pixel right above its first and
+ *              right below its last pixel (a stroke that crosses the rule; a stroke that ends on it is not kept, nor is a
+ *              grid intersection, text holding no candidate): Kh; Dh = Rh \ Kh.  Kv, Dv with rows and columns exchanged.
+ *   margins    Mh: the pixels that are not ink within M rows of a Dh pixel of their column (the half-tone edge of an
+ *              anti-aliased rule); Mv likewise along rows.  A NaN pixel is not ink and may be overwritten here.
+ *   fill       the pixels that are neither ink nor NaN are counted in the bins of the normalisation above
+ *              (g = clamp(v + 0.5f, 0, 1), bin = floor(g * 256f) within 0 .. 255); paper_bin = pct(1, 2), 255 with nothing
+ *              counted; fill = (paper_bin + 1) / 256 - 0.5 (+0.5 on a normalised page).  With paper given (not NaN):
+ *              fill = paper, paper_bin = -1, the counts are still made.
+ *   output     fill on D = Dh u Dv u Mh u Mv, the page's own word elsewhere.
+ *
+ * ocrs_rules_params_default: threshold 0, min_length 96, max_thickness 8, margin 1, paper NaN.  ocrs_rules_params_check
+ * (host only): OCRS_ERR_INVALID_ARGUMENT for a threshold that is not finite, a min_length outside 2 .. 65535, a
+ * max_thickness outside 1 .. 64, a margin outside 0 .. 8 or an infinite paper; the engine calls refuse the same, and a page
+ * with a side over 65535.  ocrs_engine_remove_rules_pages serves n pages of any sizes, each with its own params[i], in eight
+ * launches for the whole batch on one stream; out_pages[n] receives the pages, out_infos[n] (may be NULL) what was found,
+ * out_masks[n] (may be NULL) per page a host uint8 [h][w], to be released with ocrs_buffer_free: bit 0 Dh, bit 1 Dv,
+ * bit 2 Mh u Mv, bit 3 Kh u Kv.  ocrs_engine_remove_rules_page: params == NULL means the default. */
+typedef struct ocrs_rules_params {
+    float threshold;       /* finite; ink is v < threshold */
+    int32_t min_length;    /* L, 2 .. 65535 */
+    int32_t max_thickness; /* T, 1 .. 64 */
+    int32_t margin;        /* M, 0 .. 8 */
+    float paper;           /* the fill; NaN: measured on the page */
+} ocrs_rules_params;
+typedef struct ocrs_rules_info {
+    int32_t paper_bin;     /* the bin the fill was taken from; -1: paper was given */
+    float fill;            /* what the removed pixels were overwritten with */
+    uint64_t ink;          /* pixels under the threshold */
+    uint64_t counted;      /* pixels that are neither ink nor NaN */
+    uint64_t h_removed;    /* |Dh| */
+    uint64_t v_removed;    /* |Dv| */
+    uint64_t overwritten;  /* |D| */
+    uint64_t kept;         /* |Kh u Kv| */
+} ocrs_rules_info;
+OCRS_API ocrs_status ocrs_rules_params_default(ocrs_rules_params* out);
+OCRS_API ocrs_status ocrs_rules_params_check(const ocrs_rules_params* params);
+OCRS_API ocrs_status ocrs_engine_remove_rules_page(const ocrs_engine* e, const ocrs_page* page, const ocrs_rules_params* params,
+                                                   ocrs_page** out_page, uint8_t** out_mask, ocrs_rules_info* out_info);
+OCRS_API ocrs_status ocrs_engine_remove_rules_pages(const ocrs_engine* e, const ocrs_page* const* pages, size_t n,
+                                                    const ocrs_rules_params* params, ocrs_page** out_pages, uint8_t** out_masks,
+                                                    ocrs_rules_info* out_infos);
+
 /* OcrEngine::detection_threshold (lib.rs:282-287). */
 OCRS_API float ocrs_engine_detection_threshold(const ocrs_engine* e);
 

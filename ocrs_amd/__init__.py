@@ -16,7 +16,7 @@ from ._lib import OcrsError, check, lib
 
 __all__ = ["OcrEngine", "OcrEngineParams", "ImageSource", "ImageSourceError", "DimOrder", "DecodeMethod", "Model",
            "OcrInput", "TextLine", "TextWord", "TextChar", "OcrsError", "DEFAULT_ALPHABET", "EngineGroup", "line_frame",
-           "Orientation", "orientation_vote", "unrotate_rects", "unrotate_lines", "work_size", "rescale_rects", "normalize_params"]
+           "Orientation", "orientation_vote", "unrotate_rects", "unrotate_lines", "work_size", "rescale_rects", "normalize_params", "rules_params"]
 
 # lib.rs:34 (with the EUR sign the comment at lib.rs:33 asks for)
 DEFAULT_ALPHABET = " 0123456789!\"#$%&'()*+,-./:;<=>?@[\\]^_`{|}~€ABCDEFGHIJKLMNOPQRSTUVWXYZabcdefghijklmnopqrstuvwxyz"
@@ -486,6 +486,31 @@ def _normalize_struct(tile=None, polarity=None, flatten=None, levels=None):
     return p
 
 
+def rules_params(min_length=None, max_thickness=None, margin=None, threshold=None, paper=None):
+    """ocrs_rules_params as a dict: ocrs_rules_params_default (min_length 96, max_thickness 8, margin 1,
+    threshold 0, paper None = measured) with the given fields replaced, checked by ocrs_rules_params_check (host only)."""
+    p = _rules_struct(min_length, max_thickness, margin, threshold, paper)
+    check(lib().ocrs_rules_params_check(C.byref(p)))
+    return {"min_length": int(p.min_length), "max_thickness": int(p.max_thickness), "margin": int(p.margin), "threshold": float(p.threshold),
+            "paper": None if p.paper != p.paper else float(p.paper)}
+
+
+def _rules_struct(min_length=None, max_thickness=None, margin=None, threshold=None, paper=None):
+    p = _lib.RulesParams()
+    check(lib().ocrs_rules_params_default(C.byref(p)))
+    if min_length is not None:
+        p.min_length = int(min_length)
+    if max_thickness is not None:
+        p.max_thickness = int(max_thickness)
+    if margin is not None:
+        p.margin = int(margin)
+    if threshold is not None:
+        p.threshold = float(threshold)
+    if paper is not None:
+        p.paper = float(paper)
+    return p
+
+
 class Skew:
     """ocrs_engine_estimate_skew's outputs: angle (degrees; the page's content is turned counter-clockwise
     by it, deskew_map(.., angle) undoes it), scores (best coarse, runner-up coarse, at the angle), work_hw (the size the
@@ -892,6 +917,47 @@ class OcrEngine:
         check(lib().ocrs_engine_normalize_pages(self._h, pages, C.c_size_t(n), ps, out, infos if info else None))
         made = _new_inputs(out, n)
         return (made, [infos[i].as_dict() for i in range(n)]) if info else made
+
+    # ---- ruled-line removal
+    def remove_rules(self, inp, min_length=96, max_thickness=8, margin=1, threshold=0.0, paper=None, mask=False, info=False):
+        """ocrs_engine_remove_rules_page: the page with its long thin rules (table grids, form lines, underlines) overwritten
+        by the paper's level, as a new resident page of the same size; every other pixel keeps its bits.  The page is dark ink
+        on light paper (normalize makes it so) with axis-aligned rules (deskew first).  A rule: ink (< threshold) in a run of
+        at least min_length pixels, at most max_thickness thick; margin: the rows and columns of half-tone edge taken with it;
+        paper: the fill, None = the page's median paper level.  A stroke that crosses a rule is kept.  mask=True: also the
+        uint8 [H, W] mask (bit 0 horizontal rule, 1 vertical rule, 2 margin, 3 kept crossing); info=True: also {"paper_bin",
+        "fill", "ink", "counted", "h_removed", "v_removed", "overwritten", "kept"}.  -> page, or (page[, mask][, info])."""
+        out = self.remove_rules_batch([inp], [{"min_length": min_length, "max_thickness": max_thickness, "margin": margin,
+                                               "threshold": threshold, "paper": paper}], mask=mask, info=info)
+        return tuple(o[0] for o in out) if mask or info else out[0]
+
+    def remove_rules_batch(self, inputs, params=None, mask=False, info=False):
+        """ocrs_engine_remove_rules_pages: pages of any sizes, each with its own parameters (a dict of remove_rules's keywords,
+        or None for the default; one for all, or one per page), all passes for the whole batch on one stream.  -> pages, or
+        (pages[, masks][, infos])."""
+        n = len(inputs)
+        if params is None or isinstance(params, dict):
+            params = [params] * n
+        if len(params) != n:
+            raise ValueError("remove_rules_batch: one parameter set per page")
+        pages = _page_array(inputs)
+        ps = (_lib.RulesParams * n)(*[_rules_struct(**(p or {})) for p in params])
+        out = (C.c_void_p * n)()
+        masks = (C.POINTER(C.c_uint8) * n)()
+        infos = (_lib.RulesInfo * n)()
+        check(lib().ocrs_engine_remove_rules_pages(self._h, pages, C.c_size_t(n), ps, out, masks if mask else None, infos if info else None))
+        made = _new_inputs(out, n)
+        res = [made]
+        if mask:
+            got = []
+            for i in range(n):
+                h, w = made[i].shape[-2:]
+                got.append(np.ctypeslib.as_array(masks[i], shape=(h * w,)).reshape(h, w).copy())
+                lib().ocrs_buffer_free(masks[i])
+            res.append(got)
+        if info:
+            res.append([infos[i].as_dict() for i in range(n)])
+        return tuple(res) if mask or info else made
 
     # ---- page deskew (DESIGN.md §7.6)
     def skew_scores(self, inputs, sc_table):
@@ -1306,7 +1372,7 @@ class OcrEngine:
 
     # ---- lib.rs:290-300
     def get_text(self, inp, rectify=False, orientation=None, work_size=None, normalize=None, deskew=None, deskew_fill=0.5,
-                 perspective=None, perspective_fill=0.5):
+                 perspective=None, perspective_fill=0.5, rules=None):
         """rectify=True: the same sequence (detect_words, find_text_lines, recognize_text) with rectified crops.
         orientation: None reads the page as given; an int turns it by that many quarter turns counter-clockwise first
         (rotate); "auto" by what detect_orientation finds.
@@ -1319,7 +1385,10 @@ class OcrEngine:
         normalisation, which puts paper at +0.5, the default deskew_fill, and after the turn.
         perspective: None reads the page as given; "auto" reads the sheet find_outline finds, four corners (TL, TR, BR, BL
         as (x, y)) the sheet they span (straighten()).  Applied first, before normalisation: the desk is cut
-        away before normalisation looks at the paper.  get_text returns text alone; callers that want boxes run the steps
+        away before normalisation looks at the paper.
+        rules: None reads the page as given; True or a dict of remove_rules()'s keywords reads the page with its ruled lines
+        removed.  Applied after perspective, normalisation, the turn and deskew, because rules must be
+        axis-aligned, and before detection.  get_text returns text alone; callers that want boxes run the steps
         themselves and bring them back last with unproject_rects / unproject_lines."""
         if perspective is not None:
             inp = self.straighten(inp, None if isinstance(perspective, str) and perspective == "auto" else perspective, fill=perspective_fill)[0]
@@ -1330,6 +1399,8 @@ class OcrEngine:
             inp = self.rotate(inp, k)
         if deskew is not None:
             inp = self.deskew(inp, None if deskew == "auto" else float(deskew), fill=deskew_fill)[0]
+        if rules is not None and rules is not False:
+            inp = self.remove_rules(inp, **({} if rules is True else dict(rules)))
         if work_size is not None or rectify:
             lines = self.find_text_lines(inp, self.detect_words(inp, work_size=work_size))
             return "\n".join(str(t) for t in self.recognize_text(inp, lines, rectify=rectify) if t is not None)

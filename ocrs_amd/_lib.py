@@ -90,6 +90,7 @@ DECLARED_SYMBOLS = [
     "ocrs_engine_warp_page", "ocrs_engine_warp_pages", "ocrs_deskew_map", "ocrs_unwarp_rects", "ocrs_unwarp_chars",
     "ocrs_outline_params_default", "ocrs_outline_params_check", "ocrs_engine_edge_peaks", "ocrs_outline_choose", "ocrs_engine_find_outline",
     "ocrs_quad_map", "ocrs_engine_project_page", "ocrs_engine_project_pages", "ocrs_unproject_rects", "ocrs_unproject_chars",
+    "ocrs_rules_params_default", "ocrs_rules_params_check", "ocrs_engine_remove_rules_page", "ocrs_engine_remove_rules_pages",
 ]
 
 ABI_VERSION = 6   # include/ocrs_amd.h OCRS_ABI_VERSION
@@ -109,6 +110,20 @@ class NormalizeInfo(C.Structure):   # include/ocrs_amd.h ocrs_normalize_info
     def as_dict(self):
         return {"dark": int(self.dark), "vote": int(self.vote), "white": int(self.white), "lo": int(self.lo), "hi": int(self.hi),
                 "counted": int(self.counted)}
+
+
+class RulesParams(C.Structure):   # include/ocrs_amd.h ocrs_rules_params
+    _fields_ = [("threshold", C.c_float), ("min_length", C.c_int32), ("max_thickness", C.c_int32), ("margin", C.c_int32), ("paper", C.c_float)]
+
+
+class RulesInfo(C.Structure):   # include/ocrs_amd.h ocrs_rules_info
+    _fields_ = [("paper_bin", C.c_int32), ("fill", C.c_float), ("ink", C.c_uint64), ("counted", C.c_uint64), ("h_removed", C.c_uint64),
+                ("v_removed", C.c_uint64), ("overwritten", C.c_uint64), ("kept", C.c_uint64)]
+
+    def as_dict(self):
+        return {"paper_bin": int(self.paper_bin), "fill": float(self.fill), "ink": int(self.ink), "counted": int(self.counted),
+                "h_removed": int(self.h_removed), "v_removed": int(self.v_removed), "overwritten": int(self.overwritten),
+                "kept": int(self.kept)}
 
 
 class SkewParams(C.Structure):   # include/ocrs_amd.h ocrs_skew_params

@@ -98,6 +98,17 @@ def main(argv=None):
     ap.add_argument("--perspective-fill", type=float, default=None, metavar="X",
                     help="with --perspective: the grey level where the straightened sheet reaches beyond the photo, -0.5 black .. "
                          "0.5 white (default 0.5)")
+    ap.add_argument("--remove-rules", action="store_true",
+                    help="take the ruled lines of forms, tables and underlines out of the page on the GPU before reading it: long "
+                         "thin runs of ink are overwritten with the paper's level, strokes that cross them are kept (after "
+                         "--normalize, --orientation and --deskew: the rules must be axis-aligned dark ink on light paper); the "
+                         "JSON gains \"rules\" (no reference counterpart; what a detector gains is uncalibrated: DESIGN.md 7.8)")
+    ap.add_argument("--rules-min-length", type=int, default=None, metavar="N",
+                    help="with --remove-rules: the shortest run of ink that is a rule, 2 to 65535 pixels (default 96)")
+    ap.add_argument("--rules-max-thickness", type=int, default=None, metavar="N",
+                    help="with --remove-rules: the thickest rule, 1 to 64 pixels (default 8); a thicker block is left alone")
+    ap.add_argument("--rules-margin", type=int, default=None, metavar="N",
+                    help="with --remove-rules: rows and columns of a rule's half-tone edge that go with it, 0 to 8 (default 1)")
     ap.add_argument("-o", "--output")
     ap.add_argument("--debug", action="store_true")
     ap.add_argument("--text-map", action="store_true", help="write text-map.png (detect_text_pixels)")
@@ -116,6 +127,8 @@ def main(argv=None):
         ap.error("--normalize-tile and --normalize-polarity are only valid with --normalize")
     if args.deskew_fill is not None and args.deskew is None:
         ap.error("--deskew-fill is only valid with --deskew")
+    if (args.rules_min_length is not None or args.rules_max_thickness is not None or args.rules_margin is not None) and not args.remove_rules:
+        ap.error("--rules-min-length, --rules-max-thickness and --rules-margin are only valid with --remove-rules")
     if args.perspective_fill is not None and args.perspective is None:
         ap.error("--perspective-fill is only valid with --perspective")
     if args.perspective is not None and args.perspective != "auto":
@@ -208,6 +221,21 @@ def main(argv=None):
             skew = 0.0
         else:
             inp, skew_map = upright, m
+    rules_info = None
+    if args.remove_rules:   # from here on the page without its rules is the page; coordinates do not move
+        try:
+            inp, rules_info = engine.remove_rules(inp, min_length=96 if args.rules_min_length is None else args.rules_min_length,
+                                                  max_thickness=8 if args.rules_max_thickness is None else args.rules_max_thickness,
+                                                  margin=1 if args.rules_margin is None else args.rules_margin, info=True)
+        except OcrsError as e:
+            if e.status != 1:   # OCRS_ERR_INVALID_ARGUMENT: a parameter out of range
+                raise
+            ap.error("--remove-rules: %s" % e)
+        if args.debug:
+            print("Rules: %d pixels overwritten with %g (paper bin %d of %d pixels counted): %d of horizontal rules, %d of vertical "
+                  "rules, %d kept where a stroke crosses; %d pixels of ink"
+                  % (rules_info["overwritten"], rules_info["fill"], rules_info["paper_bin"], rules_info["counted"],
+                     rules_info["h_removed"], rules_info["v_removed"], rules_info["kept"], rules_info["ink"]))
     tiled = False if args.tiled is None else True if args.tiled < 0 else args.tiled
     work_hw = None   # the size the detector sees the (turned) page at: DESIGN.md 7.3
     if args.work_scale is not None or args.work_max_side is not None:
@@ -255,7 +283,8 @@ def main(argv=None):
             word_boxes = [[(unproject_rects([r], quad_m)[0], s, n) for r, s, n in boxes] for boxes in word_boxes]
     if args.json:
         content = output.format_json_output(args.image, tuple(shape_hw), texts, confidence=args.confidence, word_boxes=word_boxes,
-                                            orientation=None if turns is None else 90 * turns, normalize=norm_info, skew=skew, outline=outline)
+                                            orientation=None if turns is None else 90 * turns, normalize=norm_info, skew=skew, outline=outline,
+                                            rules=rules_info)
     else:
         content = output.format_text_output(texts)
     if args.output:

@@ -435,6 +435,45 @@ int64_t project_blocks(int dh, int dw);   // blocks an output of this size takes
 // Pages of any mix of sizes and maps in one launch; total_blocks = the sum of project_blocks() over the pages.
 void project_pages(const ProjDesc* d_descs, int n_pages, int total_blocks, hipStream_t s);
 
+// ---- kernels_rules.hip -------------------------------------
+struct RulesInfo {       // what a page's rule removal found: the layout of ocrs_rules_info
+    int32_t paper_bin;   // the bin the fill was taken from; -1: the fill was given
+    float fill;          // what the removed pixels were overwritten with
+    uint64_t ink;        // pixels under the threshold
+    uint64_t counted;    // pixels that are neither ink nor NaN
+    uint64_t h_removed, v_removed;   // |Dh|, |Dv|
+    uint64_t overwritten;            // |D|
+    uint64_t kept;                   // |Kh u Kv|
+};
+// The bit masks of a page, 64 pixels to a word.  Row-major masks: [h, ww] words, bit c of word (y, j) = pixel (y, 64 j + c).
+// Transposed masks: [w, hw] words, bit r of word (x, j) = pixel (64 j + r, x).  Bits past the page's edge are zero.
+enum RulesMask {
+    RM_INK = 0, RM_CH, RM_CV, RM_RV, RM_DV, RM_MV, RM_ROW_MAJOR,                      // row-major
+    RM_INK_T = 0, RM_CV_T, RM_CH_T, RM_RH_T, RM_DH_T, RM_MH_T, RM_TRANSPOSED          // transposed
+};
+constexpr int RULES_COUNTS = 16;
+struct RulesDesc {       // one page whose rules are removed: dst [h, w] from src [h, w]
+    const float* src;
+    float* dst;          // never overlaps src
+    unsigned long long* masks;   // rules_mask_words(h, w) words: RM_ROW_MAJOR masks of h * ww, then RM_TRANSPOSED of w * hw
+    unsigned long long* hist;    // [256] the histogram of the pixels that are neither ink nor NaN; zero when the first launch starts
+    unsigned long long* counts;  // [hw * ww, RULES_COUNTS] what each block counted
+    RulesInfo* info;
+    uint8_t* mask_out;   // [h, w] the mask of include/ocrs_amd.h, or null
+    int32_t h, w;        // each 1 .. 65535
+    int32_t ww, hw;      // ceil(w / 64), ceil(h / 64)
+    int32_t block0;      // first block of this page: the sum of hw * ww of the pages before it
+    int32_t min_length, max_thickness, margin;   // 2 .. 65535, 1 .. 64, 0 .. 8
+    float threshold;
+    float paper;         // NaN: measured
+    int32_t vec;         // w % 4 == 0 and both buffers 16-byte aligned, so 16-byte accesses are safe
+    int32_t pad_;
+};
+int64_t rules_tiles(int h, int w);        // blocks a page of this size takes (host)
+size_t rules_mask_words(int h, int w);    // 64-bit words of RulesDesc::masks (host)
+// Pages of any mix of sizes and parameters, eight launches on `s`; total_blocks = the sum of rules_tiles() over the pages.
+void remove_rules_pages(const RulesDesc* d_descs, int n_pages, int total_blocks, hipStream_t s);
+
 // kernels_peaks.hip
 void measure_peaks(double* mfma_tflops, double* copy_gbps);
 

@@ -15,7 +15,7 @@ def rounded_vertex_coords(rect6):
     return [[_rround(x), _rround(y)] for x, y in rotated_rect_corners(rect6)]
 
 
-def ocr_json(input_path, input_hw, text_lines, confidence=False, word_boxes=None, orientation=None, normalize=None, skew=None, outline=None):
+def ocr_json(input_path, input_hw, text_lines, confidence=False, word_boxes=None, orientation=None, normalize=None, skew=None, outline=None, rules=None):
     """output.rs:34-76.  text_lines: list of TextLine | None.  confidence (no reference counterpart): every line and word
     object also gets "confidence" (TextLine / TextWord.confidence; the lines must come from a scored recognize_text).
     word_boxes (no reference counterpart; indexed like text_lines): per line the detector's word boxes in reading order as
@@ -28,7 +28,9 @@ def ocr_json(input_path, input_hw, text_lines, confidence=False, word_boxes=None
     left alone); the top level then gets "skew" (the boxes given here are already in the frame of the file).
     outline (no reference counterpart): {"found", "corners"} of the sheet the page was straightened to before it was read
     (corners: TL, TR, BR, BL as [x, y] in the frame of the file; found false: the page was read as given); the top level then
-    gets "outline"."""
+    gets "outline".
+    rules (no reference counterpart): what OcrEngine.remove_rules(info=True) found on the page; the top level then gets
+    "rules": {"counted", "fill", "h_removed", "ink", "kept", "overwritten", "paper_bin", "v_removed"}."""
     line_items = []
     for li, line in enumerate(text_lines):
         if line is None:
@@ -54,14 +56,17 @@ def ocr_json(input_path, input_hw, text_lines, confidence=False, word_boxes=None
         doc["skew"] = float(skew)
     if outline is not None:
         doc["outline"] = {"found": bool(outline["found"]), "corners": [[float(x), float(y)] for x, y in outline["corners"]]}
+    if rules is not None:
+        doc["rules"] = {k: int(rules[k]) for k in ("counted", "h_removed", "ink", "kept", "overwritten", "paper_bin", "v_removed")}
+        doc["rules"]["fill"] = float(rules["fill"])
     return doc
 
 
-def format_json_output(input_path, input_hw, text_lines, confidence=False, word_boxes=None, orientation=None, normalize=None, skew=None, outline=None):
+def format_json_output(input_path, input_hw, text_lines, confidence=False, word_boxes=None, orientation=None, normalize=None, skew=None, outline=None, rules=None):
     """output.rs:98-101 (serde_json::to_string_pretty).  serde_json without `preserve_order` keeps `json!` maps in a
     BTreeMap, so the reference emits every object's keys in alphabetical order (ocrs-cli/test-data/
     format-json-expected.json: image_height, image_width, paragraphs, url / text, vertices, words): sort_keys."""
-    return json.dumps(ocr_json(input_path, input_hw, text_lines, confidence, word_boxes, orientation, normalize, skew, outline), indent=2, ensure_ascii=False,
+    return json.dumps(ocr_json(input_path, input_hw, text_lines, confidence, word_boxes, orientation, normalize, skew, outline, rules), indent=2, ensure_ascii=False,
                       sort_keys=True)
 
 
