@@ -750,6 +750,73 @@ OCRS_API ocrs_status ocrs_engine_remove_rules_pages(const ocrs_engine* e, const 
                                                     const ocrs_rules_params* params, ocrs_page** out_pages, uint8_t** out_masks,
                                                     ocrs_rules_info* out_infos);
 
+/* ------------------------------------------------------------------------
+ * Despeckling (no reference counterpart, opt-in).  Faxes, photocopies, dusty flatbeds and thresholded phone
+ * photos carry salt-and-pepper noise: isolated dark specks on the paper become stray punctuation and spurious word boxes,
+ * light pinholes inside strokes break glyphs apart.  What tells a speck from a full stop is the size of its connected
+ * component, optionally with its isolation.  These calls make a new resident page on which the small ink components are
+ * overwritten with the paper's level and (when asked for) the small paper components with the ink's level; every other
+ * pixel keeps its own 32-bit word (NaN payloads and -0.0 included); coordinates do not move, so nothing needs mapping
+ * back.  The source page is untouched; release both with ocrs_page_free in any order.  The page is dark ink on light paper
+ * (ocrs_engine_normalize_page makes it so); despeckle before a deskew warp, whose interpolation smears one-pixel specks
+ * into grey blobs.  What a trained detector or recogniser gains is uncalibrated.
+ *
+ * The definition (tests/despeckle_ref.py restates it and the library equals it bit for bit; integer and set arithmetic,
+ * every set taken from the input page and nothing iterated, so the result does not depend on schedule or batch).  With
+ * A = max_area, Hm = max_hole, K = keep_near:
+ *   ink        v < threshold, an ordinary float compare: NaN is not ink, -inf is.
+ *   components ink is 8-connected; ~ink (NaN included) is 4-connected; the page edge is a wall.
+ *   candidates cand = the pixels of ink components of area <= A; big = ink \ cand.
+ *   isolation  K > 0: a candidate component is kept when one of its pixels lies within Chebyshev distance K of a big pixel
+ *              (i-dots, full stops and diacritics when A is large enough for real dirt); another candidate does not protect
+ *              it.  speck = cand \ kept.  K = 0: nothing is kept.
+ *   holes      hole = the pixels of ~ink components of area <= Hm, those at the page edge too.
+ *   fills      bins as in the normalisation above (g = clamp(v + 0.5f, 0, 1), bin = floor(g * 256f) within 0 .. 255);
+ *              paper_bin = pct(1, 2) of the pixels that are neither ink nor NaN, 255 with nothing counted; paper_fill =
+ *              (paper_bin + 1) / 256 - 0.5.  ink_bin = pct(1, 2) of the ink pixels, 0 with no ink; ink_fill = ink_bin / 256
+ *              - 0.5.  (+0.5 and -0.5 on a normalised page.)  With paper or ink_level given (not NaN) it is the fill and its
+ *              bin reads -1; the counts are still made.
+ *   output     paper_fill on speck, ink_fill on hole, the page's own word elsewhere.
+ *
+ * ocrs_speckle_params_default: threshold 0, max_area 4, max_hole 0, keep_near 0, paper NaN, ink_level NaN.  Hole filling is
+ * off by default: at max_hole 2 a 512 x 512 text page lost 384 pixels of its glyphs' real counters.
+ * ocrs_speckle_params_check (host only): OCRS_ERR_INVALID_ARGUMENT for a threshold that is not finite, a max_area or
+ * max_hole outside 0 .. 4096, a keep_near outside 0 .. 16, an infinite paper or ink_level; the engine calls refuse the same,
+ * and a page with a side over 65535 or with more than 2^31 - 1 pixels.  max_area = max_hole = 0 is valid and makes a copy.
+ * ocrs_engine_despeckle_pages serves n pages of any sizes, each with its own params[i], in eight launches for the whole batch
+ * on one stream; out_pages[n] receives the pages, out_infos[n] (may be NULL) what was found, out_masks[n] (may be NULL) per
+ * page a host uint8 [h][w], to be released with ocrs_buffer_free: bit 0 speck, bit 1 hole, bit 2 kept.
+ * ocrs_engine_despeckle_page: params == NULL means the default. */
+typedef struct ocrs_speckle_params {
+    float threshold;       /* finite; ink is v < threshold */
+    int32_t max_area;      /* A, 0 .. 4096: the largest ink component that is a speck */
+    int32_t max_hole;      /* Hm, 0 .. 4096: the largest paper component that is a pinhole */
+    int32_t keep_near;     /* K, 0 .. 16: a candidate within this distance of big ink is kept; 0: none is */
+    float paper;           /* the specks' fill; NaN: measured on the page */
+    float ink_level;       /* the holes' fill; NaN: measured on the page */
+} ocrs_speckle_params;
+typedef struct ocrs_speckle_info {
+    int32_t paper_bin;     /* the bin paper_fill was taken from; -1: paper was given */
+    int32_t ink_bin;       /* the bin ink_fill was taken from; -1: ink_level was given */
+    float paper_fill;      /* what the specks were overwritten with */
+    float ink_fill;        /* what the holes were overwritten with */
+    uint64_t ink;          /* pixels under the threshold */
+    uint64_t counted;      /* pixels that are neither ink nor NaN */
+    uint64_t specks;       /* ink components removed */
+    uint64_t kept;         /* candidate components kept for being near big ink */
+    uint64_t speck_pixels; /* |speck| */
+    uint64_t kept_pixels;  /* |kept| */
+    uint64_t holes;        /* paper components filled */
+    uint64_t hole_pixels;  /* |hole| */
+} ocrs_speckle_info;
+OCRS_API ocrs_status ocrs_speckle_params_default(ocrs_speckle_params* out);
+OCRS_API ocrs_status ocrs_speckle_params_check(const ocrs_speckle_params* params);
+OCRS_API ocrs_status ocrs_engine_despeckle_page(const ocrs_engine* e, const ocrs_page* page, const ocrs_speckle_params* params,
+                                                ocrs_page** out_page, uint8_t** out_mask, ocrs_speckle_info* out_info);
+OCRS_API ocrs_status ocrs_engine_despeckle_pages(const ocrs_engine* e, const ocrs_page* const* pages, size_t n,
+                                                 const ocrs_speckle_params* params, ocrs_page** out_pages, uint8_t** out_masks,
+                                                 ocrs_speckle_info* out_infos);
+
 /* OcrEngine::detection_threshold (lib.rs:282-287). */
 OCRS_API float ocrs_engine_detection_threshold(const ocrs_engine* e);
 

@@ -16,7 +16,7 @@ from ._lib import OcrsError, check, lib
 
 __all__ = ["OcrEngine", "OcrEngineParams", "ImageSource", "ImageSourceError", "DimOrder", "DecodeMethod", "Model",
            "OcrInput", "TextLine", "TextWord", "TextChar", "OcrsError", "DEFAULT_ALPHABET", "EngineGroup", "line_frame",
-           "Orientation", "orientation_vote", "unrotate_rects", "unrotate_lines", "work_size", "rescale_rects", "normalize_params", "rules_params"]
+           "Orientation", "orientation_vote", "unrotate_rects", "unrotate_lines", "work_size", "rescale_rects", "normalize_params", "rules_params", "speckle_params"]
 
 # lib.rs:34 (with the EUR sign the comment at lib.rs:33 asks for)
 DEFAULT_ALPHABET = " 0123456789!\"#$%&'()*+,-./:;<=>?@[\\]^_`{|}~€ABCDEFGHIJKLMNOPQRSTUVWXYZabcdefghijklmnopqrstuvwxyz"
@@ -511,6 +511,34 @@ def _rules_struct(min_length=None, max_thickness=None, margin=None, threshold=No
     return p
 
 
+def speckle_params(max_area=None, max_hole=None, keep_near=None, threshold=None, paper=None, ink_level=None):
+    """ocrs_speckle_params as a dict: ocrs_speckle_params_default (max_area 4, max_hole 0, keep_near 0,
+    threshold 0, paper and ink_level None = measured) with the given fields replaced, checked by ocrs_speckle_params_check
+    (host only)."""
+    p = _speckle_struct(max_area, max_hole, keep_near, threshold, paper, ink_level)
+    check(lib().ocrs_speckle_params_check(C.byref(p)))
+    return {"max_area": int(p.max_area), "max_hole": int(p.max_hole), "keep_near": int(p.keep_near), "threshold": float(p.threshold),
+            "paper": None if p.paper != p.paper else float(p.paper), "ink_level": None if p.ink_level != p.ink_level else float(p.ink_level)}
+
+
+def _speckle_struct(max_area=None, max_hole=None, keep_near=None, threshold=None, paper=None, ink_level=None):
+    p = _lib.SpeckleParams()
+    check(lib().ocrs_speckle_params_default(C.byref(p)))
+    if max_area is not None:
+        p.max_area = int(max_area)
+    if max_hole is not None:
+        p.max_hole = int(max_hole)
+    if keep_near is not None:
+        p.keep_near = int(keep_near)
+    if threshold is not None:
+        p.threshold = float(threshold)
+    if paper is not None:
+        p.paper = float(paper)
+    if ink_level is not None:
+        p.ink_level = float(ink_level)
+    return p
+
+
 class Skew:
     """ocrs_engine_estimate_skew's outputs: angle (degrees; the page's content is turned counter-clockwise
     by it, deskew_map(.., angle) undoes it), scores (best coarse, runner-up coarse, at the angle), work_hw (the size the
@@ -959,6 +987,48 @@ class OcrEngine:
             res.append([infos[i].as_dict() for i in range(n)])
         return tuple(res) if mask or info else made
 
+    # ---- despeckling
+    def despeckle(self, inp, max_area=4, max_hole=0, keep_near=0, threshold=0.0, paper=None, ink_level=None, mask=False, info=False):
+        """ocrs_engine_despeckle_page: the page with its isolated specks overwritten by the paper's level and its pinholes by
+        the ink's, as a new resident page of the same size; every other pixel keeps its bits.  The page is dark ink on light
+        paper (normalize makes it so).  A speck: an 8-connected component of ink (< threshold) of at most max_area pixels;
+        keep_near > 0: one with a pixel within that Chebyshev distance of larger ink is kept (i-dots, full stops).  A hole: a
+        4-connected component of everything else of at most max_hole pixels (0, the default: none is filled).  paper,
+        ink_level: the fills, None = the page's median paper and ink levels.  mask=True: also the uint8 [H, W] mask (bit 0
+        speck, 1 hole, 2 kept); info=True: also {"paper_bin", "ink_bin", "paper_fill", "ink_fill", "ink", "counted", "specks",
+        "kept", "speck_pixels", "kept_pixels", "holes", "hole_pixels"}.  -> page, or (page[, mask][, info])."""
+        out = self.despeckle_batch([inp], [{"max_area": max_area, "max_hole": max_hole, "keep_near": keep_near, "threshold": threshold,
+                                            "paper": paper, "ink_level": ink_level}], mask=mask, info=info)
+        return tuple(o[0] for o in out) if mask or info else out[0]
+
+    def despeckle_batch(self, inputs, params=None, mask=False, info=False):
+        """ocrs_engine_despeckle_pages: pages of any sizes, each with its own parameters (a dict of despeckle's keywords, or
+        None for the default; one for all, or one per page), all passes for the whole batch on one stream.  -> pages, or
+        (pages[, masks][, infos])."""
+        n = len(inputs)
+        if params is None or isinstance(params, dict):
+            params = [params] * n
+        if len(params) != n:
+            raise ValueError("despeckle_batch: one parameter set per page")
+        pages = _page_array(inputs)
+        ps = (_lib.SpeckleParams * n)(*[_speckle_struct(**(p or {})) for p in params])
+        out = (C.c_void_p * n)()
+        masks = (C.POINTER(C.c_uint8) * n)()
+        infos = (_lib.SpeckleInfo * n)()
+        check(lib().ocrs_engine_despeckle_pages(self._h, pages, C.c_size_t(n), ps, out, masks if mask else None, infos if info else None))
+        made = _new_inputs(out, n)
+        res = [made]
+        if mask:
+            got = []
+            for i in range(n):
+                h, w = made[i].shape[-2:]
+                got.append(np.ctypeslib.as_array(masks[i], shape=(h * w,)).reshape(h, w).copy())
+                lib().ocrs_buffer_free(masks[i])
+            res.append(got)
+        if info:
+            res.append([infos[i].as_dict() for i in range(n)])
+        return tuple(res) if mask or info else made
+
     # ---- page deskew (DESIGN.md §7.6)
     def skew_scores(self, inputs, sc_table):
         """ocrs_engine_skew_scores: the skew profile scores of pages of any sizes (a side at most 4096) at the angles of
@@ -1372,7 +1442,7 @@ class OcrEngine:
 
     # ---- lib.rs:290-300
     def get_text(self, inp, rectify=False, orientation=None, work_size=None, normalize=None, deskew=None, deskew_fill=0.5,
-                 perspective=None, perspective_fill=0.5, rules=None):
+                 perspective=None, perspective_fill=0.5, rules=None, despeckle=None):
         """rectify=True: the same sequence (detect_words, find_text_lines, recognize_text) with rectified crops.
         orientation: None reads the page as given; an int turns it by that many quarter turns counter-clockwise first
         (rotate); "auto" by what detect_orientation finds.
@@ -1388,12 +1458,18 @@ class OcrEngine:
         away before normalisation looks at the paper.
         rules: None reads the page as given; True or a dict of remove_rules()'s keywords reads the page with its ruled lines
         removed.  Applied after perspective, normalisation, the turn and deskew, because rules must be
-        axis-aligned, and before detection.  get_text returns text alone; callers that want boxes run the steps
+        axis-aligned, and before detection.
+        despeckle: None reads the page as given; True or a dict of despeckle()'s keywords reads the page with its specks
+        removed.  Applied after perspective and normalisation (it needs dark ink on light paper) and before
+        the turn, deskew, whose interpolation would smear one-pixel specks into grey blobs, and rule removal.  Coordinates do
+        not move.  get_text returns text alone; callers that want boxes run the steps
         themselves and bring them back last with unproject_rects / unproject_lines."""
         if perspective is not None:
             inp = self.straighten(inp, None if isinstance(perspective, str) and perspective == "auto" else perspective, fill=perspective_fill)[0]
         if normalize is not None and normalize is not False:
             inp = self.normalize(inp, **({} if normalize is True else dict(normalize)))
+        if despeckle is not None and despeckle is not False:
+            inp = self.despeckle(inp, **({} if despeckle is True else dict(despeckle)))
         if orientation is not None:
             k = self.detect_orientation(inp).quarter_turns if orientation == "auto" else int(orientation)
             inp = self.rotate(inp, k)

@@ -91,6 +91,7 @@ DECLARED_SYMBOLS = [
     "ocrs_outline_params_default", "ocrs_outline_params_check", "ocrs_engine_edge_peaks", "ocrs_outline_choose", "ocrs_engine_find_outline",
     "ocrs_quad_map", "ocrs_engine_project_page", "ocrs_engine_project_pages", "ocrs_unproject_rects", "ocrs_unproject_chars",
     "ocrs_rules_params_default", "ocrs_rules_params_check", "ocrs_engine_remove_rules_page", "ocrs_engine_remove_rules_pages",
+    "ocrs_speckle_params_default", "ocrs_speckle_params_check", "ocrs_engine_despeckle_page", "ocrs_engine_despeckle_pages",
 ]
 
 ABI_VERSION = 6   # include/ocrs_amd.h OCRS_ABI_VERSION
@@ -124,6 +125,20 @@ class RulesInfo(C.Structure):   # include/ocrs_amd.h ocrs_rules_info
         return {"paper_bin": int(self.paper_bin), "fill": float(self.fill), "ink": int(self.ink), "counted": int(self.counted),
                 "h_removed": int(self.h_removed), "v_removed": int(self.v_removed), "overwritten": int(self.overwritten),
                 "kept": int(self.kept)}
+
+
+class SpeckleParams(C.Structure):   # include/ocrs_amd.h ocrs_speckle_params
+    _fields_ = [("threshold", C.c_float), ("max_area", C.c_int32), ("max_hole", C.c_int32), ("keep_near", C.c_int32), ("paper", C.c_float),
+                ("ink_level", C.c_float)]
+
+
+class SpeckleInfo(C.Structure):   # include/ocrs_amd.h ocrs_speckle_info
+    _fields_ = [("paper_bin", C.c_int32), ("ink_bin", C.c_int32), ("paper_fill", C.c_float), ("ink_fill", C.c_float), ("ink", C.c_uint64),
+                ("counted", C.c_uint64), ("specks", C.c_uint64), ("kept", C.c_uint64), ("speck_pixels", C.c_uint64),
+                ("kept_pixels", C.c_uint64), ("holes", C.c_uint64), ("hole_pixels", C.c_uint64)]
+
+    def as_dict(self):
+        return {name: (float if name.endswith("_fill") else int)(getattr(self, name)) for name, _ in self._fields_}
 
 
 class SkewParams(C.Structure):   # include/ocrs_amd.h ocrs_skew_params

@@ -109,6 +109,19 @@ def main(argv=None):
                     help="with --remove-rules: the thickest rule, 1 to 64 pixels (default 8); a thicker block is left alone")
     ap.add_argument("--rules-margin", type=int, default=None, metavar="N",
                     help="with --remove-rules: rows and columns of a rule's half-tone edge that go with it, 0 to 8 (default 1)")
+    ap.add_argument("--despeckle", action="store_true",
+                    help="take salt-and-pepper noise out of the page on the GPU before reading it: connected components of ink of "
+                         "at most --speck-max-area pixels are overwritten with the paper's level (after --normalize, before "
+                         "--orientation, --deskew and --remove-rules: it needs dark ink on light paper, and a warp smears specks); "
+                         "the JSON gains \"despeckle\" (no reference counterpart; what a detector gains is uncalibrated: DESIGN.md 7.9)")
+    ap.add_argument("--speck-max-area", type=int, default=None, metavar="N",
+                    help="with --despeckle: the largest component of ink that is a speck, 0 to 4096 pixels (default 4)")
+    ap.add_argument("--speck-fill-holes", type=int, default=None, metavar="N",
+                    help="with --despeckle: also fill the light holes inside ink of at most N pixels, 0 to 4096, with the ink's level "
+                         "(default 0: none; small values already close real counters of small glyphs)")
+    ap.add_argument("--speck-keep-near", type=int, default=None, metavar="N",
+                    help="with --despeckle: keep a speck that lies within N pixels of larger ink, 0 to 16 (default 0: keep none); for "
+                         "i-dots and full stops when --speck-max-area is large")
     ap.add_argument("-o", "--output")
     ap.add_argument("--debug", action="store_true")
     ap.add_argument("--text-map", action="store_true", help="write text-map.png (detect_text_pixels)")
@@ -129,6 +142,8 @@ def main(argv=None):
         ap.error("--deskew-fill is only valid with --deskew")
     if (args.rules_min_length is not None or args.rules_max_thickness is not None or args.rules_margin is not None) and not args.remove_rules:
         ap.error("--rules-min-length, --rules-max-thickness and --rules-margin are only valid with --remove-rules")
+    if (args.speck_max_area is not None or args.speck_fill_holes is not None or args.speck_keep_near is not None) and not args.despeckle:
+        ap.error("--speck-max-area, --speck-fill-holes and --speck-keep-near are only valid with --despeckle")
     if args.perspective_fill is not None and args.perspective is None:
         ap.error("--perspective-fill is only valid with --perspective")
     if args.perspective is not None and args.perspective != "auto":
@@ -196,6 +211,22 @@ def main(argv=None):
             print("Normalize: %s page (vote %d), white bin %d, levels %d .. %d, %d pixels counted"
                   % ("dark" if norm_info["dark"] else "light", norm_info["vote"], norm_info["white"], norm_info["lo"], norm_info["hi"],
                      norm_info["counted"]))
+    speckle_info = None
+    if args.despeckle:   # from here on the page without its specks is the page; coordinates do not move
+        try:
+            inp, speckle_info = engine.despeckle(inp, max_area=4 if args.speck_max_area is None else args.speck_max_area,
+                                                 max_hole=0 if args.speck_fill_holes is None else args.speck_fill_holes,
+                                                 keep_near=0 if args.speck_keep_near is None else args.speck_keep_near, info=True)
+        except OcrsError as e:
+            if e.status != 1:   # OCRS_ERR_INVALID_ARGUMENT: a parameter out of range
+                raise
+            ap.error("--despeckle: %s" % e)
+        if args.debug:
+            print("Despeckle: %d specks (%d pixels) overwritten with %g (paper bin %d of %d pixels counted), %d kept near larger ink "
+                  "(%d pixels), %d holes (%d pixels) filled with %g (ink bin %d); %d pixels of ink"
+                  % (speckle_info["specks"], speckle_info["speck_pixels"], speckle_info["paper_fill"], speckle_info["paper_bin"],
+                     speckle_info["counted"], speckle_info["kept"], speckle_info["kept_pixels"], speckle_info["holes"],
+                     speckle_info["hole_pixels"], speckle_info["ink_fill"], speckle_info["ink_bin"], speckle_info["ink"]))
     turns = None
     if args.orientation is not None:   # from here on the turned page is the page; results are mapped back before output
         if args.orientation == "auto":
@@ -284,7 +315,7 @@ def main(argv=None):
     if args.json:
         content = output.format_json_output(args.image, tuple(shape_hw), texts, confidence=args.confidence, word_boxes=word_boxes,
                                             orientation=None if turns is None else 90 * turns, normalize=norm_info, skew=skew, outline=outline,
-                                            rules=rules_info)
+                                            rules=rules_info, despeckle=speckle_info)
     else:
         content = output.format_text_output(texts)
     if args.output:

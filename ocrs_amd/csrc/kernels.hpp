@@ -474,6 +474,44 @@ size_t rules_mask_words(int h, int w);    // 64-bit words of RulesDesc::masks (h
 // Pages of any mix of sizes and parameters, eight launches on `s`; total_blocks = the sum of rules_tiles() over the pages.
 void remove_rules_pages(const RulesDesc* d_descs, int n_pages, int total_blocks, hipStream_t s);
 
+// ---- kernels_speckle.hip -----------------------------------
+struct SpeckleInfo {     // what a page's despeckling found: the layout of ocrs_speckle_info
+    int32_t paper_bin;   // the bin the specks' fill was taken from; -1: the fill was given
+    int32_t ink_bin;     // the bin the holes' fill was taken from; -1: the fill was given
+    float paper_fill;    // what the specks were overwritten with
+    float ink_fill;      // what the holes were overwritten with
+    uint64_t ink;        // pixels under the threshold
+    uint64_t counted;    // pixels that are neither ink nor NaN
+    uint64_t specks, kept;               // components removed; candidates kept for being near big ink
+    uint64_t speck_pixels, kept_pixels;  // their pixels
+    uint64_t holes, hole_pixels;         // paper components filled, and their pixels
+};
+constexpr int SPECKLE_COUNTS = 32;   // 64-bit words of a block's record: [wave][8]
+constexpr int SPECKLE_MAX_AREA = 4096, SPECKLE_MAX_NEAR = 16;
+struct SpeckleDesc {     // one page that is despeckled: dst [h, w] from src [h, w]
+    const float* src;
+    float* dst;          // never overlaps src
+    unsigned long long* masks;   // 3 row-major bit masks of h * ww words (64 pixels a word, bits past the edge zero): ink, big, near
+    int32_t* labels;     // [h * w] the union-find forest over page-local pixel indices, both classes
+    uint32_t* area;      // [h * w] at a root: the pixels of its component
+    uint8_t* near_flag;  // [h * w] at a root: 1 when a pixel of this candidate component lies within keep_near of big ink
+    unsigned long long* hist;    // [2][256] paper pixels (neither ink nor NaN), ink pixels; zero when the first launch starts
+    unsigned long long* counts;  // [hw * ww, SPECKLE_COUNTS] what each block counted
+    SpeckleInfo* info;
+    uint8_t* mask_out;   // [h, w] the mask of include/ocrs_amd.h, or null
+    int32_t h, w;        // each 1 .. 65535, h * w < 2^31
+    int32_t ww, hw;      // ceil(w / 64), ceil(h / 64)
+    int32_t block0;      // first block of this page: the sum of hw * ww of the pages before it
+    int32_t max_area, max_hole, keep_near;   // 0 .. 4096, 0 .. 4096, 0 .. 16
+    float threshold;
+    float paper, ink_level;   // NaN: measured
+    int32_t vec;         // w % 4 == 0 and both buffers 16-byte aligned, so 16-byte accesses are safe
+};
+int64_t speckle_tiles(int h, int w);        // blocks a page of this size takes (host)
+size_t speckle_mask_words(int h, int w);    // 64-bit words of SpeckleDesc::masks (host)
+// Pages of any mix of sizes and parameters, eight launches on `s`; total_blocks = the sum of speckle_tiles() over the pages.
+void despeckle_pages(const SpeckleDesc* d_descs, int n_pages, int total_blocks, hipStream_t s);
+
 // kernels_peaks.hip
 void measure_peaks(double* mfma_tflops, double* copy_gbps);
 
