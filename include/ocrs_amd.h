@@ -88,6 +88,20 @@ OCRS_API ocrs_status ocrs_ctc_beam_search(const float* logp, int t, int c, uint3
 OCRS_API ocrs_status ocrs_ctc_beam_search_scored(const float* logp, int t, int c, uint32_t width, int impl, uint32_t** labels,
                                                  uint32_t** positions, size_t* n, double* score, float** step_logp);
 
+/* Test hook: the decode stage of a packed recognition batch (everything after the head GEMM) on chosen head outputs.
+ * `logits`: the n lines' head outputs [lengths[i]][c], line after line, lines in the caller's order (a length may be 0);
+ * `excluded`: [c] flags by label, or NULL.  method: 0 greedy, 1 greedy scored, 2 beam search (the HIP kernel, `width`
+ * beams), 3 beam search scored.  The lines are sorted and packed as a request's are (longest first, row t of line slot m at
+ * packed row off[t] + m), run through the LogSoftmax + arg-max kernel and then through the same function the engine's
+ * requests end in.  Outputs, per line in the caller's order: the steps of line i are labels / positions
+ * [step_offsets[i], step_offsets[i + 1]) (step_offsets: n + 1 entries, the caller's; labels / positions malloc'ed);
+ * scored methods (step_logp and scores required, else ignored): *step_logp indexed like the steps (malloc'ed), scores[i]
+ * the line score (0 for a line of length 0); logp (optional): *logp = the lines' unmasked log-probs [lengths[i]][c], line
+ * after line (malloc'ed).  OCRS_ERR_CAPACITY: beam search with a (c, width) the kernel does not support. */
+OCRS_API ocrs_status ocrs_ctc_decode_packed(const float* logits, const int32_t* lengths, size_t n, int c, const uint8_t* excluded,
+                                            int method, uint32_t width, uint32_t** labels, uint32_t** positions,
+                                            size_t* step_offsets, float** step_logp, double* scores, float** logp);
+
 /* Test hook (host only, no GPU work): how the persistent GRU kernel would deal the 16-line row tiles of a request
  * to its waves.  lengths_desc = sequence lengths of the lines, descending (tile k = lines 16k .. 16k+15).
  * *n_clusters = clusters per direction, *waves = 4 = wave slots per cluster; tiles[4s .. 4s+3] for slot

@@ -73,7 +73,7 @@ DECLARED_SYMBOLS = [
     "ocrs_group_member_stats", "ocrs_numa_parse_cpulist", "ocrs_numa_bind_selftest", "ocrs_engine_recognize_logits", "ocrs_engine_set_option", "ocrs_engine_get_option", "ocrs_option_name", "ocrs_device_pool_stats", "ocrs_device_pool_configure", "ocrs_device_pool_trim",
     "ocrs_device_set_isolation", "ocrs_device_isolation", "ocrs_group_set_replay", "ocrs_abi_version",
     "ocrs_engine_recognize_text_scored", "ocrs_engine_recognize_text_batch_scored", "ocrs_ctc_beam_search_scored",
-    "ocrs_engine_run_recognition_ops",
+    "ocrs_engine_run_recognition_ops", "ocrs_ctc_decode_packed",
     "ocrs_engine_detect_words_scored", "ocrs_engine_detect_words_batch_scored", "ocrs_group_detect_words_batch_scored",
     "ocrs_engine_find_text_lines_indexed", "ocrs_engine_find_text_lines_batch_indexed",
     "ocrs_detection_tile_plan", "ocrs_engine_detect_words_tiled", "ocrs_engine_detect_words_batch_tiled",
@@ -286,6 +286,56 @@ def ctc_beam_search_scored(logp, width, impl=0):
     for p in (lab, pos, slp):
         lib().ocrs_buffer_free(p)
     return out, score.value, lp
+
+
+DECODE_METHODS = {"greedy": 0, "greedy_scored": 1, "beam": 2, "beam_scored": 3}   # include/ocrs_amd.h ocrs_ctc_decode_packed
+
+
+def ctc_decode_packed(mats, excluded=None, method="greedy", width=1, want_logp=True):
+    """ocrs_ctc_decode_packed on a list of head outputs [T_i, C] float32 (T_i may be 0) as one packed batch -> per line, in
+    the caller's order, a dict: steps [(label, pos)], logp (the unmasked log-probs [T_i, C]; None unless want_logp) and,
+    with a scored method, step_logp (float32) and score (float64).  excluded: labels to mask, or None."""
+    import numpy as np
+    mats = [np.ascontiguousarray(m, np.float32) for m in mats]
+    n = len(mats)
+    c = int(mats[0].shape[1]) if n else 1
+    assert all(m.ndim == 2 and m.shape[1] == c for m in mats)
+    lengths = np.array([m.shape[0] for m in mats], np.int32)
+    flat = np.concatenate([m.reshape(-1) for m in mats]) if n else np.zeros(0, np.float32)
+    flat = np.ascontiguousarray(flat if flat.size else np.zeros(1, np.float32), np.float32)
+    excl = None
+    if excluded is not None:
+        flags = np.zeros(c, np.uint8)
+        flags[list(excluded)] = 1
+        excl = flags.ctypes.data_as(C.POINTER(C.c_uint8))
+    m = DECODE_METHODS[method] if isinstance(method, str) else int(method)
+    scored = m in (1, 3)
+    lab, pos, slp, lp = C.POINTER(C.c_uint32)(), C.POINTER(C.c_uint32)(), C.POINTER(C.c_float)(), C.POINTER(C.c_float)()
+    offs = (C.c_size_t * (n + 1))()
+    scores = (C.c_double * max(n, 1))()
+    check(lib().ocrs_ctc_decode_packed(flat.ctypes.data_as(C.POINTER(C.c_float)), lengths.ctypes.data_as(C.POINTER(C.c_int32)),
+                                       C.c_size_t(n), c, excl, m, C.c_uint32(width), C.byref(lab), C.byref(pos), offs,
+                                       C.byref(slp) if scored else None, scores if scored else None,
+                                       C.byref(lp) if want_logp else None))
+    total = int(offs[n])
+    labels = np.ctypeslib.as_array(lab, shape=(max(total, 1),))[:total].copy()
+    positions = np.ctypeslib.as_array(pos, shape=(max(total, 1),))[:total].copy()
+    step_lp = np.ctypeslib.as_array(slp, shape=(max(total, 1),))[:total].copy() if scored else None
+    rows = int(lengths.sum())
+    logp = np.ctypeslib.as_array(lp, shape=(max(rows * c, 1),))[:rows * c].copy() if want_logp else None
+    for p in (lab, pos) + ((slp,) if scored else ()) + ((lp,) if want_logp else ()):
+        lib().ocrs_buffer_free(p)
+    out, row = [], 0
+    for i in range(n):
+        a, b, t = int(offs[i]), int(offs[i + 1]), int(lengths[i])
+        r = {"steps": [(int(labels[q]), int(positions[q])) for q in range(a, b)],
+             "logp": logp[row * c:(row + t) * c].reshape(t, c) if want_logp else None}
+        if scored:
+            r["step_logp"] = step_lp[a:b]
+            r["score"] = float(scores[i])
+        out.append(r)
+        row += t
+    return out
 
 
 def require_gpu():

@@ -190,6 +190,42 @@ ocrs_status ocrs_ctc_beam_search_scored(const float* logp, int t, int c, uint32_
     });
 }
 
+ocrs_status ocrs_ctc_decode_packed(const float* logits, const int32_t* lengths, size_t n, int c, const uint8_t* excluded, int method,
+                                   uint32_t width, uint32_t** labels, uint32_t** positions, size_t* step_offsets, float** step_logp,
+                                   double* scores, float** logp) {
+    return guarded([&] {
+        const bool scored = method == 1 || method == 3;
+        if (!lengths || !labels || !positions || !step_offsets || c < 1 || method < 0 || method > 3 ||
+            (scored && (!step_logp || !scores)))
+            fail(OCRS_ERR_INVALID_ARGUMENT, "bad argument");
+        size_t rows = 0;
+        for (size_t i = 0; i < n; i++) {
+            if (lengths[i] < 0) fail(OCRS_ERR_INVALID_ARGUMENT, "line %zu: length %d", i, (int)lengths[i]);
+            rows += (size_t)lengths[i];
+        }
+        if (rows > 0 && !logits) fail(OCRS_ERR_INVALID_ARGUMENT, "bad argument");
+        if (rows * (size_t)c > (size_t)1 << 30) fail(OCRS_ERR_INVALID_ARGUMENT, "batch too large");
+        std::vector<RecResult> res;
+        ctc_decode_packed(logits, lengths, n, c, excluded, method, width, logp != nullptr, &res);
+        std::vector<uint32_t> l, p;
+        std::vector<float> slp, lp;
+        for (size_t i = 0; i < n; i++) {
+            step_offsets[i] = l.size();
+            for (const CtcStep& st : res[i].steps) { l.push_back(st.label); p.push_back(st.pos); }
+            if (scored) {
+                slp.insert(slp.end(), res[i].step_logp.begin(), res[i].step_logp.end());
+                scores[i] = res[i].line_score;
+            }
+            lp.insert(lp.end(), res[i].logp.begin(), res[i].logp.end());
+        }
+        step_offsets[n] = l.size();
+        *labels = dup_buffer(l);
+        *positions = dup_buffer(p);
+        if (scored) *step_logp = dup_buffer(slp);
+        if (logp) *logp = dup_buffer(lp);
+    });
+}
+
 uint32_t ocrs_abi_version(void) { return OCRS_ABI_VERSION; }
 
 static void check_option_set(int r, const char* name, long value) {   // what set_option (common.hpp) returned

@@ -19,6 +19,8 @@
 //     insertion order is a closed-form key: (beam index, label) for an extension, (own index, 0) for a
 //     stay — unless the parent p comes earlier in the beam order, then the parent's extension inserted
 //     the entry first, at (p, label), and the entry carries the positions of that insertion.
+//     "Belongs to a current beam" is a question about label sequences: every sequence has ONE node for the whole
+//     search (node_of), also when it falls out of the beams and is reached again while a beam that extends it stayed.
 //     Selection is nth_element + sort on (score desc, key asc).  ~100x faster, identical output
 //     (tests/test_host_cpu.py compares the two on random matrices for widths 1..100).
 #include <algorithm>
@@ -128,6 +130,9 @@ std::vector<CtcStep> ctc_beam_search(const float* logp, int T, int C, int row_st
     std::vector<PosNode> pos_nodes(1, PosNode{-1, 0});
     std::vector<FBeam> beams{FBeam{0, 0, 0.0, NEG}}, next;
     std::vector<int> node2beam(1, -1);      // node id -> index among the current beams
+    // (parent node, label) -> node: one node per label sequence for the whole search.  A prefix that fell out of the beams
+    // and is reached again gets the node it had, so a surviving beam that extends it still finds it as its parent.
+    std::unordered_map<uint64_t, int> node_of;
     std::vector<double> row(C), total, stay_pb, stay_pnb;
     std::vector<int> pidx, stay_key;
     std::vector<uint8_t> is_beam_child;      // [beam][label]: that extension is one of the current beams
@@ -192,10 +197,13 @@ std::vector<CtcStep> ctc_beam_search(const float* logp, int T, int C, int row_st
                 next.push_back(FBeam{beams[j].node, (int)pos_nodes.size() - 1, stay_pb[j], stay_pnb[j]});
             } else {        // a new prefix
                 const int last = beams[i].node == 0 ? -1 : nodes[beams[i].node].label;
-                nodes.push_back(Node{beams[i].node, c});
-                node2beam.push_back(-1);
+                const auto ins = node_of.emplace(((uint64_t)(uint32_t)beams[i].node << 32) | (uint32_t)c, (int)nodes.size());
+                if (ins.second) {
+                    nodes.push_back(Node{beams[i].node, c});
+                    node2beam.push_back(-1);
+                }
                 pos_nodes.push_back(PosNode{beams[i].pos, (uint32_t)t});
-                next.push_back(FBeam{(int)nodes.size() - 1, (int)pos_nodes.size() - 1, NEG,
+                next.push_back(FBeam{ins.first->second, (int)pos_nodes.size() - 1, NEG,
                                      (c == last ? beams[i].pb : total[i]) + row[c]});
             }
         }

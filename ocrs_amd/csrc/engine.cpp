@@ -1124,13 +1124,15 @@ void recognize_callback(const ocrs_engine& e, Workspace& ws, const std::vector<C
 // padded width (hence sequence length) the reference gives it (recognition.rs:437), lines are
 // sorted by length so that step t of the recurrence works on a dense prefix of rows.
 struct Slot { int T; size_t line; };
-struct Sub {   // one ragged batch of a request: what its launches leave for the host
-    std::vector<Slot> slots;
+struct PackedDecode {   // what the decode stage of one ragged batch leaves for the host
     DecodedSteps dec;              // greedy, or beam search done on the GPU
-    uint32_t gru_status[8] = {0};  // time-out words of the persistent GRU kernels (0 = fine)
     bool gpu_beam = false;         // beam search already done on the GPU: dec holds its steps
     std::vector<float> logp;       // beam search on the host / logits wanted: packed [R][C]
     std::vector<int32_t> off;      // with logp
+};
+struct Sub : PackedDecode {   // one ragged batch of a request: what its launches leave for the host
+    std::vector<Slot> slots;
+    uint32_t gru_status[8] = {0};  // time-out words of the persistent GRU kernels (0 = fine)
 };
 struct PackedRequest {   // what the sub-batches of one request share
     const ocrs_engine& e;
@@ -1142,6 +1144,48 @@ struct PackedRequest {   // what the sub-batches of one request share
     RecResult* res;
 };
 
+// The decode stage of a packed batch, after the head: the labels / log-probs / row maxima log_softmax_argmax left on the
+// device (d_logp: beam search or want_logp; d_maxlp: scored greedy) become the steps of the M lines — the CTC launch on
+// `w`'s stream and the queued downloads of what the host needs.  The engine's launch_packed and the test hook
+// ctc_decode_packed both end in it.
+void decode_packed(Workspace& w, const HipModel::PackedPlan& plan, int C, bool beam, uint32_t beam_width, bool scored,
+                   bool want_logp, const uint8_t* d_excl, const int32_t* d_labels, const float* d_logp, const float* d_maxlp,
+                   StageTimers* T, PackedDecode& sub) {
+    hipStream_t sst = w.s();
+    const int M = plan.M, Tmax = plan.Tmax;
+    sub.gpu_beam = beam && option(OPT_BEAM_GPU) && k::ctc_beam_supported(C, (int)beam_width);
+    if (want_logp || (beam && !sub.gpu_beam)) {   // the host needs the log-probs: the caller, or its beam search
+        sub.logp.resize((size_t)plan.R * C);
+        sub.off = plan.h_off;
+        w.download(sub.logp.data(), d_logp, sub.logp.size() * sizeof(float), sst);
+    }
+    if (beam && !sub.gpu_beam) return;
+    // where the steps land: [M][Tmax] labels and positions, [M] counts; scored: step log-probs and line scores as well
+    int2* d_nodes = nullptr;
+    int2* d_posn = nullptr;
+    if (sub.gpu_beam) {
+        const size_t arena = k::ctc_beam_arena_entries(Tmax, (int)beam_width);
+        d_nodes = w.alloc_n<int2>((size_t)M * arena);
+        d_posn = w.alloc_n<int2>((size_t)M * arena);
+    }
+    uint32_t* d_ol = w.alloc_n<uint32_t>((size_t)M * Tmax);
+    uint32_t* d_op = w.alloc_n<uint32_t>((size_t)M * Tmax);
+    int32_t* d_cnt = w.alloc_n<int32_t>(M);
+    float* d_slp = scored ? w.alloc_n<float>((size_t)M * Tmax) : nullptr;
+    double* d_score = scored ? w.alloc_n<double>(M) : nullptr;
+    {
+        StageScope sc(T, ST_CTC, sst);
+        if (sub.gpu_beam)   // rten decode_beam (recognition.rs:512-514) on the GPU, one workgroup per line (kernels_beam.hip)
+            k::ctc_beam_packed(d_logp, plan.d_Tm, plan.d_off, M, Tmax, C, (int)beam_width, d_excl, d_nodes, d_posn, d_ol, d_op, d_cnt,
+                               sst, d_score, d_slp);
+        else if (scored)   // greedy CTC with each step's log-prob and the greedy path's score, in one pass
+            k::ctc_collapse_scored_packed(d_labels, d_maxlp, plan.d_Tm, plan.d_off, M, Tmax, d_ol, d_op, d_slp, d_cnt, d_score, sst);
+        else   // greedy CTC (recognition.rs:511)
+            k::ctc_collapse_packed(d_labels, plan.d_Tm, plan.d_off, M, Tmax, d_ol, d_op, d_cnt, sst);
+    }
+    download_steps(w, sst, (size_t)M, Tmax, d_ol, d_op, d_cnt, d_slp, d_score, &sub.dec);
+}
+
 // launches chunks [c0, c1) as one ragged batch on `w` and queues the downloads of what unpack_packed needs
 void launch_packed(const PackedRequest& rq, size_t c0, size_t c1, Workspace& w, Sub& sub) {
     const ocrs_engine& e = rq.e;
@@ -1149,7 +1193,6 @@ void launch_packed(const PackedRequest& rq, size_t c0, size_t c1, Workspace& w, 
     const uint8_t* d_excl = e.has_excluded ? e.d_excluded.as<uint8_t>() : nullptr;
     StageTimers* T = e.tm();
     const int C = rq.C;
-    hipStream_t sst = w.s();
     std::vector<int32_t> lineT;                      // the lines of chunks c0 .. c1 in chunk order
     std::vector<size_t> line_of;                     // and which line of the request each is
     std::vector<size_t> pos_at(c1 - c0);             // index of each chunk's first line
@@ -1166,7 +1209,6 @@ void launch_packed(const PackedRequest& rq, size_t c0, size_t c1, Workspace& w, 
     const int32_t* d_pos = HipModel::make_packed_plan(w, lineT, &plan, &order);
     if (!d_pos) return;
     for (size_t i : order) sub.slots.push_back(Slot{lineT[i], line_of[i]});
-    const int M = plan.M, Tmax = plan.Tmax;
     std::vector<HipModel::PackedGroup> pg;
     for (size_t c = c0; c < c1; c++)
         if (rq.chunk_T[c] > 0)
@@ -1177,37 +1219,7 @@ void launch_packed(const PackedRequest& rq, size_t c0, size_t c1, Workspace& w, 
     float* d_maxlp = (rq.scored && !beam) ? w.alloc_n<float>((size_t)plan.R) : nullptr;
     rq.hm->run_recognition_packed(w, pg, plan, (int)e.rec_input_height(), T, d_excl, d_labels, (beam || rq.want_logp) ? &d_logp : nullptr,
                                   d_maxlp);
-    sub.gpu_beam = beam && option(OPT_BEAM_GPU) && k::ctc_beam_supported(C, (int)e.beam_width);
-    if (rq.want_logp || (beam && !sub.gpu_beam)) {   // the host needs the log-probs: the caller, or its beam search
-        sub.logp.resize((size_t)plan.R * C);
-        sub.off = plan.h_off;
-        w.download(sub.logp.data(), d_logp, sub.logp.size() * sizeof(float), sst);
-    }
-    if (beam && !sub.gpu_beam) return;
-    // where the steps land: [M][Tmax] labels and positions, [M] counts; scored: step log-probs and line scores as well
-    int2* d_nodes = nullptr;
-    int2* d_posn = nullptr;
-    if (sub.gpu_beam) {
-        const size_t arena = k::ctc_beam_arena_entries(Tmax, (int)e.beam_width);
-        d_nodes = w.alloc_n<int2>((size_t)M * arena);
-        d_posn = w.alloc_n<int2>((size_t)M * arena);
-    }
-    uint32_t* d_ol = w.alloc_n<uint32_t>((size_t)M * Tmax);
-    uint32_t* d_op = w.alloc_n<uint32_t>((size_t)M * Tmax);
-    int32_t* d_cnt = w.alloc_n<int32_t>(M);
-    float* d_slp = rq.scored ? w.alloc_n<float>((size_t)M * Tmax) : nullptr;
-    double* d_score = rq.scored ? w.alloc_n<double>(M) : nullptr;
-    {
-        StageScope sc(T, ST_CTC, sst);
-        if (sub.gpu_beam)   // rten decode_beam (recognition.rs:512-514) on the GPU, one workgroup per line (kernels_beam.hip)
-            k::ctc_beam_packed(d_logp, plan.d_Tm, plan.d_off, M, Tmax, C, (int)e.beam_width, d_excl, d_nodes, d_posn, d_ol, d_op, d_cnt,
-                               sst, d_score, d_slp);
-        else if (rq.scored)   // greedy CTC with each step's log-prob and the greedy path's score, in one pass
-            k::ctc_collapse_scored_packed(d_labels, d_maxlp, plan.d_Tm, plan.d_off, M, Tmax, d_ol, d_op, d_slp, d_cnt, d_score, sst);
-        else   // greedy CTC (recognition.rs:511)
-            k::ctc_collapse_packed(d_labels, plan.d_Tm, plan.d_off, M, Tmax, d_ol, d_op, d_cnt, sst);
-    }
-    download_steps(w, sst, (size_t)M, Tmax, d_ol, d_op, d_cnt, d_slp, d_score, &sub.dec);
+    decode_packed(w, plan, C, beam, e.beam_width, rq.scored, rq.want_logp, d_excl, d_labels, d_logp, d_maxlp, T, sub);
 }
 
 // after the sync: the request's results from what launch_packed downloaded
@@ -1309,6 +1321,52 @@ void recognize_packed(const ocrs_engine& e, Workspace& ws, const std::vector<Chu
 }
 
 }  // namespace
+
+void ocrs::ctc_decode_packed(const float* logits, const int32_t* T, size_t n, int C, const uint8_t* excluded, int method,
+                             uint32_t width, bool want_logp, std::vector<RecResult>* res) {
+    const bool beam = method >= 2, scored = (method & 1) != 0;
+    if (beam && !k::ctc_beam_supported(C, (int)width))
+        fail(OCRS_ERR_CAPACITY, "beam search on the GPU supports up to 128 classes and width 128");
+    res->assign(n, RecResult{});
+    DeviceScope bind(-1);
+    Workspace w;
+    const std::vector<int32_t> lineT(T, T + n);
+    HipModel::PackedPlan plan;
+    std::vector<size_t> order;
+    if (!HipModel::make_packed_plan(w, lineT, &plan, &order)) return;   // no line has a row
+    const int M = plan.M;
+    std::vector<size_t> at(n + 1, 0);   // offset of each line's rows in `logits`
+    for (size_t i = 0; i < n; i++) at[i + 1] = at[i] + (size_t)lineT[i] * C;
+    std::vector<float> packed((size_t)plan.R * C);   // line order[m]'s row t at packed row off[t] + m
+    for (int m = 0; m < M; m++)
+        for (int t = 0; t < plan.h_Tm[m]; t++)
+            std::copy_n(logits + at[order[m]] + (size_t)t * C, C, &packed[((size_t)plan.h_off[t] + m) * C]);
+    float* d_logits = w.alloc_n<float>(packed.size());
+    w.upload(d_logits, packed.data(), packed.size() * sizeof(float));
+    uint8_t* d_excl = nullptr;
+    if (excluded) {
+        d_excl = w.alloc_n<uint8_t>(C);
+        w.upload(d_excl, excluded, C);
+    }
+    // what run_recognition_packed's LOGSOFTMAX step and launch_packed do after the head GEMM
+    int32_t* d_labels = w.alloc_n<int32_t>((size_t)plan.R);
+    float* d_logp = (beam || want_logp) ? w.alloc_n<float>((size_t)plan.R * C) : nullptr;
+    float* d_maxlp = (scored && !beam) ? w.alloc_n<float>((size_t)plan.R) : nullptr;
+    if (!k::log_softmax_argmax(d_logits, plan.R, C, d_excl, d_logp, d_labels, w.s(), d_maxlp))
+        fail(OCRS_ERR_CAPACITY, "LogSoftmax over %d classes exceeds the kernel's LDS staging (max ~630)", C);
+    PackedDecode out;
+    decode_packed(w, plan, C, beam, width, scored, want_logp, d_excl, d_labels, d_logp, d_maxlp, nullptr, out);
+    w.sync();
+    OCRS_HIP(hipGetLastError());
+    if (beam && !out.gpu_beam) fail(OCRS_ERR_RUN_FAILED, "option beam_gpu is off: the beam kernel did not run");
+    for (int m = 0; m < M; m++) {
+        RecResult& r = (*res)[order[m]];
+        const int Tm = plan.h_Tm[m];
+        if (want_logp) r.logp.resize((size_t)Tm * C);
+        for (int t = 0; t < Tm && want_logp; t++) std::copy_n(&out.logp[((size_t)out.off[t] + m) * C], C, &r.logp[(size_t)t * C]);
+        take_steps(out.dec, (size_t)m, (uint32_t)Tm, &r);
+    }
+}
 
 void ocrs_engine::recognize_lines(const ocrs_page* const* pages, size_t n_pages, RecResult* res, size_t L, bool scored,
                                   bool want_logp) const {

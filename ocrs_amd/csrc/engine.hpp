@@ -82,6 +82,14 @@ struct RecResult {
     std::vector<float> logp;
 };
 
+// Test hook (ocrs_ctc_decode_packed): the decode stage of a packed recognition batch on chosen head outputs.  `logits`: the
+// n lines' rows [T[i]][C], line after line; `excluded`: [C] flags or null; method 0 greedy, 1 greedy scored, 2 beam search
+// on the GPU, 3 the same scored.  The lines are planned by HipModel::make_packed_plan and laid out at rows off[t] + m as a
+// request's are, then go through log_softmax_argmax and the engine's own decode_packed (engine.cpp).  res: one result per
+// line in the caller's order — steps, step_logp / line_score (scored), logp (want_logp; unmasked), ctc_len; a line with T = 0 stays empty.
+void ctc_decode_packed(const float* logits, const int32_t* T, size_t n, int C, const uint8_t* excluded, int method,
+                       uint32_t width, bool want_logp, std::vector<RecResult>* res);
+
 // One line to crop into a tensor of recognition inputs: rows of `out_w` floats, the first at float offset `out_off`.
 struct CropLine {
     const RecLine* line;

@@ -13,7 +13,11 @@
 //     threshold are taken in slot order, and the survivors are ordered by (score desc, slot asc) — exactly the
 //     stable sort of the textbook formulation;
 //   * new prefixes get nodes (parent, label) / (parent, time) in per-line arenas in HBM; the answer is read back
-//     by walking the best beam's chain.
+//     by walking the best beam's chain;
+//   * a prefix that fell out of the beams and is reached again gets a NEW node, while a surviving beam that extends it
+//     still points at the old one: "beam i's parent prefix is beam p" is therefore a comparison of label sequences,
+//     not of node numbers — equal numbers first, else equal 64-bit hashes of the sequences (kept per beam) confirmed
+//     by walking both chains.
 #include "beam_math.hpp"
 #include "common.hpp"
 #include "kernels.hpp"
@@ -68,6 +72,24 @@ __device__ __forceinline__ void hist_add(uint32_t* hist, unsigned digit, bool ac
     if ((todo >> lane) & 1) atomicAdd(&hist[digit], 1u);
 }
 
+// hash of a label sequence from its parent's: one multiply-xorshift round per label
+__device__ __forceinline__ uint64_t seq_hash(uint64_t parent, int label) {
+    uint64_t h = (parent ^ (uint64_t)(label + 1)) * 0x9E3779B97F4A7C15ull;
+    return h ^ (h >> 29);
+}
+
+// nodes a and b spell the same label sequence: their chains agree label for label up to a common node (the root at the latest)
+__device__ __forceinline__ bool same_prefix(const int2* nodes, int a, int b) {
+    while (a != b) {
+        if (a <= 0 || b <= 0) return false;   // one chain is at the root, the other is not: different lengths
+        const int2 na = nodes[a], nb = nodes[b];
+        if (na.y != nb.y) return false;
+        a = na.x;
+        b = nb.x;
+    }
+    return true;
+}
+
 // append `value` to list[] for every lane with `take`, one atomic on the counter per wave
 __device__ __forceinline__ void list_append(uint16_t* list, int* counter, bool take, uint16_t value) {
     const uint64_t mask = __ballot(take);
@@ -96,7 +118,11 @@ ctc_beam_kernel(BeamArgs a) {
     double* npb = spnb + W;                                            // next beams
     double* npnb = npb + W;
     uint64_t* sel_key = reinterpret_cast<uint64_t*>(npnb + W);         // [W] survivors (unordered)
-    int* node = reinterpret_cast<int*>(sel_key + W);                   // [W] each
+    uint64_t* hsh = sel_key + W;                                       // [W] each: hash of the beam's label sequence,
+    uint64_t* phsh = hsh + W;                                          // of its parent's, and the next beams' two
+    uint64_t* nhsh = phsh + W;
+    uint64_t* nphsh = nhsh + W;
+    int* node = reinterpret_cast<int*>(nphsh + W);                     // [W] each
     int* par = node + W;
     int* pos = par + W;
     int* lab = pos + W;
@@ -118,6 +144,7 @@ ctc_beam_kernel(BeamArgs a) {
     int2* posn = a.posn + (size_t)m * a.cap;
     if (tid == 0) {
         node[0] = 0; par[0] = -1; pos[0] = 0; lab[0] = -1; pb[0] = 0.0; pnb[0] = kNegInf;
+        hsh[0] = 0x243F6A8885A308D3ull; phsh[0] = 0;
         ctl[NB] = 1; ctl[NODE_CNT] = 1; ctl[POS_CNT] = 1;
         nodes[0] = make_int2(-1, 0);
         posn[0] = make_int2(-1, 0);
@@ -137,9 +164,17 @@ ctc_beam_kernel(BeamArgs a) {
             tot[tid] = lse(pb[tid], pnb[tid]);
             int p = -1;
             const int pr = par[tid];
-            if (pr >= 0)
-                for (int j = 0; j < nb; j++)
+            if (pr >= 0) {
+                const uint64_t ph = phsh[tid];
+                int first = -1;   // the first beam whose sequence hashes like the parent prefix
+                for (int j = 0; j < nb; j++) {
                     if (node[j] == pr) { p = j; break; }
+                    if (first < 0 && hsh[j] == ph) first = j;
+                }
+                if (p < 0 && first >= 0)   // the parent prefix may be among the beams under a newer node
+                    for (int j = first; j < nb; j++)
+                        if (hsh[j] == ph && same_prefix(nodes, node[j], pr)) { p = j; break; }
+            }
             pidx[tid] = p;
         }
         for (int i = tid; i < N; i += BEAM_NT) { key[i] = 0; child[i] = 255; }
@@ -298,11 +333,13 @@ ctc_beam_kernel(BeamArgs a) {
             if (c == 0) {                 // beam i's own prefix, inserted by itself
                 nnode[tid] = node[i]; npar[tid] = par[i]; npos[tid] = pos[i]; nlab[tid] = lab[i];
                 npb[tid] = spb[i]; npnb[tid] = spnb[i];
+                nhsh[tid] = hsh[i]; nphsh[tid] = phsh[i];
             } else if (owner != 255) {    // beam `owner`'s prefix, first inserted as the extension (i, c) of its parent i
                 const int pn = atomicAdd(&ctl[POS_CNT], 1);
                 posn[pn] = make_int2(pos[i], t);
                 nnode[tid] = node[owner]; npar[tid] = par[owner]; npos[tid] = pn; nlab[tid] = lab[owner];
                 npb[tid] = spb[owner]; npnb[tid] = spnb[owner];
+                nhsh[tid] = hsh[owner]; nphsh[tid] = phsh[owner];
             } else {                      // a new prefix
                 const int nn = atomicAdd(&ctl[NODE_CNT], 1);
                 const int pn = atomicAdd(&ctl[POS_CNT], 1);
@@ -311,12 +348,14 @@ ctc_beam_kernel(BeamArgs a) {
                 nnode[tid] = nn; npar[tid] = node[i]; npos[tid] = pn; nlab[tid] = c;
                 npb[tid] = kNegInf;
                 npnb[tid] = (c == lab[i] ? pb[i] : tot[i]) + row[c];
+                nhsh[tid] = seq_hash(hsh[i], c); nphsh[tid] = hsh[i];
             }
         }
         __syncthreads();
         if (tid < keep) {
             node[tid] = nnode[tid]; par[tid] = npar[tid]; pos[tid] = npos[tid]; lab[tid] = nlab[tid];
             pb[tid] = npb[tid]; pnb[tid] = npnb[tid];
+            hsh[tid] = nhsh[tid]; phsh[tid] = nphsh[tid];
         }
         if (tid == 0) ctl[NB] = keep;
         __syncthreads();
@@ -355,6 +394,7 @@ size_t beam_lds_bytes(int W, int C) {
     b += (size_t)C * 8;                    // row
     b += (size_t)W * 8 * 7;                // pb pnb tot spb spnb npb npnb
     b += (size_t)W * 8;                    // sel_key
+    b += (size_t)W * 8 * 4;                // hsh phsh nhsh nphsh
     b += (size_t)W * 4 * 11;               // node par pos lab pidx nnode npar npos nlab sel_idx sorted
     b += 256 * 4 + BEAM_NT * 4 + 16 * 4;   // hist cnt256 ctl
     b += BEAM_LIST * 2;                    // list

@@ -49,9 +49,20 @@ def step_logps(L, steps):
     return np.array([L[p, l] for l, p in steps], np.float32)
 
 
-def beam_search(L, width):
+BEAM_STATS = ("steps", "threshold_ties", "short", "merges", "parent_later", "parent_earlier", "revived")
+
+
+def beam_search(L, width, stats=None):
     """oracle/pipeline.py::ctc_beam_search's loop, also returning the best beam's beam_lse(pb, pnb)
-    -> (steps [(label, pos)], line score float64)."""
+    -> (steps [(label, pos)], line score float64).
+
+    stats (optional, a dict): counts, over the time steps (BEAM_STATS), those where the scores at ranks keep - 1 and keep
+    are equal (keep = min(width, candidates): a tie at the pruning threshold), where there are fewer candidates than the
+    width ("short"), where an extension of a beam is the prefix of a current beam ("merges"), and among those where the
+    extended (parent) beam comes later / earlier in the beam order than the beam it merges with; and those where an
+    extension is a prefix that is no current beam although a current beam extends it, and both survive the pruning
+    ("revived": the prefix fell out of the beams while its child stayed, and is back beside it).  The search itself does
+    not look at it."""
     T, C = L.shape
     NEG = -math.inf
     lse = OP.beam_lse
@@ -70,7 +81,11 @@ def beam_search(L, width):
                 e[1] = lse(e[1], pb)
                 e[2] = lse(e[2], pnb)
 
-        for labels, positions, pb, pnb in beams:
+        index = {b[0]: i for i, b in enumerate(beams)} if stats is not None else None
+        orphans = {b[0][:-1] for b in beams if b[0] and b[0][:-1] not in index} if stats is not None else None
+        later = earlier = False
+        back = set()
+        for i, (labels, positions, pb, pnb) in enumerate(beams):
             total = lse(pb, pnb)
             add(labels, positions, total + row[0], NEG)
             last = labels[-1] if labels else -1
@@ -78,6 +93,12 @@ def beam_search(L, width):
                 lp = row[c]
                 if lp == NEG:
                     continue
+                if index is not None:
+                    j = index.get(labels + (c,))
+                    if j is not None:
+                        later, earlier = later or i > j, earlier or i < j
+                    if labels + (c,) in orphans:
+                        back.add(labels + (c,))
                 if c == last:
                     add(labels, positions, NEG, pnb + lp)
                     add(labels + (c,), positions + (t,), NEG, pb + lp)
@@ -85,6 +106,13 @@ def beam_search(L, width):
                     add(labels + (c,), positions + (t,), NEG, total + lp)
         scored = [(lse(cand[k][1], cand[k][2]), i, k) for i, k in enumerate(order)]
         scored.sort(key=lambda x: (-x[0], x[1]))
+        if stats is not None:
+            keep = min(width, len(scored))
+            kept = {k for _, _, k in scored[:keep]}
+            revived = any(k in kept and any(b and b[:-1] == k for b in kept) for k in back)
+            for name, hit in zip(BEAM_STATS, (True, keep < len(scored) and scored[keep - 1][0] == scored[keep][0],
+                                              len(scored) < width, later or earlier, later, earlier, revived)):
+                stats[name] = stats.get(name, 0) + int(hit)
         beams = [(k, cand[k][0], cand[k][1], cand[k][2]) for _, _, k in scored[:width]]
     best = beams[0]
     best_score = lse(best[2], best[3])

@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 
 import confidence_ref as CR
+import ctc_cases as CC
 from oracle import pipeline as OP
 
 
@@ -26,7 +27,7 @@ def _random_logp(rng, T, C, peak):
 
 def beam_matrices():
     """Seeded [T, C] matrices: masked (-inf) columns, a step where only the blank is allowed, exact ties (values
-    quantised to a few levels), T = 0 and T = 1, for widths 1, 8 and 100."""
+    quantised to a few levels), T = 0 and T = 1, for widths 1, 8 and 100; and lines with revived prefixes (ctc_cases.py)."""
     rng = np.random.default_rng(1234)
     out = []
     for T, C in [(0, 97), (1, 97), (1, 5), (12, 6), (30, 12), (40, 97), (60, 20)]:
@@ -42,7 +43,8 @@ def beam_matrices():
             lp = lv[rng.integers(0, 3, (T, C))].astype(np.float32)
             lp[:, 3] = -np.inf
             out.append(("ties-T%d-C%d-w%d" % (T, C, w), lp, w))
-    return out
+    # a prefix falls out of the beams and comes back beside a beam that extends it: the two must merge
+    return out + CC.revived_matrices()
 
 
 MATRICES = beam_matrices()
