@@ -102,6 +102,21 @@ OCRS_API ocrs_status ocrs_ctc_decode_packed(const float* logits, const int32_t* 
                                             int method, uint32_t width, uint32_t** labels, uint32_t** positions,
                                             size_t* step_offsets, float** step_logp, double* scores, float** logp);
 
+/* Test hook: the component stage of detection (find_connected_component_rects, detection.rs:41-62) on chosen masks.
+ * `masks`: n pages [h][w] of 0 / 1 bytes on the host.  They are uploaded and go through the component labelling and the
+ * contour / rectangle kernel as a detection request's masks do (RDP eps 2, the process's `ccl_quad` option), with the
+ * caller's `expand`, `min_area` and scratch sizes: `max_comp` component slots and `arena` border points per page.  Outputs
+ * (the caller's arrays), per page: n_roots[i] the number of components found (also when it exceeds max_comp), overflow[i]
+ * non-zero when the page did not fit max_comp or arena, rects [n][max_comp][6] (cx, cy, upx, upy, w, h) and valid
+ * [n][max_comp].  Slot c < min(n_roots[i], max_comp) is the page's c-th component in raster order of its first pixel;
+ * valid 1: the rect is written and w * h >= min_area; valid 0: no rect or too small (the floats are then unspecified).  A
+ * slot the kernel did not write at all holds valid 0xEE.  On an overflowed page which slots were filled is unspecified.
+ * OCRS_ERR_INVALID_ARGUMENT: h or w outside 1 .. 65535, max_comp < 1, arena < 1 or >= 2^31, or a batch beyond the hook's
+ * bounds (64 pages, 2^26 pixels, 2^26 arena points, 2^24 slots in all). */
+OCRS_API ocrs_status ocrs_mask_component_rects(const uint8_t* masks, size_t n, int h, int w, float expand, float min_area,
+                                               int max_comp, int64_t arena, int32_t* n_roots, int32_t* overflow, float* rects,
+                                               uint8_t* valid);
+
 /* Test hook (host only, no GPU work): how the persistent GRU kernel would deal the 16-line row tiles of a request
  * to its waves.  lengths_desc = sequence lengths of the lines, descending (tile k = lines 16k .. 16k+15).
  * *n_clusters = clusters per direction, *waves = 4 = wave slots per cluster; tiles[4s .. 4s+3] for slot

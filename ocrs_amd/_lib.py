@@ -73,7 +73,7 @@ DECLARED_SYMBOLS = [
     "ocrs_group_member_stats", "ocrs_numa_parse_cpulist", "ocrs_numa_bind_selftest", "ocrs_engine_recognize_logits", "ocrs_engine_set_option", "ocrs_engine_get_option", "ocrs_option_name", "ocrs_device_pool_stats", "ocrs_device_pool_configure", "ocrs_device_pool_trim",
     "ocrs_device_set_isolation", "ocrs_device_isolation", "ocrs_group_set_replay", "ocrs_abi_version",
     "ocrs_engine_recognize_text_scored", "ocrs_engine_recognize_text_batch_scored", "ocrs_ctc_beam_search_scored",
-    "ocrs_engine_run_recognition_ops", "ocrs_ctc_decode_packed",
+    "ocrs_engine_run_recognition_ops", "ocrs_ctc_decode_packed", "ocrs_mask_component_rects",
     "ocrs_engine_detect_words_scored", "ocrs_engine_detect_words_batch_scored", "ocrs_group_detect_words_batch_scored",
     "ocrs_engine_find_text_lines_indexed", "ocrs_engine_find_text_lines_batch_indexed",
     "ocrs_detection_tile_plan", "ocrs_engine_detect_words_tiled", "ocrs_engine_detect_words_batch_tiled",
@@ -335,6 +335,33 @@ def ctc_decode_packed(mats, excluded=None, method="greedy", width=1, want_logp=T
             r["score"] = float(scores[i])
         out.append(r)
         row += t
+    return out
+
+
+def mask_component_rects(masks, expand=3.0, min_area=100.0, max_comp=None, arena=None):
+    """ocrs_mask_component_rects on masks [n, h, w] (or one [h, w]) of 0 / 1 bytes -> per page a dict: n_roots, overflow
+    (bool), rects [k, 6] float32 and valid [k] uint8 for the k = min(n_roots, max_comp) slots of the page.  max_comp and
+    arena default to what a detection request takes for the page size."""
+    import numpy as np
+    masks = np.ascontiguousarray(masks, np.uint8)
+    if masks.ndim == 2:
+        masks = masks[None]
+    n, h, w = masks.shape
+    if max_comp is None:
+        max_comp = min(65536, h * w // 2 + 16)
+    if arena is None:
+        arena = 2 * h * w + 64
+    slots = max(int(max_comp), 1)
+    n_roots, overflow = np.zeros(n, np.int32), np.zeros(n, np.int32)
+    rects, valid = np.zeros((n, slots, 6), np.float32), np.zeros((n, slots), np.uint8)
+    check(lib().ocrs_mask_component_rects(masks.ctypes.data_as(C.POINTER(C.c_uint8)), C.c_size_t(n), C.c_int(h), C.c_int(w),
+                                          C.c_float(expand), C.c_float(min_area), C.c_int(int(max_comp)), C.c_int64(int(arena)),
+                                          n_roots.ctypes.data_as(C.POINTER(C.c_int32)), overflow.ctypes.data_as(C.POINTER(C.c_int32)),
+                                          rects.ctypes.data_as(C.POINTER(C.c_float)), valid.ctypes.data_as(C.POINTER(C.c_uint8))))
+    out = []
+    for i in range(n):
+        k = min(int(n_roots[i]), slots)
+        out.append({"n_roots": int(n_roots[i]), "overflow": bool(overflow[i]), "rects": rects[i, :k].copy(), "valid": valid[i, :k].copy()})
     return out
 
 

@@ -226,6 +226,22 @@ ocrs_status ocrs_ctc_decode_packed(const float* logits, const int32_t* lengths, 
     });
 }
 
+ocrs_status ocrs_mask_component_rects(const uint8_t* masks, size_t n, int h, int w, float expand, float min_area, int max_comp,
+                                      int64_t arena, int32_t* n_roots, int32_t* overflow, float* rects, uint8_t* valid) {
+    return guarded([&] {
+        if (!masks || !n_roots || !overflow || !rects || !valid || n < 1) fail(OCRS_ERR_INVALID_ARGUMENT, "bad argument");
+        if (h < 1 || w < 1 || h > 65535 || w > 65535) fail(OCRS_ERR_INVALID_ARGUMENT, "unsupported page size %dx%d", h, w);
+        if (max_comp < 1) fail(OCRS_ERR_INVALID_ARGUMENT, "max_comp %d: at least 1", max_comp);
+        if (arena < 1 || arena >= (int64_t)0x80000000ll)
+            fail(OCRS_ERR_INVALID_ARGUMENT, "arena %lld: between 1 and 2^31 - 1 border points", (long long)arena);
+        // a test hook: everything at once in device memory, so the batch is bounded (21 bytes per arena point, 33 per slot)
+        const int64_t cap = (int64_t)1 << 26;
+        if ((int64_t)n > 64 || (int64_t)n * h * w > cap || (int64_t)n * arena > cap || (int64_t)n * max_comp > cap / 4)
+            fail(OCRS_ERR_INVALID_ARGUMENT, "batch too large");
+        mask_component_rects(masks, (int)n, h, w, expand, min_area, max_comp, arena, n_roots, overflow, rects, valid);
+    });
+}
+
 uint32_t ocrs_abi_version(void) { return OCRS_ABI_VERSION; }
 
 static void check_option_set(int r, const char* name, long value) {   // what set_option (common.hpp) returned

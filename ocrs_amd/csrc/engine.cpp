@@ -1368,6 +1368,28 @@ void ocrs::ctc_decode_packed(const float* logits, const int32_t* T, size_t n, in
     }
 }
 
+void ocrs::mask_component_rects(const uint8_t* masks, int n, int h, int w, float expand, float min_area, int max_comp, int64_t arena,
+                                int32_t* n_roots, int32_t* overflow, float* rects, uint8_t* valid) {
+    DeviceScope bind(-1);
+    Workspace ws;
+    const int64_t px = (int64_t)h * w;
+    uint8_t* d_mask = ws.alloc_n<uint8_t>((size_t)n * px);
+    ws.upload(d_mask, masks, (size_t)n * px);
+    const k::CclBuffers b = alloc_ccl(ws, n, h, px, max_comp, arena, false, true);
+    // slots the contour kernel leaves unwritten are recognisable: valid 0xEE (the kernel writes 0 or 1), rects all-ones words
+    OCRS_HIP(hipMemsetAsync(b.valid, 0xEE, (size_t)n * max_comp, ws.s()));
+    OCRS_HIP(hipMemsetAsync(b.rects, 0xFF, (size_t)n * max_comp * 6 * sizeof(float), ws.s()));
+    // what run_ccl does for an unscored, unprepared size group
+    k::ccl_label(d_mask, n, h, w, b, max_comp, ws.s(), false);
+    k::contour_rects(d_mask, n, h, w, b, max_comp, arena, expand, min_area, /*eps*/ 2.0f, ws.s(), false);
+    ws.download(n_roots, b.n_roots, (size_t)n * sizeof(int32_t));
+    ws.download(overflow, b.overflow, (size_t)n * sizeof(int32_t));
+    ws.download(rects, b.rects, (size_t)n * max_comp * 6 * sizeof(float));
+    ws.download(valid, b.valid, (size_t)n * max_comp);
+    ws.sync();
+    OCRS_HIP(hipGetLastError());
+}
+
 void ocrs_engine::recognize_lines(const ocrs_page* const* pages, size_t n_pages, RecResult* res, size_t L, bool scored,
                                   bool want_logp) const {
     if (L == 0) return;

@@ -90,6 +90,14 @@ struct RecResult {
 void ctc_decode_packed(const float* logits, const int32_t* T, size_t n, int C, const uint8_t* excluded, int method,
                        uint32_t width, bool want_logp, std::vector<RecResult>* res);
 
+// Test hook (ocrs_mask_component_rects): the component stage of detection (detection.rs:41-62) on chosen masks [n][h][w]
+// (0 / 1 bytes, host).  The masks are uploaded and run through k::ccl_label and k::contour_rects as run_ccl runs an unscored,
+// unprepared size group (eps 2, the process's ccl_quad option, buffers from alloc_ccl) with the caller's expand, min_area,
+// max_comp and arena.  Out, per page: n_roots, the overflow flag, rects [max_comp][6] and valid [max_comp]; a slot the
+// contour kernel did not write holds valid 0xEE and all-ones rect words.
+void mask_component_rects(const uint8_t* masks, int n, int h, int w, float expand, float min_area, int max_comp, int64_t arena,
+                          int32_t* n_roots, int32_t* overflow, float* rects, uint8_t* valid);
+
 // One line to crop into a tensor of recognition inputs: rows of `out_w` floats, the first at float offset `out_off`.
 struct CropLine {
     const RecLine* line;
