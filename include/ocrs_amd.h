@@ -846,6 +846,61 @@ OCRS_API ocrs_status ocrs_engine_despeckle_pages(const ocrs_engine* e, const ocr
                                                  const ocrs_speckle_params* params, ocrs_page** out_pages, uint8_t** out_masks,
                                                  ocrs_speckle_info* out_infos);
 
+/* ------------------------------------------------------------------------
+ * Adaptive binarisation (no reference counterpart, opt-in).  Rule removal and despeckling above decide what
+ * is ink with one threshold for the whole page; a stain, a fold shadow narrower than a normalisation tile, show-through or
+ * faint ink beside dark ink defeat any single cut.  These calls make a new resident page of the same size on which every
+ * pixel that Sauvola's local rule calls ink is written at the ink level and every other counted pixel at the paper level;
+ * a NaN pixel keeps its own 32-bit word (payload included); coordinates do not move, so nothing needs mapping back.  The
+ * source page is untouched; release both with ocrs_page_free in any order.  The page is dark ink on light paper
+ * (ocrs_engine_normalize_page makes it so).  On the result ocrs_engine_remove_rules_page and ocrs_engine_despeckle_page at
+ * threshold 0 use the local decision.  What a trained detector or recogniser gains is uncalibrated.
+ *
+ * The definition (tests/binarize_ref.py restates it and the library equals it bit for bit; integers only, every sum a plain
+ * sum, so the result does not depend on schedule or batch).  With r = radius, kq = k_q8 and R = 128:
+ *   bins       as in the normalisation above: g = clamp(v + 0.5f, 0, 1), b = floor(g * 256f) within 0 .. 255 (so +inf is
+ *              bin 255 and -inf bin 0); NaN is not counted.
+ *   window     of pixel (y, x): [y - r, y + r] x [x - r, x + r] clipped to the page; the page edge is a wall, nothing is
+ *              mirrored or padded.  Over its counted pixels n is their number, S the sum of their bins, Q the sum of the
+ *              squares of their bins.  A counted pixel is in its own window: n >= 1.
+ *   decision   Sauvola: T = m (1 + k (s / R - 1)), m = S / n, s = sqrt(Q / n - m^2), k = kq / 256; ink is b < T.
+ *              Multiplied out: V = n Q - S^2, A = n R (256 (b n - S) + kq S), B = kq S;
+ *              ink <=> A < B sqrt(V) <=> A < 0 or A^2 < B^2 V, compared exactly (128 bits).  The strict < decides ties: a
+ *              flat window (V = 0) has no ink, so a blank page comes back as paper and so does an all-black one (Sauvola's
+ *              known behaviour).  kq = 0 is the plain local mean: b n < S.
+ *   output     keep_ink = 0: ink_level on ink, paper on every other counted pixel.  keep_ink = 1: the page's own 32-bit word
+ *              on ink (no arithmetic: -0.0 and out-of-range values survive), paper elsewhere: background whitening that
+ *              leaves the grey edges of the strokes to the recogniser.  NaN pixels keep their word in both modes.
+ *
+ * ocrs_binarize_params_default: radius 15, k_q8 87 (k = 0.34), keep_ink 0, ink_level NaN (-0.5f), paper NaN (+0.5f).
+ * ocrs_binarize_params_check (host only): OCRS_ERR_INVALID_ARGUMENT for a radius outside 1 .. 127, a k_q8 outside 0 .. 256, a
+ * keep_ink that is neither 0 nor 1, an infinite ink_level or paper; the engine calls refuse the same, and a page with a
+ * side over 65535 or with more than 2^31 - 1 pixels.
+ * ocrs_engine_binarize_pages serves n pages of any sizes, each with its own params[i], in three launches for the whole
+ * batch on one stream; out_pages[n] receives the pages, out_infos[n] (may be NULL) the counts and the fills used,
+ * out_masks[n] (may be NULL) per page a host uint8 [h][w], to be released with ocrs_buffer_free: bit 0 ink.
+ * ocrs_engine_binarize_page: params == NULL means the default. */
+typedef struct ocrs_binarize_params {
+    int32_t radius;        /* r, 1 .. 127: the window is (2 r + 1) x (2 r + 1) */
+    int32_t k_q8;          /* kq, 0 .. 256: Sauvola's k in 1/256 */
+    int32_t keep_ink;      /* 0: ink is written at ink_level; 1: ink keeps its own word */
+    float ink_level;       /* the fill of ink; NaN: -0.5f; not infinite */
+    float paper;           /* the fill of every other counted pixel; NaN: +0.5f; not infinite */
+} ocrs_binarize_params;
+typedef struct ocrs_binarize_info {
+    uint64_t counted;      /* pixels that are not NaN */
+    uint64_t ink;          /* counted pixels the local rule calls ink */
+    float ink_fill;        /* the ink fill used (with keep_ink it is not written) */
+    float paper_fill;      /* the paper fill used */
+} ocrs_binarize_info;
+OCRS_API ocrs_status ocrs_binarize_params_default(ocrs_binarize_params* out);
+OCRS_API ocrs_status ocrs_binarize_params_check(const ocrs_binarize_params* params);
+OCRS_API ocrs_status ocrs_engine_binarize_page(const ocrs_engine* e, const ocrs_page* page, const ocrs_binarize_params* params,
+                                               ocrs_page** out_page, uint8_t** out_mask, ocrs_binarize_info* out_info);
+OCRS_API ocrs_status ocrs_engine_binarize_pages(const ocrs_engine* e, const ocrs_page* const* pages, size_t n,
+                                                const ocrs_binarize_params* params, ocrs_page** out_pages, uint8_t** out_masks,
+                                                ocrs_binarize_info* out_infos);
+
 /* OcrEngine::detection_threshold (lib.rs:282-287). */
 OCRS_API float ocrs_engine_detection_threshold(const ocrs_engine* e);
 

@@ -16,7 +16,7 @@ from ._lib import OcrsError, check, lib
 
 __all__ = ["OcrEngine", "OcrEngineParams", "ImageSource", "ImageSourceError", "DimOrder", "DecodeMethod", "Model",
            "OcrInput", "TextLine", "TextWord", "TextChar", "OcrsError", "DEFAULT_ALPHABET", "EngineGroup", "line_frame",
-           "Orientation", "orientation_vote", "unrotate_rects", "unrotate_lines", "work_size", "rescale_rects", "normalize_params", "rules_params", "speckle_params"]
+           "Orientation", "orientation_vote", "unrotate_rects", "unrotate_lines", "work_size", "rescale_rects", "normalize_params", "rules_params", "speckle_params", "binarize_params"]
 
 # lib.rs:34 (with the EUR sign the comment at lib.rs:33 asks for)
 DEFAULT_ALPHABET = " 0123456789!\"#$%&'()*+,-./:;<=>?@[\\]^_`{|}~€ABCDEFGHIJKLMNOPQRSTUVWXYZabcdefghijklmnopqrstuvwxyz"
@@ -539,6 +539,33 @@ def _speckle_struct(max_area=None, max_hole=None, keep_near=None, threshold=None
     return p
 
 
+def binarize_params(radius=None, k=None, keep_ink=None, ink_level=None, paper=None):
+    """ocrs_binarize_params as a dict: ocrs_binarize_params_default (radius 15, k_q8 87, keep_ink False,
+    ink_level and paper None = -0.5 and +0.5) with the given fields replaced (k rounded to 1/256: k_q8), checked by
+    ocrs_binarize_params_check (host only)."""
+    p = _binarize_struct(radius, k, keep_ink, ink_level, paper)
+    check(lib().ocrs_binarize_params_check(C.byref(p)))
+    return {"radius": int(p.radius), "k_q8": int(p.k_q8), "keep_ink": bool(p.keep_ink),
+            "ink_level": None if p.ink_level != p.ink_level else float(p.ink_level), "paper": None if p.paper != p.paper else float(p.paper)}
+
+
+def _binarize_struct(radius=None, k=None, keep_ink=None, ink_level=None, paper=None):
+    p = _lib.BinarizeParams()
+    check(lib().ocrs_binarize_params_default(C.byref(p)))
+    if radius is not None:
+        p.radius = int(radius)
+    if k is not None:
+        q = math.floor(float(k) * 256.0 + 0.5)   # Sauvola's k in 1/256; out of range is the library's to refuse
+        p.k_q8 = int(max(-1, min(q, 257)))
+    if keep_ink is not None:
+        p.keep_ink = 1 if keep_ink else 0
+    if ink_level is not None:
+        p.ink_level = float(ink_level)
+    if paper is not None:
+        p.paper = float(paper)
+    return p
+
+
 class Skew:
     """ocrs_engine_estimate_skew's outputs: angle (degrees; the page's content is turned counter-clockwise
     by it, deskew_map(.., angle) undoes it), scores (best coarse, runner-up coarse, at the angle), work_hw (the size the
@@ -1029,6 +1056,48 @@ class OcrEngine:
             res.append([infos[i].as_dict() for i in range(n)])
         return tuple(res) if mask or info else made
 
+    # ---- adaptive binarisation
+    def binarize(self, inp, radius=15, k=0.34, keep_ink=False, ink_level=None, paper=None, mask=False, info=False):
+        """ocrs_engine_binarize_page: the page cut into ink and paper by Sauvola's local threshold, in exact integers, as a
+        new resident page of the same size.  The page is dark ink on light paper (normalize makes it so).  A pixel is ink
+        when its bin lies under m (1 + k (s / 128 - 1)), m and s the mean and the standard deviation of the bins in the
+        (2 radius + 1)^2 window around it, clipped to the page; k is rounded to 1/256 (0: the plain local mean).  A flat
+        window has no ink: a blank page comes back as paper, and so does an all-black one.  Ink is written as ink_level
+        (None: -0.5) or, with keep_ink, keeps its own bits; every other pixel is written as paper (None: +0.5); NaN pixels
+        keep their bits.  mask=True: also the uint8 [H, W] mask (bit 0 ink); info=True: also {"counted", "ink",
+        "ink_fill", "paper_fill"}.  -> page, or (page[, mask][, info])."""
+        out = self.binarize_batch([inp], [{"radius": radius, "k": k, "keep_ink": keep_ink, "ink_level": ink_level, "paper": paper}],
+                                  mask=mask, info=info)
+        return tuple(o[0] for o in out) if mask or info else out[0]
+
+    def binarize_batch(self, inputs, params=None, mask=False, info=False):
+        """ocrs_engine_binarize_pages: pages of any sizes, each with its own parameters (a dict of binarize's keywords, or
+        None for the default; one for all, or one per page), all passes for the whole batch on one stream.  -> pages, or
+        (pages[, masks][, infos])."""
+        n = len(inputs)
+        if params is None or isinstance(params, dict):
+            params = [params] * n
+        if len(params) != n:
+            raise ValueError("binarize_batch: one parameter set per page")
+        pages = _page_array(inputs)
+        ps = (_lib.BinarizeParams * n)(*[_binarize_struct(**(p or {})) for p in params])
+        out = (C.c_void_p * n)()
+        masks = (C.POINTER(C.c_uint8) * n)()
+        infos = (_lib.BinarizeInfo * n)()
+        check(lib().ocrs_engine_binarize_pages(self._h, pages, C.c_size_t(n), ps, out, masks if mask else None, infos if info else None))
+        made = _new_inputs(out, n)
+        res = [made]
+        if mask:
+            got = []
+            for i in range(n):
+                h, w = made[i].shape[-2:]
+                got.append(np.ctypeslib.as_array(masks[i], shape=(h * w,)).reshape(h, w).copy())
+                lib().ocrs_buffer_free(masks[i])
+            res.append(got)
+        if info:
+            res.append([infos[i].as_dict() for i in range(n)])
+        return tuple(res) if mask or info else made
+
     # ---- page deskew (DESIGN.md §7.6)
     def skew_scores(self, inputs, sc_table):
         """ocrs_engine_skew_scores: the skew profile scores of pages of any sizes (a side at most 4096) at the angles of
@@ -1442,7 +1511,7 @@ class OcrEngine:
 
     # ---- lib.rs:290-300
     def get_text(self, inp, rectify=False, orientation=None, work_size=None, normalize=None, deskew=None, deskew_fill=0.5,
-                 perspective=None, perspective_fill=0.5, rules=None, despeckle=None):
+                 perspective=None, perspective_fill=0.5, rules=None, despeckle=None, binarize=None):
         """rectify=True: the same sequence (detect_words, find_text_lines, recognize_text) with rectified crops.
         orientation: None reads the page as given; an int turns it by that many quarter turns counter-clockwise first
         (rotate); "auto" by what detect_orientation finds.
@@ -1462,12 +1531,19 @@ class OcrEngine:
         despeckle: None reads the page as given; True or a dict of despeckle()'s keywords reads the page with its specks
         removed.  Applied after perspective and normalisation (it needs dark ink on light paper) and before
         the turn, deskew, whose interpolation would smear one-pixel specks into grey blobs, and rule removal.  Coordinates do
-        not move.  get_text returns text alone; callers that want boxes run the steps
+        not move.
+        binarize: None reads the page as given; True or a dict of binarize()'s keywords reads the page cut into ink and
+        paper by the local threshold.  Applied after perspective and normalisation (it needs dark ink on
+        light paper) and before despeckling, the turn, deskew and rule removal, whose threshold 0 is then the local
+        decision.  Coordinates do not move.
+        get_text returns text alone; callers that want boxes run the steps
         themselves and bring them back last with unproject_rects / unproject_lines."""
         if perspective is not None:
             inp = self.straighten(inp, None if isinstance(perspective, str) and perspective == "auto" else perspective, fill=perspective_fill)[0]
         if normalize is not None and normalize is not False:
             inp = self.normalize(inp, **({} if normalize is True else dict(normalize)))
+        if binarize is not None and binarize is not False:
+            inp = self.binarize(inp, **({} if binarize is True else dict(binarize)))
         if despeckle is not None and despeckle is not False:
             inp = self.despeckle(inp, **({} if despeckle is True else dict(despeckle)))
         if orientation is not None:

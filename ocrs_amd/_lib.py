@@ -92,6 +92,7 @@ DECLARED_SYMBOLS = [
     "ocrs_quad_map", "ocrs_engine_project_page", "ocrs_engine_project_pages", "ocrs_unproject_rects", "ocrs_unproject_chars",
     "ocrs_rules_params_default", "ocrs_rules_params_check", "ocrs_engine_remove_rules_page", "ocrs_engine_remove_rules_pages",
     "ocrs_speckle_params_default", "ocrs_speckle_params_check", "ocrs_engine_despeckle_page", "ocrs_engine_despeckle_pages",
+    "ocrs_binarize_params_default", "ocrs_binarize_params_check", "ocrs_engine_binarize_page", "ocrs_engine_binarize_pages",
 ]
 
 ABI_VERSION = 6   # include/ocrs_amd.h OCRS_ABI_VERSION
@@ -136,6 +137,17 @@ class SpeckleInfo(C.Structure):   # include/ocrs_amd.h ocrs_speckle_info
     _fields_ = [("paper_bin", C.c_int32), ("ink_bin", C.c_int32), ("paper_fill", C.c_float), ("ink_fill", C.c_float), ("ink", C.c_uint64),
                 ("counted", C.c_uint64), ("specks", C.c_uint64), ("kept", C.c_uint64), ("speck_pixels", C.c_uint64),
                 ("kept_pixels", C.c_uint64), ("holes", C.c_uint64), ("hole_pixels", C.c_uint64)]
+
+    def as_dict(self):
+        return {name: (float if name.endswith("_fill") else int)(getattr(self, name)) for name, _ in self._fields_}
+
+
+class BinarizeParams(C.Structure):   # include/ocrs_amd.h ocrs_binarize_params
+    _fields_ = [("radius", C.c_int32), ("k_q8", C.c_int32), ("keep_ink", C.c_int32), ("ink_level", C.c_float), ("paper", C.c_float)]
+
+
+class BinarizeInfo(C.Structure):   # include/ocrs_amd.h ocrs_binarize_info
+    _fields_ = [("counted", C.c_uint64), ("ink", C.c_uint64), ("ink_fill", C.c_float), ("paper_fill", C.c_float)]
 
     def as_dict(self):
         return {name: (float if name.endswith("_fill") else int)(getattr(self, name)) for name, _ in self._fields_}

@@ -122,6 +122,17 @@ def main(argv=None):
     ap.add_argument("--speck-keep-near", type=int, default=None, metavar="N",
                     help="with --despeckle: keep a speck that lies within N pixels of larger ink, 0 to 16 (default 0: keep none); for "
                          "i-dots and full stops when --speck-max-area is large")
+    ap.add_argument("--binarize", action="store_true",
+                    help="cut the page into ink and paper on the GPU before reading it, by Sauvola's local threshold over a "
+                         "window around every pixel instead of one cut for the page (after --normalize, before --despeckle, "
+                         "--orientation, --deskew and --remove-rules: it needs dark ink on light paper); the JSON gains "
+                         "\"binarize\" (no reference counterpart; what a detector gains is uncalibrated: DESIGN.md 7.10)")
+    ap.add_argument("--binarize-radius", type=int, default=None, metavar="N",
+                    help="with --binarize: the window reaches N pixels to every side, 1 to 127 (default 15)")
+    ap.add_argument("--binarize-k", type=float, default=None, metavar="X",
+                    help="with --binarize: Sauvola's k, 0 to 1, rounded to 1/256 (default 0.34; 0 is the plain local mean)")
+    ap.add_argument("--binarize-keep-ink", action="store_true",
+                    help="with --binarize: ink keeps its own grey levels and only the paper is whitened")
     ap.add_argument("-o", "--output")
     ap.add_argument("--debug", action="store_true")
     ap.add_argument("--text-map", action="store_true", help="write text-map.png (detect_text_pixels)")
@@ -144,6 +155,8 @@ def main(argv=None):
         ap.error("--rules-min-length, --rules-max-thickness and --rules-margin are only valid with --remove-rules")
     if (args.speck_max_area is not None or args.speck_fill_holes is not None or args.speck_keep_near is not None) and not args.despeckle:
         ap.error("--speck-max-area, --speck-fill-holes and --speck-keep-near are only valid with --despeckle")
+    if (args.binarize_radius is not None or args.binarize_k is not None or args.binarize_keep_ink) and not args.binarize:
+        ap.error("--binarize-radius, --binarize-k and --binarize-keep-ink are only valid with --binarize")
     if args.perspective_fill is not None and args.perspective is None:
         ap.error("--perspective-fill is only valid with --perspective")
     if args.perspective is not None and args.perspective != "auto":
@@ -211,6 +224,20 @@ def main(argv=None):
             print("Normalize: %s page (vote %d), white bin %d, levels %d .. %d, %d pixels counted"
                   % ("dark" if norm_info["dark"] else "light", norm_info["vote"], norm_info["white"], norm_info["lo"], norm_info["hi"],
                      norm_info["counted"]))
+    binarize_info = None
+    if args.binarize:   # from here on the page cut into ink and paper is the page; coordinates do not move
+        try:
+            inp, binarize_info = engine.binarize(inp, radius=15 if args.binarize_radius is None else args.binarize_radius,
+                                                 k=0.34 if args.binarize_k is None else args.binarize_k,
+                                                 keep_ink=args.binarize_keep_ink, info=True)
+        except (OcrsError, ValueError) as e:
+            if isinstance(e, OcrsError) and e.status != 1:   # OCRS_ERR_INVALID_ARGUMENT: a parameter out of range
+                raise
+            ap.error("--binarize: %s" % e)
+        if args.debug:
+            print("Binarize: %d of %d counted pixels are ink, written as %g (kept: %s); paper written as %g"
+                  % (binarize_info["ink"], binarize_info["counted"], binarize_info["ink_fill"],
+                     "yes" if args.binarize_keep_ink else "no", binarize_info["paper_fill"]))
     speckle_info = None
     if args.despeckle:   # from here on the page without its specks is the page; coordinates do not move
         try:
@@ -315,7 +342,7 @@ def main(argv=None):
     if args.json:
         content = output.format_json_output(args.image, tuple(shape_hw), texts, confidence=args.confidence, word_boxes=word_boxes,
                                             orientation=None if turns is None else 90 * turns, normalize=norm_info, skew=skew, outline=outline,
-                                            rules=rules_info, despeckle=speckle_info)
+                                            rules=rules_info, despeckle=speckle_info, binarize=binarize_info)
     else:
         content = output.format_text_output(texts)
     if args.output:

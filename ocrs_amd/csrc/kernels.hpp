@@ -512,6 +512,39 @@ size_t speckle_mask_words(int h, int w);    // 64-bit words of SpeckleDesc::mask
 // Pages of any mix of sizes and parameters, eight launches on `s`; total_blocks = the sum of speckle_tiles() over the pages.
 void despeckle_pages(const SpeckleDesc* d_descs, int n_pages, int total_blocks, hipStream_t s);
 
+// ---- kernels_binarize.hip ---------------------------------
+struct BinInfo {         // what a page's binarisation counted: the layout of ocrs_binarize_info
+    uint64_t counted;    // pixels that are not NaN
+    uint64_t ink;        // counted pixels the local rule calls ink
+    float ink_fill;      // what ink was written as (keep_ink: not written)
+    float paper_fill;    // what every other counted pixel was written as
+};
+constexpr int BIN_COUNTS = 8;        // 64-bit words of a block's record: [wave][2]
+constexpr int BIN_MAX_RADIUS = 127, BIN_MAX_KQ = 256;
+constexpr int BIN_STRIP = 256;       // columns of a block of the vertical pass: a lane per column
+constexpr int BIN_ROWS = 4;          // rows of a block of the horizontal pass: a wave per row
+struct BinDesc {         // one page that is binarised: dst [h, w] from src [h, w]
+    const float* src;
+    float* dst;          // never overlaps src
+    uint32_t* sums;      // [h * w][2] per pixel, over [x - r, x + r] of its row: n << 16 | S, and Q
+    unsigned long long* counts;  // [blocks of the vertical pass, BIN_COUNTS] what each block counted
+    BinInfo* info;
+    uint8_t* mask_out;   // [h, w] the mask of include/ocrs_amd.h, or null
+    int32_t h, w;        // each 1 .. 65535, h * w < 2^31
+    int32_t block0;      // first block of this page in the vertical pass: the sum of strips * segs of the pages before it
+    int32_t row_block0;  // first block of this page in the horizontal pass: the sum of ceil(h / BIN_ROWS) before it
+    int32_t strips, segs;   // ceil(w / BIN_STRIP), ceil(h / seg_rows)
+    int32_t seg_rows;    // rows of a block of the vertical pass (bin_seg_rows)
+    int32_t radius, kq;  // 1 .. 127, 0 .. 256
+    int32_t keep_ink;    // 0 / 1
+    uint32_t ink_bits, paper_bits;   // the fills as 32-bit words, defaults resolved
+};
+int bin_seg_rows(int h, int w, int radius);       // rows of a block of the vertical pass (host)
+int64_t bin_col_blocks(int h, int w, int radius); // blocks a page takes in the vertical pass (host)
+int64_t bin_row_blocks(int h);                    // blocks a page takes in the horizontal pass (host)
+// Pages of any mix of sizes and parameters, three launches on `s`; row_blocks and col_blocks are the sums over the pages.
+void binarize_pages(const BinDesc* d_descs, int n_pages, int row_blocks, int col_blocks, hipStream_t s);
+
 // kernels_peaks.hip
 void measure_peaks(double* mfma_tflops, double* copy_gbps);
 
