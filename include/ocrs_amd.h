@@ -901,6 +901,61 @@ OCRS_API ocrs_status ocrs_engine_binarize_pages(const ocrs_engine* e, const ocrs
                                                 const ocrs_binarize_params* params, ocrs_page** out_pages, uint8_t** out_masks,
                                                 ocrs_binarize_info* out_infos);
 
+/* ------------------------------------------------------------------------
+ * Stroke repair (no reference counterpart, opt-in).  Everything above leaves the shape of the ink as it
+ * is; faint faxes, dot-matrix and thermal printouts, worn ribbons and copies of copies have strokes broken into pieces,
+ * over-inked prints have them fused.  These calls make a new resident page of the same size by grey-level morphology:
+ * running minima and maxima over a rectangle around every pixel.  A result pixel is always the 32-bit word of some pixel
+ * of the source, never a recomputed number; a NaN pixel keeps its own word (payload included); coordinates do not move, so
+ * nothing needs mapping back.  The source page is untouched; release both with ocrs_page_free in any order.  The page is
+ * dark ink on light paper (ocrs_engine_normalize_page makes it so).  What a trained detector or recogniser gains is
+ * uncalibrated.
+ *
+ * The definition (tests/morph_ref.py restates it and the library equals it bit for bit; nothing is computed, so the result
+ * does not depend on schedule or batch):
+ *   order      pixels are ordered as 32-bit words w through the key k(w) = ~w if the sign bit is set, else w | 0x80000000:
+ *              -inf < ... < -0.0 < +0.0 < ... < +inf, denormals in their places, -0.0 and +0.0 two values.  NaN of any
+ *              payload is not counted: it enters no window.
+ *   window     of pixel (y, x): [y - ry, y + ry] x [x - rx, x + rx] clipped to the page; the page edge is a wall, nothing
+ *              is mirrored or padded.  A counted pixel is in its own window.
+ *   stages     lo: every counted pixel becomes the word of least key among the counted pixels of its window; hi: of the
+ *              greatest key.  A second stage reads the first stage's page under the same rules.
+ *   ops        named for what happens to the ink (dark): OCRS_MORPH_THICKEN = lo (ink grows), OCRS_MORPH_THIN = hi (ink
+ *              shrinks), OCRS_MORPH_CLOSE = lo then hi (gaps and breaks in the ink narrower than the window are bridged,
+ *              everything else keeps its extent), OCRS_MORPH_OPEN = hi then lo (hairs and bridges of ink narrower than the
+ *              window vanish; fused characters separate).
+ *
+ * ocrs_morph_params_default: close, rx 1, ry 1.
+ * ocrs_morph_params_check (host only): OCRS_ERR_INVALID_ARGUMENT for an op outside 0 .. 3, an rx or ry outside 0 .. 63, or
+ * both 0; the engine calls refuse the same, and a page with a side over 65535 or with more than 2^31 - 1 pixels.
+ * ocrs_engine_morph_pages serves n pages of any sizes, each with its own params[i] (ops and radii mix freely), in at most
+ * five launches for the whole batch on one stream; out_pages[n] receives the pages, out_infos[n] (may be NULL) the counts,
+ * out_masks[n] (may be NULL) per page a host uint8 [h][w], to be released with ocrs_buffer_free: bit 0 ink after (counted
+ * and under 0.0f), bit 1 the word changed.
+ * ocrs_engine_morph_page: params == NULL means the default. */
+#define OCRS_MORPH_THICKEN 0
+#define OCRS_MORPH_THIN 1
+#define OCRS_MORPH_CLOSE 2
+#define OCRS_MORPH_OPEN 3
+typedef struct ocrs_morph_params {
+    int32_t op;            /* OCRS_MORPH_* */
+    int32_t rx;            /* 0 .. 63: the window is (2 ry + 1) rows of (2 rx + 1) pixels */
+    int32_t ry;            /* 0 .. 63; not both 0 */
+} ocrs_morph_params;
+typedef struct ocrs_morph_info {
+    uint64_t counted;      /* pixels that are not NaN */
+    uint64_t changed;      /* counted pixels whose word changed */
+    uint64_t ink_before;   /* counted pixels under 0.0f on the source */
+    uint64_t ink_after;    /* counted pixels under 0.0f on the result */
+} ocrs_morph_info;
+OCRS_API ocrs_status ocrs_morph_params_default(ocrs_morph_params* out);
+OCRS_API ocrs_status ocrs_morph_params_check(const ocrs_morph_params* params);
+OCRS_API ocrs_status ocrs_engine_morph_page(const ocrs_engine* e, const ocrs_page* page, const ocrs_morph_params* params,
+                                            ocrs_page** out_page, uint8_t** out_mask, ocrs_morph_info* out_info);
+OCRS_API ocrs_status ocrs_engine_morph_pages(const ocrs_engine* e, const ocrs_page* const* pages, size_t n,
+                                             const ocrs_morph_params* params, ocrs_page** out_pages, uint8_t** out_masks,
+                                             ocrs_morph_info* out_infos);
+
 /* OcrEngine::detection_threshold (lib.rs:282-287). */
 OCRS_API float ocrs_engine_detection_threshold(const ocrs_engine* e);
 

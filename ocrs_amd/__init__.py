@@ -16,7 +16,7 @@ from ._lib import OcrsError, check, lib
 
 __all__ = ["OcrEngine", "OcrEngineParams", "ImageSource", "ImageSourceError", "DimOrder", "DecodeMethod", "Model",
            "OcrInput", "TextLine", "TextWord", "TextChar", "OcrsError", "DEFAULT_ALPHABET", "EngineGroup", "line_frame",
-           "Orientation", "orientation_vote", "unrotate_rects", "unrotate_lines", "work_size", "rescale_rects", "normalize_params", "rules_params", "speckle_params", "binarize_params"]
+           "Orientation", "orientation_vote", "unrotate_rects", "unrotate_lines", "work_size", "rescale_rects", "normalize_params", "rules_params", "speckle_params", "binarize_params", "morph_params"]
 
 # lib.rs:34 (with the EUR sign the comment at lib.rs:33 asks for)
 DEFAULT_ALPHABET = " 0123456789!\"#$%&'()*+,-./:;<=>?@[\\]^_`{|}~€ABCDEFGHIJKLMNOPQRSTUVWXYZabcdefghijklmnopqrstuvwxyz"
@@ -566,6 +566,33 @@ def _binarize_struct(radius=None, k=None, keep_ink=None, ink_level=None, paper=N
     return p
 
 
+MORPH_OPS = ("thicken", "thin", "close", "open")   # include/ocrs_amd.h OCRS_MORPH_*
+
+
+def morph_params(op=None, rx=None, ry=None):
+    """ocrs_morph_params as a dict: ocrs_morph_params_default (close, rx 1, ry 1) with the given fields
+    replaced (op by name; ry=None with an rx given means ry = rx), checked by ocrs_morph_params_check (host only)."""
+    p = _morph_struct(op, rx, ry)
+    check(lib().ocrs_morph_params_check(C.byref(p)))
+    return {"op": MORPH_OPS[p.op], "rx": int(p.rx), "ry": int(p.ry)}
+
+
+def _morph_struct(op=None, rx=None, ry=None):
+    p = _lib.MorphParams()
+    check(lib().ocrs_morph_params_default(C.byref(p)))
+    if op is not None:
+        if op not in MORPH_OPS:
+            raise ValueError("morph: op is one of %s, not %r" % (", ".join(MORPH_OPS), op))
+        p.op = MORPH_OPS.index(op)
+    if rx is not None:
+        p.rx = int(rx)   # out of range is the library's to refuse
+        if ry is None:
+            p.ry = int(rx)
+    if ry is not None:
+        p.ry = int(ry)
+    return p
+
+
 class Skew:
     """ocrs_engine_estimate_skew's outputs: angle (degrees; the page's content is turned counter-clockwise
     by it, deskew_map(.., angle) undoes it), scores (best coarse, runner-up coarse, at the angle), work_hw (the size the
@@ -1098,6 +1125,48 @@ class OcrEngine:
             res.append([infos[i].as_dict() for i in range(n)])
         return tuple(res) if mask or info else made
 
+    # ---- stroke repair
+    def morph(self, inp, op="close", rx=1, ry=None, mask=False, info=False):
+        """ocrs_engine_morph_page: the page with its ink thickened, thinned, closed or opened by running minima and maxima
+        over the window of 2 ry + 1 rows of 2 rx + 1 pixels around every pixel, clipped to the page, as a new resident page
+        of the same size (ry=None: ry = rx; 0 .. 63, not both 0).  The page is dark ink on light paper (normalize makes it
+        so).  "thicken": the darkest pixel of the window (ink grows); "thin": the lightest (ink shrinks); "close": thicken
+        then thin (gaps and breaks in the ink narrower than the window are bridged, everything else keeps its extent);
+        "open": thin then thicken (hairs and bridges of ink narrower than the window vanish, fused characters separate).
+        Every result pixel has the bits of some source pixel; NaN pixels are not counted and keep their bits.  mask=True:
+        also the uint8 [H, W] mask (bit 0 ink after, bit 1 changed); info=True: also {"counted", "changed", "ink_before",
+        "ink_after"}.  -> page, or (page[, mask][, info])."""
+        out = self.morph_batch([inp], [{"op": op, "rx": rx, "ry": ry}], mask=mask, info=info)
+        return tuple(o[0] for o in out) if mask or info else out[0]
+
+    def morph_batch(self, inputs, params=None, mask=False, info=False):
+        """ocrs_engine_morph_pages: pages of any sizes, each with its own parameters (a dict of morph's keywords, or None
+        for the default; one for all, or one per page; ops and radii mix freely), all passes for the whole batch on one
+        stream.  -> pages, or (pages[, masks][, infos])."""
+        n = len(inputs)
+        if params is None or isinstance(params, dict):
+            params = [params] * n
+        if len(params) != n:
+            raise ValueError("morph_batch: one parameter set per page")
+        pages = _page_array(inputs)
+        ps = (_lib.MorphParams * n)(*[_morph_struct(**(p or {})) for p in params])
+        out = (C.c_void_p * n)()
+        masks = (C.POINTER(C.c_uint8) * n)()
+        infos = (_lib.MorphInfo * n)()
+        check(lib().ocrs_engine_morph_pages(self._h, pages, C.c_size_t(n), ps, out, masks if mask else None, infos if info else None))
+        made = _new_inputs(out, n)
+        res = [made]
+        if mask:
+            got = []
+            for i in range(n):
+                h, w = made[i].shape[-2:]
+                got.append(np.ctypeslib.as_array(masks[i], shape=(h * w,)).reshape(h, w).copy())
+                lib().ocrs_buffer_free(masks[i])
+            res.append(got)
+        if info:
+            res.append([infos[i].as_dict() for i in range(n)])
+        return tuple(res) if mask or info else made
+
     # ---- page deskew (DESIGN.md §7.6)
     def skew_scores(self, inputs, sc_table):
         """ocrs_engine_skew_scores: the skew profile scores of pages of any sizes (a side at most 4096) at the angles of
@@ -1511,7 +1580,7 @@ class OcrEngine:
 
     # ---- lib.rs:290-300
     def get_text(self, inp, rectify=False, orientation=None, work_size=None, normalize=None, deskew=None, deskew_fill=0.5,
-                 perspective=None, perspective_fill=0.5, rules=None, despeckle=None, binarize=None):
+                 perspective=None, perspective_fill=0.5, rules=None, despeckle=None, binarize=None, morph=None):
         """rectify=True: the same sequence (detect_words, find_text_lines, recognize_text) with rectified crops.
         orientation: None reads the page as given; an int turns it by that many quarter turns counter-clockwise first
         (rotate); "auto" by what detect_orientation finds.
@@ -1536,6 +1605,9 @@ class OcrEngine:
         paper by the local threshold.  Applied after perspective and normalisation (it needs dark ink on
         light paper) and before despeckling, the turn, deskew and rule removal, whose threshold 0 is then the local
         decision.  Coordinates do not move.
+        morph: None reads the page as given; True or a dict of morph()'s keywords reads the page with its strokes repaired
+        (DESIGN.md §7.11).  Applied last, before detection: after despeckling, so that specks are not grown or welded to
+        text, and after rule removal, whose max_thickness a thickened rule would exceed.  Coordinates do not move.
         get_text returns text alone; callers that want boxes run the steps
         themselves and bring them back last with unproject_rects / unproject_lines."""
         if perspective is not None:
@@ -1553,6 +1625,8 @@ class OcrEngine:
             inp = self.deskew(inp, None if deskew == "auto" else float(deskew), fill=deskew_fill)[0]
         if rules is not None and rules is not False:
             inp = self.remove_rules(inp, **({} if rules is True else dict(rules)))
+        if morph is not None and morph is not False:
+            inp = self.morph(inp, **({} if morph is True else dict(morph)))
         if work_size is not None or rectify:
             lines = self.find_text_lines(inp, self.detect_words(inp, work_size=work_size))
             return "\n".join(str(t) for t in self.recognize_text(inp, lines, rectify=rectify) if t is not None)

@@ -93,6 +93,7 @@ DECLARED_SYMBOLS = [
     "ocrs_rules_params_default", "ocrs_rules_params_check", "ocrs_engine_remove_rules_page", "ocrs_engine_remove_rules_pages",
     "ocrs_speckle_params_default", "ocrs_speckle_params_check", "ocrs_engine_despeckle_page", "ocrs_engine_despeckle_pages",
     "ocrs_binarize_params_default", "ocrs_binarize_params_check", "ocrs_engine_binarize_page", "ocrs_engine_binarize_pages",
+    "ocrs_morph_params_default", "ocrs_morph_params_check", "ocrs_engine_morph_page", "ocrs_engine_morph_pages",
 ]
 
 ABI_VERSION = 6   # include/ocrs_amd.h OCRS_ABI_VERSION
@@ -151,6 +152,17 @@ class BinarizeInfo(C.Structure):   # include/ocrs_amd.h ocrs_binarize_info
 
     def as_dict(self):
         return {name: (float if name.endswith("_fill") else int)(getattr(self, name)) for name, _ in self._fields_}
+
+
+class MorphParams(C.Structure):   # include/ocrs_amd.h ocrs_morph_params
+    _fields_ = [("op", C.c_int32), ("rx", C.c_int32), ("ry", C.c_int32)]
+
+
+class MorphInfo(C.Structure):   # include/ocrs_amd.h ocrs_morph_info
+    _fields_ = [("counted", C.c_uint64), ("changed", C.c_uint64), ("ink_before", C.c_uint64), ("ink_after", C.c_uint64)]
+
+    def as_dict(self):
+        return {name: int(getattr(self, name)) for name, _ in self._fields_}
 
 
 class SkewParams(C.Structure):   # include/ocrs_amd.h ocrs_skew_params

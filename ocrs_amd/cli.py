@@ -133,6 +133,13 @@ def main(argv=None):
                     help="with --binarize: Sauvola's k, 0 to 1, rounded to 1/256 (default 0.34; 0 is the plain local mean)")
     ap.add_argument("--binarize-keep-ink", action="store_true",
                     help="with --binarize: ink keeps its own grey levels and only the paper is whitened")
+    ap.add_argument("--morph", default=None, metavar="OP[:RX[xRY]]",
+                    help="repair the strokes on the GPU before reading the page, by running minima and maxima over a window that "
+                         "reaches RX pixels to the left and right and RY up and down (0 to 63, not both 0; default 1; RY defaults to "
+                         "RX).  OP: close bridges gaps and breaks in the ink, open removes hairs and separates fused characters, "
+                         "thicken grows the ink, thin shrinks it; e.g. --morph close, --morph thicken:1x0 (applied last, after "
+                         "--despeckle and --remove-rules; the JSON gains \"morph\"; no reference counterpart; what a detector gains "
+                         "is uncalibrated: DESIGN.md 7.11)")
     ap.add_argument("-o", "--output")
     ap.add_argument("--debug", action="store_true")
     ap.add_argument("--text-map", action="store_true", help="write text-map.png (detect_text_pixels)")
@@ -157,6 +164,16 @@ def main(argv=None):
         ap.error("--speck-max-area, --speck-fill-holes and --speck-keep-near are only valid with --despeckle")
     if (args.binarize_radius is not None or args.binarize_k is not None or args.binarize_keep_ink) and not args.binarize:
         ap.error("--binarize-radius, --binarize-k and --binarize-keep-ink are only valid with --binarize")
+    morph_kw = None
+    if args.morph is not None:
+        import re
+
+        from . import MORPH_OPS
+        m = re.fullmatch(r"([a-z]+)(?::(\d+)(?:x(\d+))?)?", args.morph)
+        if not m or m.group(1) not in MORPH_OPS:
+            ap.error("--morph: OP[:RX[xRY]] with OP one of %s, e.g. close, close:2, thicken:1x0; not %r" % (", ".join(MORPH_OPS), args.morph))
+        rx = 1 if m.group(2) is None else int(m.group(2))
+        morph_kw = {"op": m.group(1), "rx": rx, "ry": rx if m.group(3) is None else int(m.group(3))}
     if args.perspective_fill is not None and args.perspective is None:
         ap.error("--perspective-fill is only valid with --perspective")
     if args.perspective is not None and args.perspective != "auto":
@@ -294,6 +311,19 @@ def main(argv=None):
                   "rules, %d kept where a stroke crosses; %d pixels of ink"
                   % (rules_info["overwritten"], rules_info["fill"], rules_info["paper_bin"], rules_info["counted"],
                      rules_info["h_removed"], rules_info["v_removed"], rules_info["kept"], rules_info["ink"]))
+    morph_info = None
+    if morph_kw is not None:   # from here on the page with its strokes repaired is the page; coordinates do not move
+        try:
+            inp, morph_info = engine.morph(inp, info=True, **morph_kw)
+        except OcrsError as e:
+            if e.status != 1:   # OCRS_ERR_INVALID_ARGUMENT: a parameter out of range
+                raise
+            ap.error("--morph: %s" % e)
+        morph_info = dict(morph_info, **morph_kw)
+        if args.debug:
+            print("Morph: %s over %d x %d: %d of %d counted pixels changed; %d pixels of ink before, %d after"
+                  % (morph_kw["op"], 2 * morph_kw["rx"] + 1, 2 * morph_kw["ry"] + 1, morph_info["changed"], morph_info["counted"],
+                     morph_info["ink_before"], morph_info["ink_after"]))
     tiled = False if args.tiled is None else True if args.tiled < 0 else args.tiled
     work_hw = None   # the size the detector sees the (turned) page at: DESIGN.md 7.3
     if args.work_scale is not None or args.work_max_side is not None:
@@ -342,7 +372,7 @@ def main(argv=None):
     if args.json:
         content = output.format_json_output(args.image, tuple(shape_hw), texts, confidence=args.confidence, word_boxes=word_boxes,
                                             orientation=None if turns is None else 90 * turns, normalize=norm_info, skew=skew, outline=outline,
-                                            rules=rules_info, despeckle=speckle_info, binarize=binarize_info)
+                                            rules=rules_info, despeckle=speckle_info, binarize=binarize_info, morph=morph_info)
     else:
         content = output.format_text_output(texts)
     if args.output:

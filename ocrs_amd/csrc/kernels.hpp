@@ -545,6 +545,47 @@ int64_t bin_row_blocks(int h);                    // blocks a page takes in the 
 // Pages of any mix of sizes and parameters, three launches on `s`; row_blocks and col_blocks are the sums over the pages.
 void binarize_pages(const BinDesc* d_descs, int n_pages, int row_blocks, int col_blocks, hipStream_t s);
 
+// ---- kernels_morph.hip ------------------------------------
+struct MorphInfo {       // what a page's stroke repair counted: the layout of ocrs_morph_info
+    uint64_t counted;    // pixels that are not NaN
+    uint64_t changed;    // counted pixels whose 32-bit word changed
+    uint64_t ink_before; // counted pixels under 0.0f on the source
+    uint64_t ink_after;  // counted pixels under 0.0f on the result
+};
+constexpr int MORPH_COUNTS = 4;       // 64-bit words of a block's record: the four counts of MorphInfo
+constexpr int MORPH_MAX_RADIUS = 63;
+constexpr int MORPH_OPS = 4;          // thicken (lo), thin (hi), close (lo, hi), open (hi, lo): OCRS_MORPH_*
+constexpr int MORPH_STRIP = 64;       // columns of a block of the vertical pass: a lane per column, one wave
+constexpr int MORPH_ROWS = 4;         // rows of a block of the horizontal pass: a wave per row
+constexpr int MORPH_SEG = 256;        // columns of a block of the horizontal pass
+struct MorphDesc {       // one page that is repaired: dst [h, w] from src [h, w], in one or two stages
+    const float* src;
+    float* dst;          // never overlaps src
+    float* mid;          // [h, w] the page between the stages of close and open; null for thicken and thin
+    uint32_t* keys;      // [h, w] the row extrema of the stage at hand as ordered keys (NaN: the empty key), at every pixel
+    unsigned long long* counts;  // [strips * segs, MORPH_COUNTS] what each block of the last vertical pass counted
+    MorphInfo* info;
+    uint8_t* mask_out;   // [h, w] the mask of include/ocrs_amd.h, or null
+    int32_t h, w;        // each 1 .. 65535, h * w < 2^31
+    int32_t block0;      // first block of this page in the vertical pass of stage 1: the sum of strips * segs before it
+    int32_t row_block0;  // ... in the horizontal pass of stage 1: the sum of row_blocks before it
+    int32_t block0_2;    // ... in the vertical pass of stage 2: pages of one stage take no blocks there
+    int32_t row_block0_2;   // ... in the horizontal pass of stage 2
+    int32_t strips, segs;   // ceil(w / MORPH_STRIP), ceil(h / seg_rows)
+    int32_t seg_rows;    // rows of a block of the vertical pass (morph_seg_rows): a multiple of 2 ry + 1
+    int32_t row_segs;    // ceil(w / MORPH_SEG)
+    int32_t rx, ry;      // 0 .. 63, not both 0
+    int32_t stages;      // 1 or 2
+    uint32_t flip[2];    // per stage: 0 for lo, ~0 for hi; the stage takes the least of key ^ flip
+};
+int morph_seg_rows(int h, int w, int ry);         // rows of a block of the vertical pass (host)
+int64_t morph_col_blocks(int h, int w, int ry);   // blocks a page takes in a vertical pass (host)
+int64_t morph_row_blocks(int h, int w);           // blocks a page takes in a horizontal pass (host)
+// Pages of any mix of sizes, ops and radii; at most five launches on `s`.  row_blocks[s] and col_blocks[s] are the sums over
+// the pages of stage s + 1; a page of one stage adds nothing to those of stage 2.  max_ry: the largest ry of the batch, by
+// which the vertical pass sizes its LDS.
+void morph_pages(const MorphDesc* d_descs, int n_pages, const int row_blocks[2], const int col_blocks[2], int max_ry, hipStream_t s);
+
 // kernels_peaks.hip
 void measure_peaks(double* mfma_tflops, double* copy_gbps);
 

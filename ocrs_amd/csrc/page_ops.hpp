@@ -1,6 +1,7 @@
 // Page operations: what the calls that make new resident pages out of resident pages share: quarter
 // turns (orient.cpp), resampling (resample.cpp), normalisation (normalize.cpp), the deskew warp (deskew.cpp), rule removal
-// (rules.cpp), despeckling (speckle.cpp), adaptive binarisation (binarize.cpp).  Not part of the public header.
+// (rules.cpp), despeckling (speckle.cpp), adaptive binarisation (binarize.cpp), stroke repair
+// (morph.cpp).  Not part of the public header.
 #pragma once
 #include <limits>
 #include <memory>
