@@ -974,6 +974,36 @@ class OcrEngine:
         o.quarter_turns = k.value
         return o
 
+    # ---- the page operations with parameters per page
+    def _page_op_batch(self, name, entry, params_cls, struct_of, info_cls, inputs, params, mask, info):
+        """<name>_batch: `entry` on the pages of `inputs`, page i with the params struct struct_of(**params[i]) (a dict of
+        keywords, or None for the default; `params` is one for all, or one per page).  mask: None for an entry point that
+        takes no masks.  -> pages, or (pages[, masks][, infos])."""
+        n = len(inputs)
+        if params is None or isinstance(params, dict):
+            params = [params] * n
+        if len(params) != n:
+            raise ValueError("%s_batch: one parameter set per page" % name)
+        pages = _page_array(inputs)
+        ps = (params_cls * n)(*[struct_of(**(p or {})) for p in params])
+        out = (C.c_void_p * n)()
+        masks = (C.POINTER(C.c_uint8) * n)()
+        infos = (info_cls * n)()
+        outputs = ([] if mask is None else [masks if mask else None]) + [infos if info else None]
+        check(entry(self._h, pages, C.c_size_t(n), ps, out, *outputs))
+        made = _new_inputs(out, n)
+        res = [made]
+        if mask:
+            got = []
+            for i in range(n):
+                h, w = made[i].shape[-2:]
+                got.append(np.ctypeslib.as_array(masks[i], shape=(h * w,)).reshape(h, w).copy())
+                lib().ocrs_buffer_free(masks[i])
+            res.append(got)
+        if info:
+            res.append([infos[i].as_dict() for i in range(n)])
+        return tuple(res) if mask or info else made
+
     # ---- page normalisation (DESIGN.md §7.4)
     def normalize(self, inp, tile=64, polarity="auto", flatten=True, levels=True, info=False):
         """ocrs_engine_normalize_page: the page with its background flattened, its levels stretched and its polarity made
@@ -987,18 +1017,8 @@ class OcrEngine:
         """ocrs_engine_normalize_pages: pages of any sizes, each with its own parameters (a dict of normalize's keywords, or
         None for the default; one for all, or one per page), all passes for the whole batch on one stream.  info=True: ->
         (pages, infos)."""
-        n = len(inputs)
-        if params is None or isinstance(params, dict):
-            params = [params] * n
-        if len(params) != n:
-            raise ValueError("normalize_batch: one parameter set per page")
-        pages = _page_array(inputs)
-        ps = (_lib.NormalizeParams * n)(*[_normalize_struct(**(p or {})) for p in params])
-        out = (C.c_void_p * n)()
-        infos = (_lib.NormalizeInfo * n)()
-        check(lib().ocrs_engine_normalize_pages(self._h, pages, C.c_size_t(n), ps, out, infos if info else None))
-        made = _new_inputs(out, n)
-        return (made, [infos[i].as_dict() for i in range(n)]) if info else made
+        return self._page_op_batch("normalize", lib().ocrs_engine_normalize_pages, _lib.NormalizeParams, _normalize_struct, _lib.NormalizeInfo,
+                                           inputs, params, None, info)
 
     # ---- ruled-line removal (DESIGN.md §7.8)
     def remove_rules(self, inp, min_length=96, max_thickness=8, margin=1, threshold=0.0, paper=None, mask=False, info=False):
@@ -1017,29 +1037,8 @@ class OcrEngine:
         """ocrs_engine_remove_rules_pages: pages of any sizes, each with its own parameters (a dict of remove_rules's keywords,
         or None for the default; one for all, or one per page), all passes for the whole batch on one stream.  -> pages, or
         (pages[, masks][, infos])."""
-        n = len(inputs)
-        if params is None or isinstance(params, dict):
-            params = [params] * n
-        if len(params) != n:
-            raise ValueError("remove_rules_batch: one parameter set per page")
-        pages = _page_array(inputs)
-        ps = (_lib.RulesParams * n)(*[_rules_struct(**(p or {})) for p in params])
-        out = (C.c_void_p * n)()
-        masks = (C.POINTER(C.c_uint8) * n)()
-        infos = (_lib.RulesInfo * n)()
-        check(lib().ocrs_engine_remove_rules_pages(self._h, pages, C.c_size_t(n), ps, out, masks if mask else None, infos if info else None))
-        made = _new_inputs(out, n)
-        res = [made]
-        if mask:
-            got = []
-            for i in range(n):
-                h, w = made[i].shape[-2:]
-                got.append(np.ctypeslib.as_array(masks[i], shape=(h * w,)).reshape(h, w).copy())
-                lib().ocrs_buffer_free(masks[i])
-            res.append(got)
-        if info:
-            res.append([infos[i].as_dict() for i in range(n)])
-        return tuple(res) if mask or info else made
+        return self._page_op_batch("remove_rules", lib().ocrs_engine_remove_rules_pages, _lib.RulesParams, _rules_struct, _lib.RulesInfo,
+                                           inputs, params, mask, info)
 
     # ---- despeckling (DESIGN.md §7.9)
     def despeckle(self, inp, max_area=4, max_hole=0, keep_near=0, threshold=0.0, paper=None, ink_level=None, mask=False, info=False):
@@ -1059,29 +1058,8 @@ class OcrEngine:
         """ocrs_engine_despeckle_pages: pages of any sizes, each with its own parameters (a dict of despeckle's keywords, or
         None for the default; one for all, or one per page), all passes for the whole batch on one stream.  -> pages, or
         (pages[, masks][, infos])."""
-        n = len(inputs)
-        if params is None or isinstance(params, dict):
-            params = [params] * n
-        if len(params) != n:
-            raise ValueError("despeckle_batch: one parameter set per page")
-        pages = _page_array(inputs)
-        ps = (_lib.SpeckleParams * n)(*[_speckle_struct(**(p or {})) for p in params])
-        out = (C.c_void_p * n)()
-        masks = (C.POINTER(C.c_uint8) * n)()
-        infos = (_lib.SpeckleInfo * n)()
-        check(lib().ocrs_engine_despeckle_pages(self._h, pages, C.c_size_t(n), ps, out, masks if mask else None, infos if info else None))
-        made = _new_inputs(out, n)
-        res = [made]
-        if mask:
-            got = []
-            for i in range(n):
-                h, w = made[i].shape[-2:]
-                got.append(np.ctypeslib.as_array(masks[i], shape=(h * w,)).reshape(h, w).copy())
-                lib().ocrs_buffer_free(masks[i])
-            res.append(got)
-        if info:
-            res.append([infos[i].as_dict() for i in range(n)])
-        return tuple(res) if mask or info else made
+        return self._page_op_batch("despeckle", lib().ocrs_engine_despeckle_pages, _lib.SpeckleParams, _speckle_struct, _lib.SpeckleInfo,
+                                           inputs, params, mask, info)
 
     # ---- adaptive binarisation (DESIGN.md §7.10)
     def binarize(self, inp, radius=15, k=0.34, keep_ink=False, ink_level=None, paper=None, mask=False, info=False):
@@ -1101,29 +1079,8 @@ class OcrEngine:
         """ocrs_engine_binarize_pages: pages of any sizes, each with its own parameters (a dict of binarize's keywords, or
         None for the default; one for all, or one per page), all passes for the whole batch on one stream.  -> pages, or
         (pages[, masks][, infos])."""
-        n = len(inputs)
-        if params is None or isinstance(params, dict):
-            params = [params] * n
-        if len(params) != n:
-            raise ValueError("binarize_batch: one parameter set per page")
-        pages = _page_array(inputs)
-        ps = (_lib.BinarizeParams * n)(*[_binarize_struct(**(p or {})) for p in params])
-        out = (C.c_void_p * n)()
-        masks = (C.POINTER(C.c_uint8) * n)()
-        infos = (_lib.BinarizeInfo * n)()
-        check(lib().ocrs_engine_binarize_pages(self._h, pages, C.c_size_t(n), ps, out, masks if mask else None, infos if info else None))
-        made = _new_inputs(out, n)
-        res = [made]
-        if mask:
-            got = []
-            for i in range(n):
-                h, w = made[i].shape[-2:]
-                got.append(np.ctypeslib.as_array(masks[i], shape=(h * w,)).reshape(h, w).copy())
-                lib().ocrs_buffer_free(masks[i])
-            res.append(got)
-        if info:
-            res.append([infos[i].as_dict() for i in range(n)])
-        return tuple(res) if mask or info else made
+        return self._page_op_batch("binarize", lib().ocrs_engine_binarize_pages, _lib.BinarizeParams, _binarize_struct, _lib.BinarizeInfo,
+                                           inputs, params, mask, info)
 
     # ---- stroke repair (DESIGN.md §7.11)
     def morph(self, inp, op="close", rx=1, ry=None, mask=False, info=False):
@@ -1143,29 +1100,8 @@ class OcrEngine:
         """ocrs_engine_morph_pages: pages of any sizes, each with its own parameters (a dict of morph's keywords, or None
         for the default; one for all, or one per page; ops and radii mix freely), all passes for the whole batch on one
         stream.  -> pages, or (pages[, masks][, infos])."""
-        n = len(inputs)
-        if params is None or isinstance(params, dict):
-            params = [params] * n
-        if len(params) != n:
-            raise ValueError("morph_batch: one parameter set per page")
-        pages = _page_array(inputs)
-        ps = (_lib.MorphParams * n)(*[_morph_struct(**(p or {})) for p in params])
-        out = (C.c_void_p * n)()
-        masks = (C.POINTER(C.c_uint8) * n)()
-        infos = (_lib.MorphInfo * n)()
-        check(lib().ocrs_engine_morph_pages(self._h, pages, C.c_size_t(n), ps, out, masks if mask else None, infos if info else None))
-        made = _new_inputs(out, n)
-        res = [made]
-        if mask:
-            got = []
-            for i in range(n):
-                h, w = made[i].shape[-2:]
-                got.append(np.ctypeslib.as_array(masks[i], shape=(h * w,)).reshape(h, w).copy())
-                lib().ocrs_buffer_free(masks[i])
-            res.append(got)
-        if info:
-            res.append([infos[i].as_dict() for i in range(n)])
-        return tuple(res) if mask or info else made
+        return self._page_op_batch("morph", lib().ocrs_engine_morph_pages, _lib.MorphParams, _morph_struct, _lib.MorphInfo,
+                                           inputs, params, mask, info)
 
     # ---- page deskew (DESIGN.md §7.6)
     def skew_scores(self, inputs, sc_table):

@@ -38,29 +38,17 @@ uint32_t fill_bits(float given, float otherwise) {
     return u;
 }
 
-struct FreeHost {
-    void operator()(uint8_t* p) const { free(p); }
-};
-
 // every page binarised as a new page of its own, all passes for all pages on `ws`'s stream; waits for them
 PageBatch<k::BinDesc> binarize(Workspace& ws, const ocrs_page* const* pages, size_t n, const ocrs_binarize_params* params,
                                uint8_t** out_masks, ocrs_binarize_info* out_infos) {
     PageBatch<k::BinDesc> batch{"binarize"};
     if (n == 0) return batch;
-    for (size_t i = 0; i < n; i++) {
-        check_page_side("binarize", pages[i]);
-        if ((int64_t)pages[i]->h * pages[i]->w > (int64_t)std::numeric_limits<int32_t>::max())
-            fail(OCRS_ERR_INVALID_ARGUMENT, "binarize: a page of %d x %d: at most 2^31 - 1 pixels", pages[i]->h, pages[i]->w);
-    }
+    check_pages_in("binarize", pages, n, true);
     int64_t row_blocks = 0;
     for (size_t i = 0; i < n; i++) {
         const ocrs_page* p = pages[i];
         const ocrs_binarize_params& q = params[i];
-        k::BinDesc& d = batch.add(p->h, p->w, k::bin_col_blocks(p->h, p->w, q.radius));
-        d.src = p->grey.as<float>();
-        d.dst = batch.made.back()->grey.as<float>();
-        d.h = p->h;
-        d.w = p->w;
+        k::BinDesc& d = batch.add_like(p, k::bin_col_blocks(p->h, p->w, q.radius));
         d.row_block0 = (int32_t)row_blocks;
         row_blocks += k::bin_row_blocks(p->h);
         if (row_blocks > std::numeric_limits<int32_t>::max()) fail(OCRS_ERR_CAPACITY, "binarize: the pages of one call take more than 2^31 blocks");
@@ -74,29 +62,11 @@ PageBatch<k::BinDesc> binarize(Workspace& ws, const ocrs_page* const* pages, siz
         d.paper_bits = fill_bits(q.paper, 0.5f);
     }
     // per page: the row sums of its pixels, its blocks' counts and its info; the byte mask when it is asked for
-    unsigned long long* d_counts = ws.alloc_n<unsigned long long>((size_t)batch.blocks * k::BIN_COUNTS);
-    k::BinInfo* d_info = ws.alloc_n<k::BinInfo>(n);
-    std::vector<std::unique_ptr<uint8_t, FreeHost>> host_masks;
-    for (size_t i = 0; i < n; i++) {
-        k::BinDesc& d = batch.descs[i];
-        const size_t px = (size_t)d.h * d.w;
-        d.sums = ws.alloc_n<uint32_t>(2 * px);
-        d.counts = d_counts + (size_t)d.block0 * k::BIN_COUNTS;
-        d.info = d_info + i;
-        if (out_masks) {
-            d.mask_out = ws.alloc_n<uint8_t>(px);
-            host_masks.emplace_back(static_cast<uint8_t*>(malloc(px)));
-            if (!host_masks.back()) throw std::bad_alloc();
-        }
-    }
-    batch.run(ws, [&](const k::BinDesc* d_descs, int n_pages, int blocks) {
+    batch.carve_outputs(ws, k::BIN_COUNTS, out_masks != nullptr);
+    for (k::BinDesc& d : batch.descs) d.sums = ws.alloc_n<uint32_t>(2 * (size_t)d.h * d.w);
+    batch.run_outputs(ws, out_infos, out_masks, [&](const k::BinDesc* d_descs, int n_pages, int blocks) {
         k::binarize_pages(d_descs, n_pages, (int)row_blocks, blocks, ws.s());
-        OCRS_HIP(hipGetLastError());   // of the launches, before the downloads are queued
-        if (out_infos) ws.download(out_infos, d_info, n * sizeof(k::BinInfo));
-        for (size_t i = 0; i < host_masks.size(); i++)
-            ws.download(host_masks[i].get(), batch.descs[i].mask_out, (size_t)batch.descs[i].h * batch.descs[i].w);
     });
-    for (size_t i = 0; i < host_masks.size(); i++) out_masks[i] = host_masks[i].release();
     return batch;
 }
 
@@ -116,31 +86,20 @@ ocrs_status ocrs_binarize_params_default(ocrs_binarize_params* out) {
 }
 
 ocrs_status ocrs_binarize_params_check(const ocrs_binarize_params* params) {
-    return guarded([&] {
-        if (!params) fail(OCRS_ERR_INVALID_ARGUMENT, "null argument");
-        check_params(*params);
-    });
+    return params_check(params, check_params);
 }
 
 ocrs_status ocrs_engine_binarize_pages(const ocrs_engine* e, const ocrs_page* const* pages, size_t n, const ocrs_binarize_params* params,
                                        ocrs_page** out_pages, uint8_t** out_masks, ocrs_binarize_info* out_infos) {
-    return guarded_engine(e, [&] {
-        if (!e || (n > 0 && (!pages || !params || !out_pages))) fail(OCRS_ERR_INVALID_ARGUMENT, "null argument");
-        check_pages_on(e, pages, n);
-        for (size_t i = 0; i < n; i++) check_params(params[i]);
-        Workspace ws;
-        binarize(ws, pages, n, params, out_masks, out_infos).release_into(out_pages);
-    });
+    return pages_call(e, pages, n, params, check_params, out_pages,
+                      [&](Workspace& ws) { return binarize(ws, pages, n, params, out_masks, out_infos); });
 }
 
 ocrs_status ocrs_engine_binarize_page(const ocrs_engine* e, const ocrs_page* page, const ocrs_binarize_params* params, ocrs_page** out_page,
                                       uint8_t** out_mask, ocrs_binarize_info* out_info) {
-    ocrs_binarize_params def;
-    if (!params) {
-        ocrs_binarize_params_default(&def);
-        params = &def;
-    }
-    return ocrs_engine_binarize_pages(e, &page, 1, params, out_page, out_mask, out_info);
+    return page_call(params, ocrs_binarize_params_default, [&](const ocrs_binarize_params* q) {
+        return ocrs_engine_binarize_pages(e, &page, 1, q, out_page, out_mask, out_info);
+    });
 }
 
 }  // extern "C"

@@ -29,6 +29,7 @@
 // the same for every thread of the block (it depends on the page width alone); shuffles are reached by whole waves.
 #include "find_desc.hpp"
 #include "kernels.hpp"
+#include "page_device.hpp"
 
 namespace ocrs {
 namespace k {
@@ -39,13 +40,6 @@ constexpr int BIN_RING = 512;   // prefixes a wave keeps: those of the 2 rounds 
 static_assert(BIN_WAVES == BIN_ROWS && BIN_THREADS == BIN_STRIP && BIN_COUNTS == 2 * BIN_WAVES, "the layout of a block");
 static_assert(2 * 64 + 64 + BIN_MAX_RADIUS + 1 <= BIN_RING, "the ring holds what a delayed round reads");
 
-typedef unsigned long long u64;
-// The pointers come out of a descriptor in memory, where the compiler cannot see their address space: say it, so that
-// the accesses are global_ instructions and not flat_ ones.
-typedef __attribute__((address_space(1))) float gfloat;
-typedef __attribute__((address_space(1))) uint32_t gword;
-typedef __attribute__((address_space(1))) uint8_t gbyte;
-typedef __attribute__((address_space(1))) u64 gu64;
 typedef __attribute__((address_space(1))) BinInfo ginfo;
 typedef uint32_t uint2v __attribute__((ext_vector_type(2)));
 typedef __attribute__((address_space(1))) uint2v gpair;
@@ -65,46 +59,12 @@ int64_t bin_col_blocks(int h, int w, int radius) {
 }
 int64_t bin_row_blocks(int h) { return (h + BIN_ROWS - 1) / BIN_ROWS; }
 
-// block b of pass 1 belongs to the last descriptor whose row_block0 is <= b (find_desc.hpp, on the other prefix)
-__device__ __forceinline__ int find_row_desc(const BinDesc* __restrict__ descs, int n, int b) {
-    int lo = 0, hi = n - 1;
-    while (lo < hi) {
-        const int mid = (lo + hi + 1) >> 1;
-        if (descs[mid].row_block0 <= b) lo = mid;
-        else hi = mid - 1;
-    }
-    return lo;
-}
-
-__device__ __forceinline__ u64 shfl_xor64(u64 v, int mask) {
-    const int lo = __shfl_xor((int)(uint32_t)v, mask), hi = __shfl_xor((int)(uint32_t)(v >> 32), mask);
-    return (u64)(uint32_t)lo | ((u64)(uint32_t)hi << 32);
-}
-
-// sum over the wave; all 64 lanes call it together
-__device__ __forceinline__ u64 wave_sum(u64 v) {
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) v += shfl_xor64(v, d);
-    return v;
-}
-
-__device__ __forceinline__ float clamp01(float a) { return a < 0.0f ? 0.0f : (a > 1.0f ? 1.0f : a); }   // NaN stays
-
-// the bin of a grey level (§7.4); -1: NaN, not counted
-__device__ __forceinline__ int bin_of(float g) {
-    const float t = g * 256.0f;
-    if (t != t) return -1;
-    float f = floorf(t);
-    f = f < 0.0f ? 0.0f : (f > 255.0f ? 255.0f : f);
-    return (int)f;
-}
-
 // ---- pass 1
 __global__ void __launch_bounds__(BIN_THREADS)
 bin_rows_kernel(const BinDesc* __restrict__ descs, int n_pages) {
     __shared__ uint32_t ring[BIN_WAVES][3][BIN_RING];   // prefix i of the row (the sums of pixels 0 .. i - 1) at i % BIN_RING
     const int b = (int)blockIdx.x, tid = (int)threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const BinDesc d = descs[find_row_desc(descs, n_pages, b)];
+    const BinDesc d = descs[find_desc(descs, n_pages, b, &BinDesc::row_block0)];
     const int h = d.h, w = d.w, r = d.radius;
     const int y = (b - d.row_block0) * BIN_ROWS + wave;
     const bool row = y < h;

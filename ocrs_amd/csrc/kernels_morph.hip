@@ -36,6 +36,7 @@
 // morph_rows_kernel alone, in loops whose trip count depends on the page's rx: the same for every thread of the block.
 #include "find_desc.hpp"
 #include "kernels.hpp"
+#include "page_device.hpp"
 
 namespace ocrs {
 namespace k {
@@ -52,12 +53,6 @@ static_assert(MORPH_SEG % 64 == 0 && MORPH_SEG + 2 * MORPH_MAX_RADIUS <= MORPH_S
 static_assert(MORPH_STRIP == 64, "a block of the vertical pass is one wave");
 static_assert(MORPH_WINDOW * MORPH_STRIP * 4 <= 64 * 1024, "the suffix array fits the static LDS of a block");
 
-typedef unsigned long long u64;
-// The pointers come out of a descriptor in memory, where the compiler cannot see their address space: say it, so that
-// the accesses are global_ instructions and not flat_ ones.
-typedef __attribute__((address_space(1))) uint32_t gword;
-typedef __attribute__((address_space(1))) uint8_t gbyte;
-typedef __attribute__((address_space(1))) u64 gu64;
 typedef __attribute__((address_space(1))) MorphInfo ginfo;
 
 int morph_seg_rows(int h, int w, int ry) {
@@ -80,7 +75,9 @@ int64_t morph_col_blocks(int h, int w, int ry) {
 }
 int64_t morph_row_blocks(int h, int w) { return (int64_t)((h + MORPH_ROWS - 1) / MORPH_ROWS) * ((w + MORPH_SEG - 1) / MORPH_SEG); }
 
-// block b belongs to the last descriptor whose prefix `first` is <= b (find_desc.hpp, on another prefix)
+// block b belongs to the last descriptor whose prefix `first` is <= b.  This is find_desc.hpp's member-pointer form, kept
+// as a function of its own: with both searches of morph_cols_kernel going through find_desc the compiler folds them into
+// one loop and the kernel's code changes, which would need measuring again.
 __device__ __forceinline__ int find_by(const MorphDesc* __restrict__ descs, int n, int b, int32_t MorphDesc::*first) {
     int lo = 0, hi = n - 1;
     while (lo < hi) {
@@ -98,7 +95,7 @@ __device__ __forceinline__ uint32_t word_of(uint32_t k) { return (k & 0x80000000
 __device__ __forceinline__ bool is_dark_word(uint32_t w) { return w > 0x80000000u; }
 __device__ __forceinline__ uint32_t least(uint32_t a, uint32_t b) { return a < b ? a : b; }
 
-// sum over the wave; all 64 lanes call it together
+// sum over the wave of 32-bit counts (page_device.hpp has the 64-bit one); all 64 lanes call it together
 __device__ __forceinline__ uint32_t wave_sum(uint32_t v) {
 #pragma unroll
     for (int d = 32; d >= 1; d >>= 1) v += (uint32_t)__shfl_xor((int)v, d);

@@ -33,6 +33,7 @@
 #include "bilinear.hpp"
 #include "find_desc.hpp"
 #include "kernels.hpp"
+#include "page_device.hpp"
 
 namespace ocrs {
 namespace k {
@@ -40,12 +41,6 @@ namespace k {
 constexpr int NORM_THREADS = 256;
 constexpr int NORM_WAVES = NORM_THREADS / 64;
 
-// The pointers come out of a descriptor in memory, where the compiler cannot see their address space: say it, so that
-// the accesses are global_ instructions and not flat_ ones.
-typedef __attribute__((address_space(1))) float gfloat;
-typedef __attribute__((address_space(1))) uint32_t gword;
-typedef __attribute__((address_space(1))) uint8_t gbyte;
-typedef __attribute__((address_space(1))) unsigned long long gu64;
 typedef __attribute__((address_space(1))) NormState gstate;
 // a tile's record (NormDesc::tiles)
 __device__ __forceinline__ uint32_t tile_word(int white_light, int white_dark, bool present) {
@@ -53,29 +48,6 @@ __device__ __forceinline__ uint32_t tile_word(int white_light, int white_dark, b
 }
 typedef float float4v __attribute__((ext_vector_type(4)));
 typedef __attribute__((address_space(1))) float4v gquad;
-
-__device__ __forceinline__ float clamp01(float a) { return a < 0.0f ? 0.0f : (a > 1.0f ? 1.0f : a); }   // NaN stays
-
-// the bin of a grey level or of u; -1: NaN, not counted
-__device__ __forceinline__ int bin_of(float g) {
-    const float t = g * 256.0f;
-    if (t != t) return -1;
-    float f = floorf(t);
-    f = f < 0.0f ? 0.0f : (f > 255.0f ? 255.0f : f);
-    return (int)f;
-}
-
-// One bin per lane (-1: none) into this wave's histogram, runs of equal bins merged.  All 64 lanes call it together.
-__device__ __forceinline__ void hist_add(uint32_t* __restrict__ wave_hist, int bin, int lane) {
-    const int left = __shfl_up(bin, 1);
-    const bool head = lane == 0 || left != bin;
-    const unsigned long long heads = __ballot(head);
-    if (head && bin >= 0) {
-        const unsigned long long rest = lane == 63 ? 0ull : heads >> (lane + 1);
-        const int run = rest ? __builtin_ctzll(rest) + 1 : 64 - lane;
-        atomicAdd(&wave_hist[bin], (uint32_t)run);
-    }
-}
 
 // inclusive scan of one value per thread over the block's 256 threads; *total = the sum.  Holds two barriers.
 template <class T>

@@ -38,6 +38,7 @@
 // every thread of every block reaches them; shuffles and ballots are reached by whole waves.
 #include "find_desc.hpp"
 #include "kernels.hpp"
+#include "page_device.hpp"
 
 namespace ocrs {
 namespace k {
@@ -46,13 +47,6 @@ constexpr int RULES_THREADS = 256;
 constexpr int RULES_WAVES = RULES_THREADS / 64;
 static_assert(RULES_WAVES == 4 && RULES_COUNTS == 16, "the layout of a block's counts");
 
-typedef unsigned long long u64;
-// The pointers come out of a descriptor in memory, where the compiler cannot see their address space: say it, so that
-// the accesses are global_ instructions and not flat_ ones.
-typedef __attribute__((address_space(1))) float gfloat;
-typedef __attribute__((address_space(1))) uint32_t gword;
-typedef __attribute__((address_space(1))) uint8_t gbyte;
-typedef __attribute__((address_space(1))) u64 gu64;
 typedef __attribute__((address_space(1))) RulesInfo ginfo;
 typedef uint32_t uint4v __attribute__((ext_vector_type(4)));
 typedef __attribute__((address_space(1))) uint4v gquadw;
@@ -77,11 +71,6 @@ __device__ __forceinline__ Masks masks_of(const RulesDesc& d) {
     return m;
 }
 
-__device__ __forceinline__ u64 shfl_xor64(u64 v, int mask) {
-    const int lo = __shfl_xor((int)(uint32_t)v, mask), hi = __shfl_xor((int)(uint32_t)(v >> 32), mask);
-    return (u64)(uint32_t)lo | ((u64)(uint32_t)hi << 32);
-}
-
 // A 64 x 64 bit matrix, row r in lane r (bit c = column c) -> its transpose, row c in lane c.  All 64 lanes call it together.
 __device__ __forceinline__ u64 transpose64(u64 a, int lane) {
     const u64 keep[6] = {0x00000000FFFFFFFFull, 0x0000FFFF0000FFFFull, 0x00FF00FF00FF00FFull,
@@ -95,13 +84,6 @@ __device__ __forceinline__ u64 transpose64(u64 a, int lane) {
     return a;
 }
 
-// sum over the wave; all 64 lanes call it together
-__device__ __forceinline__ u64 wave_sum(u64 v) {
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) v += shfl_xor64(v, d);
-    return v;
-}
-
 // What a page's blocks counted, a record of RULES_COUNTS words (one cache line) per block, every word of it written by
 // plain stores: [RC_INK + wave] pass 1, [RC_H + wave] and [RC_V + wave] pass 6, [RC_D] and [RC_K] pass 7.  Pass 8 adds them up.
 // (With every wave or block adding into a word of the page's info instead, hundreds of atomics to a page's one cache line,
@@ -111,29 +93,6 @@ __device__ __forceinline__ gu64* counts_of(const RulesDesc& d, int tile) { retur
 
 __device__ __forceinline__ void count_add(gu64* at, u64 v) {
     if (v) __hip_atomic_fetch_add(at, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
-__device__ __forceinline__ float clamp01(float a) { return a < 0.0f ? 0.0f : (a > 1.0f ? 1.0f : a); }   // NaN stays
-
-// the bin of a grey level (§7.4); -1: NaN, not counted
-__device__ __forceinline__ int bin_of(float g) {
-    const float t = g * 256.0f;
-    if (t != t) return -1;
-    float f = floorf(t);
-    f = f < 0.0f ? 0.0f : (f > 255.0f ? 255.0f : f);
-    return (int)f;
-}
-
-// One bin per lane (-1: none) into this wave's histogram, runs of equal bins merged (§7.4).  All 64 lanes call it together.
-__device__ __forceinline__ void hist_add(uint32_t* __restrict__ wave_hist, int bin, int lane) {
-    const int left = __shfl_up(bin, 1);
-    const bool head = lane == 0 || left != bin;
-    const u64 heads = __ballot(head);
-    if (head && bin >= 0) {
-        const u64 rest = lane == 63 ? 0ull : heads >> (lane + 1);
-        const int run = rest ? __builtin_ctzll(rest) + 1 : 64 - lane;
-        atomicAdd(&wave_hist[bin], (uint32_t)run);
-    }
 }
 
 // ---- pass 1

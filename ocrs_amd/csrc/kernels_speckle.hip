@@ -43,6 +43,7 @@
 // by whole waves.
 #include "find_desc.hpp"
 #include "kernels.hpp"
+#include "page_device.hpp"
 
 namespace ocrs {
 namespace k {
@@ -52,14 +53,7 @@ constexpr int SPECKLE_WAVES = SPECKLE_THREADS / 64;
 constexpr int SPECKLE_ROWS = 64 / SPECKLE_WAVES;   // of a tile, per wave
 static_assert(SPECKLE_WAVES == 4 && SPECKLE_COUNTS == 32, "the layout of a block's counts");
 
-typedef unsigned long long u64;
-// The pointers come out of a descriptor in memory, where the compiler cannot see their address space: say it, so that
-// the accesses are global_ instructions and not flat_ ones.
-typedef __attribute__((address_space(1))) float gfloat;
-typedef __attribute__((address_space(1))) uint32_t gword;
 typedef __attribute__((address_space(1))) int32_t gint;
-typedef __attribute__((address_space(1))) uint8_t gbyte;
-typedef __attribute__((address_space(1))) u64 gu64;
 typedef __attribute__((address_space(1))) SpeckleInfo ginfo;
 typedef uint32_t uint4v __attribute__((ext_vector_type(4)));
 typedef int32_t int4v __attribute__((ext_vector_type(4)));
@@ -75,45 +69,10 @@ __device__ __forceinline__ gu64* mask_of(const SpeckleDesc& d, int m) {
     return (gu64*)(uintptr_t)d.masks + (size_t)m * (size_t)d.h * (size_t)d.ww;
 }
 
-__device__ __forceinline__ u64 shfl_xor64(u64 v, int mask) {
-    const int lo = __shfl_xor((int)(uint32_t)v, mask), hi = __shfl_xor((int)(uint32_t)(v >> 32), mask);
-    return (u64)(uint32_t)lo | ((u64)(uint32_t)hi << 32);
-}
-
-// sum over the wave; all 64 lanes call it together
-__device__ __forceinline__ u64 wave_sum(u64 v) {
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) v += shfl_xor64(v, d);
-    return v;
-}
-
 // What a page's blocks counted in pass 7, a record of SPECKLE_COUNTS words per block, [wave][8], every word of it written by
 // plain stores; pass 8 adds them up.  (Atomics into one cache line per page cost the rule removal 2.4 to 6 times: §7.8.)
 enum { SC_SPECKS = 0, SC_KEPT, SC_SPECK_PX, SC_KEPT_PX, SC_HOLES, SC_HOLE_PX, SC_PER_WAVE = 8 };
 __device__ __forceinline__ gu64* counts_of(const SpeckleDesc& d, int tile) { return (gu64*)(uintptr_t)d.counts + (size_t)tile * SPECKLE_COUNTS; }
-
-__device__ __forceinline__ float clamp01(float a) { return a < 0.0f ? 0.0f : (a > 1.0f ? 1.0f : a); }   // NaN stays
-
-// the bin of a grey level (§7.4); -1: NaN, not counted
-__device__ __forceinline__ int bin_of(float g) {
-    const float t = g * 256.0f;
-    if (t != t) return -1;
-    float f = floorf(t);
-    f = f < 0.0f ? 0.0f : (f > 255.0f ? 255.0f : f);
-    return (int)f;
-}
-
-// One bin per lane (-1: none) into this wave's histogram, runs of equal bins merged (§7.4).  All 64 lanes call it together.
-__device__ __forceinline__ void hist_add(uint32_t* __restrict__ wave_hist, int bin, int lane) {
-    const int left = __shfl_up(bin, 1);
-    const bool head = lane == 0 || left != bin;
-    const u64 heads = __ballot(head);
-    if (head && bin >= 0) {
-        const u64 rest = lane == 63 ? 0ull : heads >> (lane + 1);
-        const int run = rest ? __builtin_ctzll(rest) + 1 : 64 - lane;
-        atomicAdd(&wave_hist[bin], (uint32_t)run);
-    }
-}
 
 // ---- the union-find forest: labels are page-local pixel indices, a root is its component's raster-first pixel
 __device__ __forceinline__ int uf_find(gint* L, int x) {

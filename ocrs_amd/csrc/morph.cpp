@@ -29,20 +29,12 @@ void check_params(const ocrs_morph_params& p) {
     if (p.rx == 0 && p.ry == 0) fail(OCRS_ERR_INVALID_ARGUMENT, "morph: rx and ry are both 0: the window is the pixel");
 }
 
-struct FreeHost {
-    void operator()(uint8_t* p) const { free(p); }
-};
-
 // every page repaired as a new page of its own, all passes for all pages on `ws`'s stream; waits for them
 PageBatch<k::MorphDesc> morph(Workspace& ws, const ocrs_page* const* pages, size_t n, const ocrs_morph_params* params, uint8_t** out_masks,
                               ocrs_morph_info* out_infos) {
     PageBatch<k::MorphDesc> batch{"morph"};
     if (n == 0) return batch;
-    for (size_t i = 0; i < n; i++) {
-        check_page_side("morph", pages[i]);
-        if ((int64_t)pages[i]->h * pages[i]->w > (int64_t)std::numeric_limits<int32_t>::max())
-            fail(OCRS_ERR_INVALID_ARGUMENT, "morph: a page of %d x %d: at most 2^31 - 1 pixels", pages[i]->h, pages[i]->w);
-    }
+    check_pages_in("morph", pages, n, true);
     // the stages of an op: lo takes the least key, hi the greatest, which is the least of the flipped keys
     constexpr uint32_t LO = 0u, HI = 0xffffffffu;
     static const uint32_t flips[k::MORPH_OPS][2] = {{LO, LO}, {HI, HI}, {LO, HI}, {HI, LO}};
@@ -52,11 +44,7 @@ PageBatch<k::MorphDesc> morph(Workspace& ws, const ocrs_page* const* pages, size
         const ocrs_page* p = pages[i];
         const ocrs_morph_params& q = params[i];
         const int64_t cols = k::morph_col_blocks(p->h, p->w, q.ry), rows = k::morph_row_blocks(p->h, p->w);
-        k::MorphDesc& d = batch.add(p->h, p->w, cols);
-        d.src = p->grey.as<float>();
-        d.dst = batch.made.back()->grey.as<float>();
-        d.h = p->h;
-        d.w = p->w;
+        k::MorphDesc& d = batch.add_like(p, cols);
         d.stages = q.op == OCRS_MORPH_CLOSE || q.op == OCRS_MORPH_OPEN ? 2 : 1;
         d.row_block0 = (int32_t)row_blocks[0];
         d.row_block0_2 = (int32_t)row_blocks[1];
@@ -79,31 +67,16 @@ PageBatch<k::MorphDesc> morph(Workspace& ws, const ocrs_page* const* pages, size
     }
     // per page: the row extrema of the stage at hand, the page between two stages, its blocks' counts and its info; the
     // byte mask when it is asked for
-    unsigned long long* d_counts = ws.alloc_n<unsigned long long>((size_t)batch.blocks * k::MORPH_COUNTS);
-    k::MorphInfo* d_info = ws.alloc_n<k::MorphInfo>(n);
-    std::vector<std::unique_ptr<uint8_t, FreeHost>> host_masks;
-    for (size_t i = 0; i < n; i++) {
-        k::MorphDesc& d = batch.descs[i];
+    batch.carve_outputs(ws, k::MORPH_COUNTS, out_masks != nullptr);
+    for (k::MorphDesc& d : batch.descs) {
         const size_t px = (size_t)d.h * d.w;
         d.keys = ws.alloc_n<uint32_t>(px);
         d.mid = d.stages == 2 ? ws.alloc_n<float>(px) : nullptr;
-        d.counts = d_counts + (size_t)d.block0 * k::MORPH_COUNTS;
-        d.info = d_info + i;
-        if (out_masks) {
-            d.mask_out = ws.alloc_n<uint8_t>(px);
-            host_masks.emplace_back(static_cast<uint8_t*>(malloc(px)));
-            if (!host_masks.back()) throw std::bad_alloc();
-        }
     }
-    batch.run(ws, [&](const k::MorphDesc* d_descs, int n_pages, int blocks) {
+    batch.run_outputs(ws, out_infos, out_masks, [&](const k::MorphDesc* d_descs, int n_pages, int blocks) {
         const int rows[2] = {(int)row_blocks[0], (int)row_blocks[1]}, cols[2] = {blocks, (int)col_blocks2};
         k::morph_pages(d_descs, n_pages, rows, cols, max_ry, ws.s());
-        OCRS_HIP(hipGetLastError());   // of the launches, before the downloads are queued
-        if (out_infos) ws.download(out_infos, d_info, n * sizeof(k::MorphInfo));
-        for (size_t i = 0; i < host_masks.size(); i++)
-            ws.download(host_masks[i].get(), batch.descs[i].mask_out, (size_t)batch.descs[i].h * batch.descs[i].w);
     });
-    for (size_t i = 0; i < host_masks.size(); i++) out_masks[i] = host_masks[i].release();
     return batch;
 }
 
@@ -121,31 +94,20 @@ ocrs_status ocrs_morph_params_default(ocrs_morph_params* out) {
 }
 
 ocrs_status ocrs_morph_params_check(const ocrs_morph_params* params) {
-    return guarded([&] {
-        if (!params) fail(OCRS_ERR_INVALID_ARGUMENT, "null argument");
-        check_params(*params);
-    });
+    return params_check(params, check_params);
 }
 
 ocrs_status ocrs_engine_morph_pages(const ocrs_engine* e, const ocrs_page* const* pages, size_t n, const ocrs_morph_params* params,
                                     ocrs_page** out_pages, uint8_t** out_masks, ocrs_morph_info* out_infos) {
-    return guarded_engine(e, [&] {
-        if (!e || (n > 0 && (!pages || !params || !out_pages))) fail(OCRS_ERR_INVALID_ARGUMENT, "null argument");
-        check_pages_on(e, pages, n);
-        for (size_t i = 0; i < n; i++) check_params(params[i]);
-        Workspace ws;
-        morph(ws, pages, n, params, out_masks, out_infos).release_into(out_pages);
-    });
+    return pages_call(e, pages, n, params, check_params, out_pages,
+                      [&](Workspace& ws) { return morph(ws, pages, n, params, out_masks, out_infos); });
 }
 
 ocrs_status ocrs_engine_morph_page(const ocrs_engine* e, const ocrs_page* page, const ocrs_morph_params* params, ocrs_page** out_page,
                                    uint8_t** out_mask, ocrs_morph_info* out_info) {
-    ocrs_morph_params def;
-    if (!params) {
-        ocrs_morph_params_default(&def);
-        params = &def;
-    }
-    return ocrs_engine_morph_pages(e, &page, 1, params, out_page, out_mask, out_info);
+    return page_call(params, ocrs_morph_params_default, [&](const ocrs_morph_params* q) {
+        return ocrs_engine_morph_pages(e, &page, 1, q, out_page, out_mask, out_info);
+    });
 }
 
 }  // extern "C"

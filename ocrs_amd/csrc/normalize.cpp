@@ -34,16 +34,12 @@ PageBatch<k::NormDesc> normalize_pages(Workspace& ws, const ocrs_page* const* pa
                                        ocrs_normalize_info* out_info) {
     PageBatch<k::NormDesc> batch{"normalize"};
     if (n == 0) return batch;
-    for (size_t i = 0; i < n; i++) check_page_side("normalize", pages[i]);
+    check_pages_in("normalize", pages, n, false);
     for (size_t i = 0; i < n; i++) {
         const ocrs_page* p = pages[i];
         const int tshift = tile_shift(params[i]);
         const int th = (p->h + (1 << tshift) - 1) >> tshift, tw = (p->w + (1 << tshift) - 1) >> tshift;
-        k::NormDesc& d = batch.add(p->h, p->w, (int64_t)th * tw);
-        d.src = p->grey.as<float>();
-        d.dst = batch.made.back()->grey.as<float>();
-        d.h = p->h;
-        d.w = p->w;
+        k::NormDesc& d = batch.add_like(p, (int64_t)th * tw);
         d.tshift = tshift;
         d.th = th;
         d.tw = tw;
@@ -87,31 +83,20 @@ ocrs_status ocrs_normalize_params_default(ocrs_normalize_params* out) {
 }
 
 ocrs_status ocrs_normalize_params_check(const ocrs_normalize_params* params) {
-    return guarded([&] {
-        if (!params) fail(OCRS_ERR_INVALID_ARGUMENT, "null argument");
-        check_params(*params);
-    });
+    return params_check(params, check_params);
 }
 
 ocrs_status ocrs_engine_normalize_pages(const ocrs_engine* e, const ocrs_page* const* pages, size_t n, const ocrs_normalize_params* params,
                                         ocrs_page** out_pages, ocrs_normalize_info* out_info) {
-    return guarded_engine(e, [&] {
-        if (!e || (n > 0 && (!pages || !params || !out_pages))) fail(OCRS_ERR_INVALID_ARGUMENT, "null argument");
-        check_pages_on(e, pages, n);
-        for (size_t i = 0; i < n; i++) check_params(params[i]);
-        Workspace ws;
-        normalize_pages(ws, pages, n, params, out_info).release_into(out_pages);
-    });
+    return pages_call(e, pages, n, params, check_params, out_pages,
+                      [&](Workspace& ws) { return normalize_pages(ws, pages, n, params, out_info); });
 }
 
 ocrs_status ocrs_engine_normalize_page(const ocrs_engine* e, const ocrs_page* page, const ocrs_normalize_params* params, ocrs_page** out_page,
                                        ocrs_normalize_info* out_info) {
-    ocrs_normalize_params def;
-    if (!params) {
-        ocrs_normalize_params_default(&def);
-        params = &def;
-    }
-    return ocrs_engine_normalize_pages(e, &page, 1, params, out_page, out_info);
+    return page_call(params, ocrs_normalize_params_default, [&](const ocrs_normalize_params* q) {
+        return ocrs_engine_normalize_pages(e, &page, 1, q, out_page, out_info);
+    });
 }
 
 }  // extern "C"

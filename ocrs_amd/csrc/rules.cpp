@@ -26,24 +26,16 @@ void check_params(const ocrs_rules_params& p) {
     if (std::isinf(p.paper)) fail(OCRS_ERR_INVALID_ARGUMENT, "rules: paper is a finite number, or NaN to measure it");
 }
 
-struct FreeHost {
-    void operator()(uint8_t* p) const { free(p); }
-};
-
 // every page with its rules removed as a new page of its own, all passes for all pages on `ws`'s stream; waits for them
 PageBatch<k::RulesDesc> remove_rules(Workspace& ws, const ocrs_page* const* pages, size_t n, const ocrs_rules_params* params,
                                      uint8_t** out_masks, ocrs_rules_info* out_infos) {
     PageBatch<k::RulesDesc> batch{"rules"};
     if (n == 0) return batch;
-    for (size_t i = 0; i < n; i++) check_page_side("rules", pages[i]);
+    check_pages_in("rules", pages, n, false);
     size_t mask_words = 0;
     for (size_t i = 0; i < n; i++) {
         const ocrs_page* p = pages[i];
-        k::RulesDesc& d = batch.add(p->h, p->w, k::rules_tiles(p->h, p->w));
-        d.src = p->grey.as<float>();
-        d.dst = batch.made.back()->grey.as<float>();
-        d.h = p->h;
-        d.w = p->w;
+        k::RulesDesc& d = batch.add_like(p, k::rules_tiles(p->h, p->w));
         d.ww = (p->w + 63) / 64;
         d.hw = (p->h + 63) / 64;
         d.min_length = params[i].min_length;
@@ -57,32 +49,18 @@ PageBatch<k::RulesDesc> remove_rules(Workspace& ws, const ocrs_page* const* page
     // per page: its bit masks, its histogram, its blocks' counts and its info; the byte mask when it is asked for
     unsigned long long* d_masks = ws.alloc_n<unsigned long long>(mask_words);
     unsigned long long* d_hist = ws.alloc_n<unsigned long long>(n * 256);
-    unsigned long long* d_counts = ws.alloc_n<unsigned long long>((size_t)batch.blocks * k::RULES_COUNTS);
-    k::RulesInfo* d_info = ws.alloc_n<k::RulesInfo>(n);
-    std::vector<std::unique_ptr<uint8_t, FreeHost>> host_masks;
+    batch.carve_outputs(ws, k::RULES_COUNTS, out_masks != nullptr);
     mask_words = 0;
     for (size_t i = 0; i < n; i++) {
         k::RulesDesc& d = batch.descs[i];
         d.masks = d_masks + mask_words;
         mask_words += k::rules_mask_words(d.h, d.w);
         d.hist = d_hist + i * 256;
-        d.counts = d_counts + (size_t)d.block0 * k::RULES_COUNTS;
-        d.info = d_info + i;
-        if (out_masks) {
-            d.mask_out = ws.alloc_n<uint8_t>((size_t)d.h * d.w);
-            host_masks.emplace_back(static_cast<uint8_t*>(malloc((size_t)d.h * d.w)));
-            if (!host_masks.back()) throw std::bad_alloc();
-        }
     }
-    batch.run(ws, [&](const k::RulesDesc* d_descs, int n_pages, int blocks) {
+    batch.run_outputs(ws, out_infos, out_masks, [&](const k::RulesDesc* d_descs, int n_pages, int blocks) {
         OCRS_HIP(hipMemsetAsync(d_hist, 0, n * 256 * sizeof(unsigned long long), ws.s()));
         k::remove_rules_pages(d_descs, n_pages, blocks, ws.s());
-        OCRS_HIP(hipGetLastError());   // of the launches, before the downloads are queued
-        if (out_infos) ws.download(out_infos, d_info, n * sizeof(k::RulesInfo));
-        for (size_t i = 0; i < host_masks.size(); i++)
-            ws.download(host_masks[i].get(), batch.descs[i].mask_out, (size_t)batch.descs[i].h * batch.descs[i].w);
     });
-    for (size_t i = 0; i < host_masks.size(); i++) out_masks[i] = host_masks[i].release();
     return batch;
 }
 
@@ -102,31 +80,20 @@ ocrs_status ocrs_rules_params_default(ocrs_rules_params* out) {
 }
 
 ocrs_status ocrs_rules_params_check(const ocrs_rules_params* params) {
-    return guarded([&] {
-        if (!params) fail(OCRS_ERR_INVALID_ARGUMENT, "null argument");
-        check_params(*params);
-    });
+    return params_check(params, check_params);
 }
 
 ocrs_status ocrs_engine_remove_rules_pages(const ocrs_engine* e, const ocrs_page* const* pages, size_t n, const ocrs_rules_params* params,
                                            ocrs_page** out_pages, uint8_t** out_masks, ocrs_rules_info* out_infos) {
-    return guarded_engine(e, [&] {
-        if (!e || (n > 0 && (!pages || !params || !out_pages))) fail(OCRS_ERR_INVALID_ARGUMENT, "null argument");
-        check_pages_on(e, pages, n);
-        for (size_t i = 0; i < n; i++) check_params(params[i]);
-        Workspace ws;
-        remove_rules(ws, pages, n, params, out_masks, out_infos).release_into(out_pages);
-    });
+    return pages_call(e, pages, n, params, check_params, out_pages,
+                      [&](Workspace& ws) { return remove_rules(ws, pages, n, params, out_masks, out_infos); });
 }
 
 ocrs_status ocrs_engine_remove_rules_page(const ocrs_engine* e, const ocrs_page* page, const ocrs_rules_params* params, ocrs_page** out_page,
                                           uint8_t** out_mask, ocrs_rules_info* out_info) {
-    ocrs_rules_params def;
-    if (!params) {
-        ocrs_rules_params_default(&def);
-        params = &def;
-    }
-    return ocrs_engine_remove_rules_pages(e, &page, 1, params, out_page, out_mask, out_info);
+    return page_call(params, ocrs_rules_params_default, [&](const ocrs_rules_params* q) {
+        return ocrs_engine_remove_rules_pages(e, &page, 1, q, out_page, out_mask, out_info);
+    });
 }
 
 }  // extern "C"

@@ -33,28 +33,16 @@ void check_params(const ocrs_speckle_params& p) {
     if (std::isinf(p.ink_level)) fail(OCRS_ERR_INVALID_ARGUMENT, "despeckle: ink_level is a finite number, or NaN to measure it");
 }
 
-struct FreeHost {
-    void operator()(uint8_t* p) const { free(p); }
-};
-
 // every page despeckled as a new page of its own, all passes for all pages on `ws`'s stream; waits for them
 PageBatch<k::SpeckleDesc> despeckle(Workspace& ws, const ocrs_page* const* pages, size_t n, const ocrs_speckle_params* params,
                                     uint8_t** out_masks, ocrs_speckle_info* out_infos) {
     PageBatch<k::SpeckleDesc> batch{"despeckle"};
     if (n == 0) return batch;
-    for (size_t i = 0; i < n; i++) {
-        check_page_side("despeckle", pages[i]);
-        if ((int64_t)pages[i]->h * pages[i]->w > (int64_t)std::numeric_limits<int32_t>::max())   // the labels are int32 pixel indices
-            fail(OCRS_ERR_INVALID_ARGUMENT, "despeckle: a page of %d x %d: at most 2^31 - 1 pixels", pages[i]->h, pages[i]->w);
-    }
+    check_pages_in("despeckle", pages, n, true);   // the labels are int32 pixel indices
     size_t mask_words = 0;
     for (size_t i = 0; i < n; i++) {
         const ocrs_page* p = pages[i];
-        k::SpeckleDesc& d = batch.add(p->h, p->w, k::speckle_tiles(p->h, p->w));
-        d.src = p->grey.as<float>();
-        d.dst = batch.made.back()->grey.as<float>();
-        d.h = p->h;
-        d.w = p->w;
+        k::SpeckleDesc& d = batch.add_like(p, k::speckle_tiles(p->h, p->w));
         d.ww = (p->w + 63) / 64;
         d.hw = (p->h + 63) / 64;
         d.max_area = params[i].max_area;
@@ -69,9 +57,7 @@ PageBatch<k::SpeckleDesc> despeckle(Workspace& ws, const ocrs_page* const* pages
     // mask when it is asked for
     unsigned long long* d_masks = ws.alloc_n<unsigned long long>(mask_words);
     unsigned long long* d_hist = ws.alloc_n<unsigned long long>(n * 512);
-    unsigned long long* d_counts = ws.alloc_n<unsigned long long>((size_t)batch.blocks * k::SPECKLE_COUNTS);
-    k::SpeckleInfo* d_info = ws.alloc_n<k::SpeckleInfo>(n);
-    std::vector<std::unique_ptr<uint8_t, FreeHost>> host_masks;
+    batch.carve_outputs(ws, k::SPECKLE_COUNTS, out_masks != nullptr);
     mask_words = 0;
     for (size_t i = 0; i < n; i++) {
         k::SpeckleDesc& d = batch.descs[i];
@@ -82,24 +68,12 @@ PageBatch<k::SpeckleDesc> despeckle(Workspace& ws, const ocrs_page* const* pages
         d.area = ws.alloc_n<uint32_t>(px);
         d.near_flag = ws.alloc_n<uint8_t>(px);
         d.hist = d_hist + i * 512;
-        d.counts = d_counts + (size_t)d.block0 * k::SPECKLE_COUNTS;
-        d.info = d_info + i;
-        if (out_masks) {
-            d.mask_out = ws.alloc_n<uint8_t>(px);
-            host_masks.emplace_back(static_cast<uint8_t*>(malloc(px)));
-            if (!host_masks.back()) throw std::bad_alloc();
-        }
         d.vec = vec16_ok(d.w, d.src, d.dst) && vec16_ok(d.w, d.labels, d.mask_out) ? 1 : 0;
     }
-    batch.run(ws, [&](const k::SpeckleDesc* d_descs, int n_pages, int blocks) {
+    batch.run_outputs(ws, out_infos, out_masks, [&](const k::SpeckleDesc* d_descs, int n_pages, int blocks) {
         OCRS_HIP(hipMemsetAsync(d_hist, 0, n * 512 * sizeof(unsigned long long), ws.s()));
         k::despeckle_pages(d_descs, n_pages, blocks, ws.s());
-        OCRS_HIP(hipGetLastError());   // of the launches, before the downloads are queued
-        if (out_infos) ws.download(out_infos, d_info, n * sizeof(k::SpeckleInfo));
-        for (size_t i = 0; i < host_masks.size(); i++)
-            ws.download(host_masks[i].get(), batch.descs[i].mask_out, (size_t)batch.descs[i].h * batch.descs[i].w);
     });
-    for (size_t i = 0; i < host_masks.size(); i++) out_masks[i] = host_masks[i].release();
     return batch;
 }
 
@@ -120,31 +94,20 @@ ocrs_status ocrs_speckle_params_default(ocrs_speckle_params* out) {
 }
 
 ocrs_status ocrs_speckle_params_check(const ocrs_speckle_params* params) {
-    return guarded([&] {
-        if (!params) fail(OCRS_ERR_INVALID_ARGUMENT, "null argument");
-        check_params(*params);
-    });
+    return params_check(params, check_params);
 }
 
 ocrs_status ocrs_engine_despeckle_pages(const ocrs_engine* e, const ocrs_page* const* pages, size_t n, const ocrs_speckle_params* params,
                                         ocrs_page** out_pages, uint8_t** out_masks, ocrs_speckle_info* out_infos) {
-    return guarded_engine(e, [&] {
-        if (!e || (n > 0 && (!pages || !params || !out_pages))) fail(OCRS_ERR_INVALID_ARGUMENT, "null argument");
-        check_pages_on(e, pages, n);
-        for (size_t i = 0; i < n; i++) check_params(params[i]);
-        Workspace ws;
-        despeckle(ws, pages, n, params, out_masks, out_infos).release_into(out_pages);
-    });
+    return pages_call(e, pages, n, params, check_params, out_pages,
+                      [&](Workspace& ws) { return despeckle(ws, pages, n, params, out_masks, out_infos); });
 }
 
 ocrs_status ocrs_engine_despeckle_page(const ocrs_engine* e, const ocrs_page* page, const ocrs_speckle_params* params, ocrs_page** out_page,
                                        uint8_t** out_mask, ocrs_speckle_info* out_info) {
-    ocrs_speckle_params def;
-    if (!params) {
-        ocrs_speckle_params_default(&def);
-        params = &def;
-    }
-    return ocrs_engine_despeckle_pages(e, &page, 1, params, out_page, out_mask, out_info);
+    return page_call(params, ocrs_speckle_params_default, [&](const ocrs_speckle_params* q) {
+        return ocrs_engine_despeckle_pages(e, &page, 1, q, out_page, out_mask, out_info);
+    });
 }
 
 }  // extern "C"

@@ -15,18 +15,14 @@
 No threshold gates anything here; the file says which figures were measured.
 """
 import argparse
-import csv
-import glob
 import os
-import shutil
 import statistics
-import subprocess
 import sys
-import tempfile
-import time
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+
+from bench_util import timed, traced   # tools/, beside this file
 
 BATCH, SIDE = 16, 1024
 RADII = (15, 127)
@@ -50,59 +46,6 @@ def shaded_page(seed, side):
     return (grey * light - 0.5).astype(np.float32)
 
 
-def timed(call, reps):
-    for _ in range(5):
-        call()
-    times = []
-    for _ in range(reps):
-        t0 = time.perf_counter()
-        call()
-        times.append(1e3 * (time.perf_counter() - t0))
-    return statistics.median(times), min(times)
-
-
-def kernel_durations(trace_dir):
-    """kernel -> sorted per-launch durations in us, from a rocprofv3 output directory (kernel-trace CSV, or the rocpd
-    database)."""
-    import sqlite3
-    rows = []
-    for path in glob.glob(os.path.join(trace_dir, "**", "*kernel_trace.csv"), recursive=True):
-        with open(path, newline="") as f:
-            rows += [(r.get("Kernel_Name", ""), int(r["Start_Timestamp"]), int(r["End_Timestamp"])) for r in csv.DictReader(f)]
-    if not rows:
-        for path in glob.glob(os.path.join(trace_dir, "**", "*.db"), recursive=True):
-            db = sqlite3.connect(path)
-            tables = [r[0] for r in db.execute("select name from sqlite_master where type='table'")]
-            kd = [t for t in tables if t.startswith("rocpd_kernel_dispatch")][0]
-            ks = [t for t in tables if t.startswith("rocpd_info_kernel_symbol")][0]
-            scols = [r[1] for r in db.execute("pragma table_info(%s)" % ks)]
-            name_col = "kernel_name" if "kernel_name" in scols else "display_name"
-            rows += list(db.execute("select s.%s, d.start, d.end from %s d join %s s on d.kernel_id = s.id" % (name_col, kd, ks)))
-    return {name: sorted((en - st) / 1e3 for n, st, en in rows if name in n) for name, _, _ in KERNELS}
-
-
-def traced(reps, radius):
-    """Runs --only-kernel under rocprofv3 in a child process -> (kernel -> durations, the command) or (None, why not)."""
-    prof = shutil.which("rocprofv3") or "/opt/rocm/bin/rocprofv3"
-    if not os.path.exists(prof):
-        return None, "rocprofv3 was not found"
-    tmp = tempfile.mkdtemp(prefix="binarize_prof_")
-    cmd = [prof, "--kernel-trace", "--stats", "--output-format", "csv", "-d", tmp, "--", sys.executable, os.path.abspath(__file__),
-           "--only-kernel", "--radius", str(radius), "--reps", str(reps)]
-    try:
-        r = subprocess.run(cmd, capture_output=True, text=True, timeout=300)
-        if r.returncode != 0:
-            return None, "the traced run ended with status %d: %s" % (r.returncode, (r.stderr or r.stdout)[-300:].replace("\n", " | "))
-        found = kernel_durations(tmp)
-        if not all(found[name] for name, _, _ in KERNELS):
-            return None, "the trace holds no launches of %s" % ", ".join(n for n, _, _ in KERNELS if not found[n])
-        return found, " ".join(["rocprofv3"] + cmd[1:5] + ["-d", "DIR", "--", "python", "tools/binarize_bench.py"] + cmd[-5:])
-    except subprocess.TimeoutExpired:
-        return None, "the traced run did not end within 300 s"
-    finally:
-        shutil.rmtree(tmp, ignore_errors=True)
-
-
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=20)
@@ -111,7 +54,9 @@ def main():
     ap.add_argument("--radius", type=int, default=15, help="with --only-kernel: the radius of the batch")
     a = ap.parse_args()
 
-    traces = [] if a.only_kernel else [(r,) + traced(a.reps, r) for r in RADII]   # before this process opens the GPU
+    # before this process opens the GPU
+    traces = [] if a.only_kernel else [(r,) + traced(__file__, ["--radius", str(r)], a.reps, [k[0] for k in KERNELS], "binarize_prof_")
+                                       for r in RADII]
 
     from ocrs_amd import DimOrder, ImageSource, Model, OcrEngine, _lib, models, synth
     _lib.require_gpu()

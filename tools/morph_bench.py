@@ -16,18 +16,14 @@
 No threshold gates anything here; the file says which figures were measured.
 """
 import argparse
-import csv
-import glob
 import os
-import shutil
 import statistics
-import subprocess
 import sys
-import tempfile
-import time
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+
+from bench_util import timed, traced   # tools/, beside this file
 
 BATCH, SIDE = 16, 1024
 OPS = ("thicken", "thin", "close", "open")
@@ -49,59 +45,16 @@ def damaged_page(seed, side):
     return grey
 
 
-def timed(call, reps):
-    for _ in range(WARM):
-        call()
-    times = []
-    for _ in range(reps):
-        t0 = time.perf_counter()
-        call()
-        times.append(1e3 * (time.perf_counter() - t0))
-    return statistics.median(times), min(times)
-
-
-def kernel_launches(trace_dir, names):
-    """kernel -> per-launch durations in us in the order of their start, from a rocprofv3 output directory (kernel-trace
-    CSV, or the rocpd database)."""
-    import sqlite3
-    rows = []
-    for path in glob.glob(os.path.join(trace_dir, "**", "*kernel_trace.csv"), recursive=True):
-        with open(path, newline="") as f:
-            rows += [(r.get("Kernel_Name", ""), int(r["Start_Timestamp"]), int(r["End_Timestamp"])) for r in csv.DictReader(f)]
-    if not rows:
-        for path in glob.glob(os.path.join(trace_dir, "**", "*.db"), recursive=True):
-            db = sqlite3.connect(path)
-            tables = [r[0] for r in db.execute("select name from sqlite_master where type='table'")]
-            kd = [t for t in tables if t.startswith("rocpd_kernel_dispatch")][0]
-            ks = [t for t in tables if t.startswith("rocpd_info_kernel_symbol")][0]
-            scols = [r[1] for r in db.execute("pragma table_info(%s)" % ks)]
-            name_col = "kernel_name" if "kernel_name" in scols else "display_name"
-            rows += list(db.execute("select s.%s, d.start, d.end from %s d join %s s on d.kernel_id = s.id" % (name_col, kd, ks)))
-    rows.sort(key=lambda r: r[1])
-    return {name: [(en - st) / 1e3 for n, st, en in rows if name in n] for name in names}
-
-
-def traced(reps):
-    """Runs --only-kernel under rocprofv3 in a child process -> (per configuration and kernel the sum of a batch's launches in
-    us, one per batch; the same for binarize; the command) or (None, None, why not)."""
-    prof = shutil.which("rocprofv3") or "/opt/rocm/bin/rocprofv3"
-    if not os.path.exists(prof):
-        return None, None, "rocprofv3 was not found"
-    tmp = tempfile.mkdtemp(prefix="morph_prof_")
-    cmd = [prof, "--kernel-trace", "--stats", "--output-format", "csv", "-d", tmp, "--", sys.executable, os.path.abspath(__file__),
-           "--only-kernel", "--reps", str(reps)]
-    try:
-        r = subprocess.run(cmd, capture_output=True, text=True, timeout=400)
-        if r.returncode != 0:
-            return None, None, "the traced run ended with status %d: %s" % (r.returncode, (r.stderr or r.stdout)[-300:].replace("\n", " | "))
-        found = kernel_launches(tmp, MORPH_KERNELS + BIN_KERNELS)
+def per_batch(reps):
+    """traced's pick: (per configuration and kernel the sum of a batch's launches in us, one per batch; the same for binarize)."""
+    def pick(found):
         batches = reps + WARM
         want = {"morph_rows_kernel": sum(STAGES[op] for op, _ in CONFIGS) * batches, "morph_cols_kernel": sum(STAGES[op] for op, _ in CONFIGS) * batches,
                 "morph_info_kernel": len(CONFIGS) * batches}
         want.update({name: batches for name in BIN_KERNELS})
         for name, n in want.items():
             if len(found[name]) != n:
-                return None, None, "the trace holds %d launches of %s, not %d" % (len(found[name]), name, n)
+                return None, "the trace holds %d launches of %s, not %d" % (len(found[name]), name, n)
         per = {}
         at = dict.fromkeys(MORPH_KERNELS, 0)
         for op, radius in CONFIGS:
@@ -112,11 +65,8 @@ def traced(reps):
                 at[name] += k * batches
                 per[(op, radius)][name] = sorted(sum(us[i * k:(i + 1) * k]) for i in range(WARM, batches))
         bins = {name: sorted(found[name][WARM:]) for name in BIN_KERNELS}
-        return per, bins, " ".join(["rocprofv3"] + cmd[1:5] + ["-d", "DIR", "--", "python", "tools/morph_bench.py"] + cmd[-3:])
-    except subprocess.TimeoutExpired:
-        return None, None, "the traced run did not end within 400 s"
-    finally:
-        shutil.rmtree(tmp, ignore_errors=True)
+        return (per, bins), None
+    return pick
 
 
 def main():
@@ -126,7 +76,10 @@ def main():
     ap.add_argument("--only-kernel", action="store_true", help="only the batch loops, nothing written: what the kernel trace runs")
     a = ap.parse_args()
 
-    per, bins, how = (None, None, None) if a.only_kernel else traced(a.reps)   # before this process opens the GPU
+    # before this process opens the GPU
+    trace, how = (None, None) if a.only_kernel else traced(__file__, [], a.reps, MORPH_KERNELS + BIN_KERNELS, "morph_prof_",
+                                                           per_batch(a.reps), limit=400)
+    per, bins = trace or (None, None)
 
     from ocrs_amd import DimOrder, ImageSource, Model, OcrEngine, _lib, models, synth
     _lib.require_gpu()

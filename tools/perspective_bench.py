@@ -17,47 +17,20 @@ No threshold gates anything here; the file says which figures were measured.
 """
 import argparse
 import os
-import shutil
 import statistics
-import subprocess
 import sys
-import tempfile
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tools"))
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
-import deskew_bench as DB   # timed(), kernel_durations()
+from bench_util import last_launches, timed, traced
 
 SIZES = ((512, 384, 30), (3000, 2200, 200))   # height, width, text lines
 KERNELS = ("edge_profiles_kernel", "edge_peaks_kernel", "skew_profiles_kernel", "project_pages_kernel")
 QUAD = (0.12, 0.08, 0.88, 0.10, 0.95, 0.93, 0.05, 0.90)   # of the sheet, as fractions of the photo's width and height
 DESK = -0.2
-
-
-def traced(reps):
-    """Runs --only-kernel under rocprofv3 in a child process -> (kernel -> durations, the command) or (None, why not)."""
-    prof = shutil.which("rocprofv3") or "/opt/rocm/bin/rocprofv3"
-    if not os.path.exists(prof):
-        return None, "rocprofv3 was not found"
-    tmp = tempfile.mkdtemp(prefix="perspective_prof_")
-    cmd = [prof, "--kernel-trace", "--stats", "--output-format", "csv", "-d", tmp, "--", sys.executable, os.path.abspath(__file__),
-           "--only-kernel", "--reps", str(reps)]
-    try:
-        r = subprocess.run(cmd, capture_output=True, text=True, timeout=300)
-        if r.returncode != 0:
-            return None, "the traced run ended with status %d: %s" % (r.returncode, (r.stderr or r.stdout)[-300:].replace("\n", " | "))
-        found = DB.kernel_durations(tmp, KERNELS)
-        want = len(SIZES) * (reps + 5)
-        found = {name: found[name][-want:] for name in KERNELS}   # (making the photos launched the warp before the loops)
-        if not all(len(found[name]) == want for name in KERNELS):
-            return None, "the trace holds %s launches, not %d each" % (", ".join("%d of %s" % (len(found[n]), n) for n in KERNELS), want)
-        return found, " ".join(["rocprofv3"] + cmd[1:5] + ["-d", "DIR", "--", "python", "tools/perspective_bench.py"] + cmd[-3:])
-    except subprocess.TimeoutExpired:
-        return None, "the traced run did not end within 300 s"
-    finally:
-        shutil.rmtree(tmp, ignore_errors=True)
 
 
 def main():
@@ -67,7 +40,9 @@ def main():
     ap.add_argument("--only-kernel", action="store_true", help="only the kernel loops, nothing written: what the kernel trace runs")
     a = ap.parse_args()
 
-    trace, how = (None, None) if a.only_kernel else traced(a.reps)   # before this process opens the GPU
+    # before this process opens the GPU; making the photos launches the warp before the loops
+    trace, how = (None, None) if a.only_kernel else traced(__file__, [], a.reps, KERNELS, "perspective_prof_",
+                                                           last_launches(KERNELS, len(SIZES) * (a.reps + 5)))
 
     import numpy as np
     import ocrs_amd
@@ -132,7 +107,7 @@ def main():
         for name, call in (("find_outline", lambda: eng.find_outline(photo)), ("edge_peaks (61 angles, work copy)", lambda: eng.edge_peaks([work], table, 8)),
                            ("project", lambda: eng.project(photo, m, out_hw)), ("straighten (outline + project)", lambda: eng.straighten(photo)),
                            ("detect_words", lambda: eng.detect_words(photo))):
-            med, best = DB.timed(call, a.reps)
+            med, best = timed(call, a.reps)
             out.append("one photo of %d x %d, %-34s %7.3f ms median (%7.3f min)" % (h, w, name + ":", med, best))
         o = eng.find_outline(photo)
         quad = np.array([v * (w if i % 2 == 0 else h) for i, v in enumerate(QUAD)], np.float64).reshape(4, 2)

@@ -17,15 +17,14 @@
 No threshold gates anything here; the file says which figures were measured.
 """
 import argparse
-import csv
-import glob
 import os
 import statistics
 import sys
-import time
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+
+from bench_util import kernel_launches, timed   # tools/, beside this file
 
 SHAPES = (((3508, 2480), (1754, 1240), "area"), ((1024, 1024), (1536, 1536), "bilinear"))
 KERNEL = "resample_pages_kernel"
@@ -35,49 +34,18 @@ def moved_bytes(src, dst):
     return 4.0 * (src[0] * src[1] + dst[0] * dst[1])
 
 
-def timed(call, reps):
-    for _ in range(5):
-        call()
-    times = []
-    for _ in range(reps):
-        t0 = time.perf_counter()
-        call()
-        times.append(1e3 * (time.perf_counter() - t0))
-    return statistics.median(times), min(times)
-
-
-def kernel_launches(trace_dir):
-    """(start ns, end ns) of every launch of the kernel in a rocprofv3 output directory: the rocpd database, or the
-    kernel-trace CSV of --output-format csv."""
-    import sqlite3
-    spans = []
-    for path in glob.glob(os.path.join(trace_dir, "**", "*.db"), recursive=True):
-        db = sqlite3.connect(path)
-        tables = [r[0] for r in db.execute("select name from sqlite_master where type='table'")]
-        kd = [t for t in tables if t.startswith("rocpd_kernel_dispatch")][0]
-        ks = [t for t in tables if t.startswith("rocpd_info_kernel_symbol")][0]
-        scols = [r[1] for r in db.execute("pragma table_info(%s)" % ks)]
-        name_col = "kernel_name" if "kernel_name" in scols else "display_name"
-        spans += [(st, en) for name, st, en in db.execute("select s.%s, d.start, d.end from %s d join %s s on d.kernel_id = s.id"
-                                                           % (name_col, kd, ks)) if KERNEL in name]
-    for path in glob.glob(os.path.join(trace_dir, "**", "*kernel_trace.csv"), recursive=True):
-        with open(path, newline="") as f:
-            spans += [(int(r["Start_Timestamp"]), int(r["End_Timestamp"])) for r in csv.DictReader(f) if KERNEL in r.get("Kernel_Name", "")]
-    return sorted(spans)
-
-
 def append_trace(trace_dir, out):
     """Per-launch durations of the kernel from a kernel trace of --only-kernel, which runs the loop of SHAPES[0] to its end
     and then that of SHAPES[1], the same number of launches each: the first half of the launches is the one, the second
     half the other."""
-    spans = kernel_launches(trace_dir)
-    if not spans or len(spans) % len(SHAPES):
-        raise SystemExit("%d launches of %s under %s: expected the same number per shape" % (len(spans), KERNEL, trace_dir))
-    per = len(spans) // len(SHAPES)
+    launches = kernel_launches(trace_dir, [KERNEL])[KERNEL]   # us, in the order of their start
+    if not launches or len(launches) % len(SHAPES):
+        raise SystemExit("%d launches of %s under %s: expected the same number per shape" % (len(launches), KERNEL, trace_dir))
+    per = len(launches) // len(SHAPES)
     lines = ["", "Appended by tools/resample_bench.py --append-trace, MEASURED in a run of its own on one MI355X:",
              "    rocprofv3 --kernel-trace --stats -d resample_prof -- python tools/resample_bench.py --only-kernel --reps %d" % (per - 5)]
     for i, (src, dst, filt) in enumerate(SHAPES):
-        us = sorted((en - st) / 1e3 for st, en in spans[i * per:(i + 1) * per])
+        us = sorted(launches[i * per:(i + 1) * per])
         mb = moved_bytes(src, dst) / 1e6
         med = statistics.median(us)
         lines.append("%s, %s %d x %d -> %d x %d, %d launches: %.1f us median, %.1f us minimum, %.1f us maximum per launch; %.1f MB "

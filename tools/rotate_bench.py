@@ -17,23 +17,12 @@ No threshold gates anything here; the file says which figures were measured.
 """
 import argparse
 import os
-import statistics
 import sys
-import time
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
-
-def timed(call, reps):
-    for _ in range(5):
-        call()
-    times = []
-    for _ in range(reps):
-        t0 = time.perf_counter()
-        call()
-        times.append(1e3 * (time.perf_counter() - t0))
-    return statistics.median(times), min(times)
+from bench_util import timed   # tools/, beside this file
 
 
 def main():
