@@ -956,6 +956,114 @@ OCRS_API ocrs_status ocrs_engine_morph_pages(const ocrs_engine* e, const ocrs_pa
                                              const ocrs_morph_params* params, ocrs_page** out_pages, uint8_t** out_masks,
                                              ocrs_morph_info* out_infos);
 
+/* ------------------------------------------------------------------------
+ * Page framing (no reference counterpart, opt-in).  What surrounds the text: the black bars of photocopies
+ * and flatbed scans, the dark wedge a skewed sheet leaves, the slice of the neighbouring page and the gutter shadow of a
+ * book scan, the two pages of a spread.  The detector turns such bars into word boxes and the line finder joins the two
+ * pages of a spread; despeckling refuses anything over 4096 pixels and rule removal anything thicker than max_thickness.
+ * Four pieces, each usable alone: frame cleanup, ink profiles, the choice of the content box and the gutter, and the crop
+ * with its maps back.  The page is dark ink on light paper (ocrs_engine_normalize_page makes it so; bars survive a
+ * binarisation).  What a trained detector or recogniser gains is uncalibrated.
+ *
+ * 1. Frame cleanup makes a new resident page of the same size on which the ink that is connected to the page frame is
+ * overwritten with the paper's level; every other pixel keeps its own 32-bit word (NaN payloads and -0.0 included);
+ * coordinates do not move.  The definition (tests/frame_ref.py restates it and the library equals it bit for bit; integer
+ * and set arithmetic, nothing iterated, so the result does not depend on schedule or batch).  With D = depth:
+ *   ink        v < threshold, an ordinary float compare: NaN is not ink, -inf is.
+ *   ring       d(y, x) = min(x, y, w - 1 - x, h - 1 - y); D = 0: the whole page; D > 0: the pixels with d < D.  Nothing
+ *              deeper than D is ever changed: the bound on the damage when a table frame or an underline runs off the sheet.
+ *   components R = ink in the ring, 8-connected; the page edge and the ring's inner edge are walls: a stroke that leaves
+ *              the ring and comes back in is two components.
+ *   seeds      the pixels of R on an enabled side; `sides` bit 0 left (x = 0), 1 top (y = 0), 2 right (x = w - 1), 3 bottom
+ *              (y = h - 1).
+ *   classes    a component holding a seed is touching; its area is its number of pixels in R.  removed = the pixels of
+ *              touching components of area >= min_area; kept = those of touching components of area < min_area (a glyph cut
+ *              by the edge of a tight screenshot crop).
+ *   fill       despeckling's paper fill: paper_bin = pct(1, 2) of the pixels of the whole page that are neither ink nor
+ *              NaN, 255 with nothing counted; paper_fill = (paper_bin + 1) / 256 - 0.5.  With paper given (not NaN) it is
+ *              the fill and the bin reads -1.
+ *   output     paper_fill on removed, the page's own word elsewhere.
+ * ocrs_frame_params_default: threshold 0, depth 128, sides 15, min_area 0, paper NaN.  ocrs_frame_params_check (host only):
+ * OCRS_ERR_INVALID_ARGUMENT for a threshold that is not finite, a depth outside 0 .. 65535, sides outside 1 .. 15, a negative
+ * min_area, an infinite paper; the engine calls refuse the same, and a page with a side over 65535 or with more than
+ * 2^31 - 1 pixels.  ocrs_engine_clean_frame_pages serves n pages of any sizes, each with its own params[i], in six launches
+ * for the whole batch on one stream; out_pages[n] receives the pages, out_infos[n] (may be NULL) what was found,
+ * out_masks[n] (may be NULL) per page a host uint8 [h][w], to be released with ocrs_buffer_free: bit 0 removed, bit 1 kept,
+ * bit 2 in R.  ocrs_engine_clean_frame_page: params == NULL means the default.
+ *
+ * 2. ocrs_engine_ink_profiles counts the pixels with v < threshold (finite) per column into out_cols[w] and per row into
+ * out_rows[h]; either may be NULL.  One launch; integer sums, exact whatever the order.
+ *
+ * 3. ocrs_frame_choose (host only) makes the content box and the gutter of a spread out of the two profiles:
+ *   content    cx0 = the first column with col_ink >= min_count, cx1 = the last such column + 1; rows likewise.  None:
+ *              found = 0 and the box is the whole page.  Otherwise the box is [cx0 - pad, cx1 + pad) x [cy0 - pad, cy1 + pad)
+ *              clipped to the page.
+ *   gutter     only when found, otherwise -1.  band = [cx0 + 3 (cx1 - cx0) / 8, cx0 + 5 (cx1 - cx0) / 8), floor division.  A
+ *              column is quiet when col_ink <= gutter_max_ink.  Among the maximal runs of quiet columns inside the band the
+ *              longest; ties to the least |2 mid - (cx0 + cx1)| with mid = start + len / 2, then to the leftmost.  Its
+ *              length >= gutter_min_width: gutter_x = mid, otherwise -1.  The left page is [x0, gutter_x), the right page
+ *              [gutter_x, x1).
+ * ocrs_frame_choice_params_default: min_count 1, pad 16, gutter_min_width 8, gutter_max_ink 0; _check: INVALID_ARGUMENT for
+ * min_count < 1, pad outside 0 .. 65535, gutter_min_width < 1, gutter_max_ink < 0.  ocrs_frame_choose refuses the same and
+ * sides outside 1 .. 65535; params == NULL means the default.
+ *
+ * 4. ocrs_engine_crop_pages cuts rects[i] = [x0, x1) x [y0, y1) out of pages[i] as a new resident page of (y1 - y0) x
+ * (x1 - x0), each side 1 .. 65535 (otherwise INVALID_ARGUMENT), for pages of any mix of sizes in one launch.  The rectangle
+ * may lie partly or wholly outside the page: an outside pixel is the 32-bit word of fill[i], whatever its bits, an inside
+ * pixel the source's word; a crop that adds margins is a valid use.  ocrs_uncrop_rects / ocrs_uncrop_chars (declared with
+ * ocrs_unrotate_rects below; host only, in place): results found on the cropped page mapped back to the frame of the page
+ * it was cut from: the centre of a rect gets one float32 addition of the offset per coordinate, char boxes get integer
+ * addition, everything else is untouched. */
+typedef struct ocrs_frame_params {
+    float threshold;       /* finite; ink is v < threshold */
+    int32_t depth;         /* D, 0 .. 65535: the ring's depth; 0: the whole page */
+    int32_t sides;         /* 1 .. 15: bit 0 left, 1 top, 2 right, 3 bottom */
+    int32_t min_area;      /* >= 0: a touching component smaller than this is kept */
+    float paper;           /* the fill; NaN: measured on the page */
+} ocrs_frame_params;
+typedef struct ocrs_frame_info {
+    int32_t paper_bin;     /* the bin paper_fill was taken from; -1: paper was given */
+    float paper_fill;      /* what the removed ink was overwritten with */
+    uint64_t ink;          /* pixels under the threshold */
+    uint64_t counted;      /* pixels that are neither ink nor NaN */
+    uint64_t ring_ink;     /* |R| */
+    uint64_t removed;      /* touching components removed */
+    uint64_t removed_pixels; /* |removed| */
+    uint64_t kept;         /* touching components kept for being smaller than min_area */
+    uint64_t kept_pixels;  /* |kept| */
+} ocrs_frame_info;
+typedef struct ocrs_frame_choice_params {
+    int32_t min_count;         /* >= 1 */
+    int32_t pad;               /* 0 .. 65535 */
+    int32_t gutter_min_width;  /* >= 1 */
+    int32_t gutter_max_ink;    /* >= 0 */
+} ocrs_frame_choice_params;
+typedef struct ocrs_frame_choice {
+    int32_t found;             /* 1: there is content */
+    int32_t x0, y0, x1, y1;    /* the box, half open */
+    int32_t gutter_x;          /* the right page's first column; -1: no gutter */
+} ocrs_frame_choice;
+typedef struct ocrs_crop_rect {
+    int32_t x0, y0, x1, y1;    /* half open; may reach outside the page */
+} ocrs_crop_rect;
+OCRS_API ocrs_status ocrs_frame_params_default(ocrs_frame_params* out);
+OCRS_API ocrs_status ocrs_frame_params_check(const ocrs_frame_params* params);
+OCRS_API ocrs_status ocrs_engine_clean_frame_page(const ocrs_engine* e, const ocrs_page* page, const ocrs_frame_params* params,
+                                                  ocrs_page** out_page, uint8_t** out_mask, ocrs_frame_info* out_info);
+OCRS_API ocrs_status ocrs_engine_clean_frame_pages(const ocrs_engine* e, const ocrs_page* const* pages, size_t n,
+                                                   const ocrs_frame_params* params, ocrs_page** out_pages, uint8_t** out_masks,
+                                                   ocrs_frame_info* out_infos);
+OCRS_API ocrs_status ocrs_engine_ink_profiles(const ocrs_engine* e, const ocrs_page* page, float threshold, uint32_t* out_cols,
+                                              uint32_t* out_rows);
+OCRS_API ocrs_status ocrs_frame_choice_params_default(ocrs_frame_choice_params* out);
+OCRS_API ocrs_status ocrs_frame_choice_params_check(const ocrs_frame_choice_params* params);
+OCRS_API ocrs_status ocrs_frame_choose(int h, int w, const uint32_t* col_ink, const uint32_t* row_ink,
+                                       const ocrs_frame_choice_params* params, ocrs_frame_choice* out);
+OCRS_API ocrs_status ocrs_engine_crop_page(const ocrs_engine* e, const ocrs_page* page, const ocrs_crop_rect* rect, float fill,
+                                           ocrs_page** out_page);
+OCRS_API ocrs_status ocrs_engine_crop_pages(const ocrs_engine* e, const ocrs_page* const* pages, size_t n, const ocrs_crop_rect* rects,
+                                            const float* fill, ocrs_page** out_pages);
+
 /* OcrEngine::detection_threshold (lib.rs:282-287). */
 OCRS_API float ocrs_engine_detection_threshold(const ocrs_engine* e);
 
@@ -1144,6 +1252,9 @@ OCRS_API ocrs_status ocrs_engine_rotate_pages(const ocrs_engine* e, const ocrs_p
                                               ocrs_page** out);
 OCRS_API ocrs_status ocrs_unrotate_rects(float* rects6, size_t n, int page_h, int page_w, int k);
 OCRS_API ocrs_status ocrs_unrotate_chars(ocrs_text_char* chars, size_t n, int page_h, int page_w, int k);
+/* "Page framing" above: results of a page cut out at (x0, y0) back in the frame of the page it was cut from */
+OCRS_API ocrs_status ocrs_uncrop_rects(float* rects6, size_t n, int x0, int y0);
+OCRS_API ocrs_status ocrs_uncrop_chars(ocrs_text_char* chars, size_t n, int x0, int y0);
 /* "Page deskew" above: its char boxes (declared here, after ocrs_text_char). */
 OCRS_API ocrs_status ocrs_unwarp_chars(ocrs_text_char* chars, size_t n, const float m[6]);
 /* "Perspective correction" above: its char boxes. */

@@ -16,7 +16,8 @@ from ._lib import OcrsError, check, lib
 
 __all__ = ["OcrEngine", "OcrEngineParams", "ImageSource", "ImageSourceError", "DimOrder", "DecodeMethod", "Model",
            "OcrInput", "TextLine", "TextWord", "TextChar", "OcrsError", "DEFAULT_ALPHABET", "EngineGroup", "line_frame",
-           "Orientation", "orientation_vote", "unrotate_rects", "unrotate_lines", "work_size", "rescale_rects", "normalize_params", "rules_params", "speckle_params", "binarize_params", "morph_params"]
+           "Orientation", "orientation_vote", "unrotate_rects", "unrotate_lines", "work_size", "rescale_rects", "normalize_params", "rules_params", "speckle_params", "binarize_params", "morph_params",
+           "frame_params", "frame_choose", "uncrop_rects", "uncrop_boxes", "uncrop_lines"]
 
 # lib.rs:34 (with the EUR sign the comment at lib.rs:33 asks for)
 DEFAULT_ALPHABET = " 0123456789!\"#$%&'()*+,-./:;<=>?@[\\]^_`{|}~€ABCDEFGHIJKLMNOPQRSTUVWXYZabcdefghijklmnopqrstuvwxyz"
@@ -593,6 +594,104 @@ def _morph_struct(op=None, rx=None, ry=None):
     return p
 
 
+FRAME_SIDES = {"L": 1, "T": 2, "R": 4, "B": 8}   # include/ocrs_amd.h ocrs_frame_params.sides
+
+
+def _frame_sides(sides):
+    """sides as the bits of ocrs_frame_params, from an int or from letters out of "LTRB" (any case)."""
+    if isinstance(sides, str):
+        if not sides or any(c not in FRAME_SIDES for c in sides.upper()):
+            raise ValueError("clean_frame: sides are letters out of LTRB, not %r" % (sides,))
+        bits = 0
+        for c in sides.upper():
+            bits |= FRAME_SIDES[c]
+        return bits
+    return int(sides)
+
+
+def frame_params(depth=None, sides=None, min_area=None, threshold=None, paper=None):
+    """ocrs_frame_params as a dict: ocrs_frame_params_default (depth 128, sides 15, min_area 0, threshold 0,
+    paper None = measured) with the given fields replaced (sides: the bits, or letters out of "LTRB"), checked by
+    ocrs_frame_params_check (host only)."""
+    p = _frame_struct(depth, sides, min_area, threshold, paper)
+    check(lib().ocrs_frame_params_check(C.byref(p)))
+    return {"depth": int(p.depth), "sides": int(p.sides), "min_area": int(p.min_area), "threshold": float(p.threshold),
+            "paper": None if p.paper != p.paper else float(p.paper)}
+
+
+def _frame_struct(depth=None, sides=None, min_area=None, threshold=None, paper=None):
+    p = _lib.FrameParams()
+    check(lib().ocrs_frame_params_default(C.byref(p)))
+    if depth is not None:
+        p.depth = int(depth)   # out of range is the library's to refuse
+    if sides is not None:
+        p.sides = _frame_sides(sides)
+    if min_area is not None:
+        p.min_area = int(min_area)
+    if threshold is not None:
+        p.threshold = float(threshold)
+    if paper is not None:
+        p.paper = float(paper)
+    return p
+
+
+def _choice_struct(min_count=None, pad=None, gutter_min_width=None, gutter_max_ink=None):
+    p = _lib.FrameChoiceParams()
+    check(lib().ocrs_frame_choice_params_default(C.byref(p)))
+    for name, v in (("min_count", min_count), ("pad", pad), ("gutter_min_width", gutter_min_width), ("gutter_max_ink", gutter_max_ink)):
+        if v is not None:
+            setattr(p, name, int(v))
+    return p
+
+
+def frame_choose(page_hw, col_ink, row_ink, min_count=None, pad=None, gutter_min_width=None, gutter_max_ink=None):
+    """ocrs_frame_choose (host only): the content box and the gutter of a page_hw = (height, width) page
+    from its ink profiles (uint32 [width], uint32 [height]: OcrEngine.ink_profiles) -> {"found", "x0", "y0", "x1", "y1",
+    "gutter_x"}.  The box is half open and is the whole page when nothing was found; gutter_x is the first column of the
+    right page of a spread, -1 without one.  Defaults: min_count 1, pad 16, gutter_min_width 8, gutter_max_ink 0."""
+    h, w = int(page_hw[0]), int(page_hw[1])
+    cols, rows = np.ascontiguousarray(col_ink, np.uint32), np.ascontiguousarray(row_ink, np.uint32)
+    if cols.shape != (w,) or rows.shape != (h,):
+        raise ValueError("frame_choose: the profiles of a %d x %d page are [%d] and [%d]" % (h, w, w, h))
+    p = _choice_struct(min_count, pad, gutter_min_width, gutter_max_ink)
+    out = _lib.FrameChoice()
+    check(lib().ocrs_frame_choose(C.c_int(h), C.c_int(w), cols.ctypes.data_as(C.POINTER(C.c_uint32)),
+                                  rows.ctypes.data_as(C.POINTER(C.c_uint32)), C.byref(p), C.byref(out)))
+    return out.as_dict()
+
+
+def uncrop_rects(rects, origin):
+    """ocrs_uncrop_rects (host only): word rects found on a page cut out at origin = (x0, y0) -> the same rects in the frame
+    of the page it was cut from, float32 [n, 6] (a copy)."""
+    a = _rects_to_array(rects).copy()
+    check(lib().ocrs_uncrop_rects(a.ctypes.data_as(C.POINTER(C.c_float)), C.c_size_t(len(a)), C.c_int(int(origin[0])), C.c_int(int(origin[1]))))
+    return a
+
+
+def uncrop_boxes(boxes, origin):
+    """ocrs_uncrop_chars on bare boxes: int32 [n, 4] (top, left, bottom, right) on a page cut out at origin = (x0, y0) -> in
+    the frame of the page it was cut from."""
+    b = np.asarray(boxes, np.int32).reshape(-1, 4)
+    arr = (_lib.TextCharC * max(len(b), 1))()
+    for i, (t, l, bo, r) in enumerate(b.tolist()):
+        arr[i] = _lib.TextCharC(0, t, l, bo, r)
+    check(lib().ocrs_uncrop_chars(arr, C.c_size_t(len(b)), C.c_int(int(origin[0])), C.c_int(int(origin[1]))))
+    return np.array([[arr[i].top, arr[i].left, arr[i].bottom, arr[i].right] for i in range(len(b))], np.int32).reshape(-1, 4)
+
+
+def uncrop_lines(text_lines, origin):
+    """recognize_text's output on a page cut out at origin = (x0, y0) -> new TextLines (None stays None) whose char boxes are
+    in the frame of the page it was cut from (ocrs_uncrop_chars); text, log-probs and scores are kept."""
+    out = []
+    for t in text_lines:
+        if t is None:
+            out.append(None)
+            continue
+        boxes = uncrop_boxes([c.rect for c in t.chars()], origin)
+        out.append(TextLine([TextChar(c.char, tuple(int(v) for v in b), c.logp) for c, b in zip(t.chars(), boxes)], t.score))
+    return out
+
+
 class Skew:
     """ocrs_engine_estimate_skew's outputs: angle (degrees; the page's content is turned counter-clockwise
     by it, deskew_map(.., angle) undoes it), scores (best coarse, runner-up coarse, at the angle), work_hw (the size the
@@ -1103,6 +1202,95 @@ class OcrEngine:
         return self._page_op_batch("morph", lib().ocrs_engine_morph_pages, _lib.MorphParams, _morph_struct, _lib.MorphInfo,
                                            inputs, params, mask, info)
 
+    # ---- page framing
+    def clean_frame(self, inp, depth=128, sides=15, min_area=0, threshold=0.0, paper=None, mask=False, info=False):
+        """ocrs_engine_clean_frame_page: the page with the ink that is connected to its frame (scanner bars, the wedge of a
+        skewed sheet, the slice of a neighbouring page, a gutter shadow) overwritten by the paper's level, as a new resident
+        page of the same size; every other pixel keeps its bits.  The page is dark ink on light paper (normalize makes it
+        so).  Only ink (< threshold) within `depth` pixels of the nearest side is looked at (0: the whole page), as
+        8-connected components inside that ring; a component with a pixel on one of `sides` (bits 0 left, 1 top, 2 right, 3
+        bottom, or letters out of "LTRB") and at least min_area pixels is removed, a smaller one is kept.  paper: the fill,
+        None = the page's median paper level.  mask=True: also the uint8 [H, W] mask (bit 0 removed, 1 kept, 2 ink in the
+        ring); info=True: also {"paper_bin", "paper_fill", "ink", "counted", "ring_ink", "removed", "removed_pixels", "kept",
+        "kept_pixels"}.  -> page, or (page[, mask][, info])."""
+        out = self.clean_frame_batch([inp], [{"depth": depth, "sides": sides, "min_area": min_area, "threshold": threshold, "paper": paper}],
+                                     mask=mask, info=info)
+        return tuple(o[0] for o in out) if mask or info else out[0]
+
+    def clean_frame_batch(self, inputs, params=None, mask=False, info=False):
+        """ocrs_engine_clean_frame_pages: pages of any sizes, each with its own parameters (a dict of clean_frame's keywords,
+        or None for the default; one for all, or one per page), all passes for the whole batch on one stream.  -> pages, or
+        (pages[, masks][, infos])."""
+        return self._page_op_batch("clean_frame", lib().ocrs_engine_clean_frame_pages, _lib.FrameParams, _frame_struct, _lib.FrameInfo,
+                                           inputs, params, mask, info)
+
+    def ink_profiles(self, inp, threshold=0.0, cols=True, rows=True):
+        """ocrs_engine_ink_profiles: the pixels under `threshold` per column (uint32 [W]) and per row (uint32 [H]) ->
+        (col_ink, row_ink); cols=False or rows=False: None in its place, and the library is not asked for it."""
+        h, w = inp.shape[-2:]
+        c = np.zeros(w, np.uint32) if cols else None
+        r = np.zeros(h, np.uint32) if rows else None
+        check(lib().ocrs_engine_ink_profiles(self._h, inp._h, C.c_float(float(threshold)),
+                                             c.ctypes.data_as(C.POINTER(C.c_uint32)) if cols else None,
+                                             r.ctypes.data_as(C.POINTER(C.c_uint32)) if rows else None))
+        return c, r
+
+    def crop(self, inp, rect, fill=0.5):
+        """ocrs_engine_crop_page: rect = (x0, y0, x1, y1), half open, cut out of the page as a new resident page of (y1 - y0)
+        x (x1 - x0), each 1 .. 65535.  The rectangle may reach outside the page: a pixel there is `fill` (a float32 scalar
+        keeps its bits, NaN payloads included)."""
+        return self.crop_batch([inp], [rect], [fill])[0]
+
+    def crop_batch(self, inputs, rects, fill=0.5):
+        """ocrs_engine_crop_pages: pages of any sizes, each with its own rectangle and fill (one fill for all, or one per
+        page), in one launch."""
+        n = len(inputs)
+        if len(rects) != n:
+            raise ValueError("crop_batch: one rectangle per page")
+        fills = list(fill) if isinstance(fill, (list, tuple, np.ndarray)) else [fill] * n
+        if len(fills) != n:
+            raise ValueError("crop_batch: one fill per page")
+        words = np.zeros(max(n, 1), np.float32)
+        for i, f in enumerate(fills):   # a float32 by its word: a conversion could quiet a signalling NaN
+            words.view(np.uint32)[i] = f.view(np.uint32) if isinstance(f, np.float32) else np.array([f], np.float32).view(np.uint32)[0]
+        rs = (_lib.CropRect * max(n, 1))(*[_lib.CropRect(*[int(v) for v in r]) for r in rects])
+        out = (C.c_void_p * n)()
+        check(lib().ocrs_engine_crop_pages(self._h, _page_array(inputs), C.c_size_t(n), rs, words.ctypes.data_as(C.POINTER(C.c_float)), out))
+        return _new_inputs(out, n)
+
+    def _framed(self, inp, kw):
+        """clean_frame, ink_profiles of the cleaned page and frame_choose, each with its own keywords out of kw ->
+        (cleaned page, frame info, choice)."""
+        kw = dict(kw)
+        clean_kw = {k: kw.pop(k) for k in ("depth", "sides", "min_area", "threshold", "paper") if k in kw}
+        choice_kw = {k: kw.pop(k) for k in ("min_count", "pad", "gutter_min_width", "gutter_max_ink") if k in kw}
+        if kw:
+            raise TypeError("unexpected keywords: %s" % ", ".join(sorted(kw)))
+        page, info = self.clean_frame(inp, info=True, **clean_kw)
+        cols, rows = self.ink_profiles(page, clean_kw.get("threshold", 0.0))
+        return page, info, frame_choose(page.shape[-2:], cols, rows, **choice_kw)
+
+    def frame(self, inp, info=False, **kw):
+        """The page without what surrounds its text: clean_frame, then ink_profiles of the cleaned page, then frame_choose,
+        then crop to the content box.  Keywords: clean_frame's (depth, sides, min_area, threshold, paper) and frame_choose's
+        (min_count, pad).  -> (page, (x0, y0)[, info]): the origin of the new page on the old one, for uncrop_rects /
+        uncrop_lines; info=True: also clean_frame's info with the choice under "choice".  A page without ink comes back whole."""
+        page, finfo, c = self._framed(inp, kw)
+        out = self.crop(page, (c["x0"], c["y0"], c["x1"], c["y1"]), np.float32(finfo["paper_fill"]))
+        return (out, (c["x0"], c["y0"]), dict(finfo, choice=c)) if info else (out, (c["x0"], c["y0"]))
+
+    def split_spread(self, inp, info=False, **kw):
+        """The pages of a spread: clean_frame, ink_profiles, frame_choose, then the content box cut at the gutter ->
+        [(page, (x0, y0))], one entry without a gutter, otherwise the left page [x0, gutter_x) first and the right page
+        [gutter_x, x1) second.  Keywords: clean_frame's and frame_choose's (gutter_min_width and gutter_max_ink too).
+        info=True: -> (that list, clean_frame's info with the choice under "choice")."""
+        page, finfo, c = self._framed(inp, kw)
+        cuts = [c["x0"], c["gutter_x"], c["x1"]] if c["x0"] < c["gutter_x"] < c["x1"] else [c["x0"], c["x1"]]   # no empty page
+        rects = [(a, c["y0"], b, c["y1"]) for a, b in zip(cuts[:-1], cuts[1:])]
+        made = self.crop_batch([page] * len(rects), rects, np.float32(finfo["paper_fill"]))
+        parts = [(p, (r[0], r[1])) for p, r in zip(made, rects)]
+        return (parts, dict(finfo, choice=c)) if info else parts
+
     # ---- page deskew (DESIGN.md §7.6)
     def skew_scores(self, inputs, sc_table):
         """ocrs_engine_skew_scores: the skew profile scores of pages of any sizes (a side at most 4096) at the angles of
@@ -1516,7 +1704,7 @@ class OcrEngine:
 
     # ---- lib.rs:290-300
     def get_text(self, inp, rectify=False, orientation=None, work_size=None, normalize=None, deskew=None, deskew_fill=0.5,
-                 perspective=None, perspective_fill=0.5, rules=None, despeckle=None, binarize=None, morph=None):
+                 perspective=None, perspective_fill=0.5, rules=None, despeckle=None, binarize=None, morph=None, frame=None):
         """rectify=True: the same sequence (detect_words, find_text_lines, recognize_text) with rectified crops.
         orientation: None reads the page as given; an int turns it by that many quarter turns counter-clockwise first
         (rotate); "auto" by what detect_orientation finds.
@@ -1544,6 +1732,11 @@ class OcrEngine:
         morph: None reads the page as given; True or a dict of morph()'s keywords reads the page with its strokes repaired
         (DESIGN.md §7.11).  Applied last, before detection: after despeckling, so that specks are not grown or welded to
         text, and after rule removal, whose max_thickness a thickened rule would exceed.  Coordinates do not move.
+        frame: None reads the page as given; True or a dict of frame()'s keywords reads the content box of the page with the
+        ink connected to its frame removed.  Applied after perspective, normalisation and binarisation (it
+        needs dark ink on light paper, and bars survive a binarisation) and before despeckling, the turn, deskew and rule
+        removal, so that detect_orientation and estimate_skew no longer see the bars.  The crop moves coordinates; get_text
+        returns text alone, so nothing is mapped back.
         get_text returns text alone; callers that want boxes run the steps
         themselves and bring them back last with unproject_rects / unproject_lines."""
         if perspective is not None:
@@ -1552,6 +1745,8 @@ class OcrEngine:
             inp = self.normalize(inp, **({} if normalize is True else dict(normalize)))
         if binarize is not None and binarize is not False:
             inp = self.binarize(inp, **({} if binarize is True else dict(binarize)))
+        if frame is not None and frame is not False:
+            inp = self.frame(inp, **({} if frame is True else dict(frame)))[0]
         if despeckle is not None and despeckle is not False:
             inp = self.despeckle(inp, **({} if despeckle is True else dict(despeckle)))
         if orientation is not None:

@@ -94,6 +94,9 @@ DECLARED_SYMBOLS = [
     "ocrs_speckle_params_default", "ocrs_speckle_params_check", "ocrs_engine_despeckle_page", "ocrs_engine_despeckle_pages",
     "ocrs_binarize_params_default", "ocrs_binarize_params_check", "ocrs_engine_binarize_page", "ocrs_engine_binarize_pages",
     "ocrs_morph_params_default", "ocrs_morph_params_check", "ocrs_engine_morph_page", "ocrs_engine_morph_pages",
+    "ocrs_frame_params_default", "ocrs_frame_params_check", "ocrs_engine_clean_frame_page", "ocrs_engine_clean_frame_pages",
+    "ocrs_engine_ink_profiles", "ocrs_frame_choice_params_default", "ocrs_frame_choice_params_check", "ocrs_frame_choose",
+    "ocrs_engine_crop_page", "ocrs_engine_crop_pages", "ocrs_uncrop_rects", "ocrs_uncrop_chars",
 ]
 
 ABI_VERSION = 6   # include/ocrs_amd.h OCRS_ABI_VERSION
@@ -163,6 +166,33 @@ class MorphInfo(C.Structure):   # include/ocrs_amd.h ocrs_morph_info
 
     def as_dict(self):
         return {name: int(getattr(self, name)) for name, _ in self._fields_}
+
+
+class FrameParams(C.Structure):   # include/ocrs_amd.h ocrs_frame_params
+    _fields_ = [("threshold", C.c_float), ("depth", C.c_int32), ("sides", C.c_int32), ("min_area", C.c_int32), ("paper", C.c_float)]
+
+
+class FrameInfo(C.Structure):   # include/ocrs_amd.h ocrs_frame_info
+    _fields_ = [("paper_bin", C.c_int32), ("paper_fill", C.c_float), ("ink", C.c_uint64), ("counted", C.c_uint64), ("ring_ink", C.c_uint64),
+                ("removed", C.c_uint64), ("removed_pixels", C.c_uint64), ("kept", C.c_uint64), ("kept_pixels", C.c_uint64)]
+
+    def as_dict(self):
+        return {name: (float if name.endswith("_fill") else int)(getattr(self, name)) for name, _ in self._fields_}
+
+
+class FrameChoiceParams(C.Structure):   # include/ocrs_amd.h ocrs_frame_choice_params
+    _fields_ = [("min_count", C.c_int32), ("pad", C.c_int32), ("gutter_min_width", C.c_int32), ("gutter_max_ink", C.c_int32)]
+
+
+class FrameChoice(C.Structure):   # include/ocrs_amd.h ocrs_frame_choice
+    _fields_ = [("found", C.c_int32), ("x0", C.c_int32), ("y0", C.c_int32), ("x1", C.c_int32), ("y1", C.c_int32), ("gutter_x", C.c_int32)]
+
+    def as_dict(self):
+        return {name: int(getattr(self, name)) for name, _ in self._fields_}
+
+
+class CropRect(C.Structure):   # include/ocrs_amd.h ocrs_crop_rect
+    _fields_ = [("x0", C.c_int32), ("y0", C.c_int32), ("x1", C.c_int32), ("y1", C.c_int32)]
 
 
 class SkewParams(C.Structure):   # include/ocrs_amd.h ocrs_skew_params

@@ -140,6 +140,30 @@ def main(argv=None):
                          "thicken grows the ink, thin shrinks it; e.g. --morph close, --morph thicken:1x0 (applied last, after "
                          "--despeckle and --remove-rules; the JSON gains \"morph\"; no reference counterpart; what a detector gains "
                          "is uncalibrated: DESIGN.md 7.11)")
+    ap.add_argument("--frame", action="store_true",
+                    help="take what surrounds the text out of the page on the GPU before reading it: ink that is connected to the "
+                         "page's edges (scanner bars, the wedge of a skewed sheet, a slice of the neighbouring page) is overwritten "
+                         "with the paper's level and the page is cut down to its content (after --normalize and --binarize, before "
+                         "--despeckle, --orientation, --deskew and --remove-rules: it needs dark ink on light paper, and the probes "
+                         "no longer see the bars).  Boxes are reported in the frame of the file as given; the JSON gains \"frame\" "
+                         "(no reference counterpart; what a detector gains is uncalibrated: DESIGN.md 7.12)")
+    ap.add_argument("--frame-depth", type=int, default=None, metavar="N",
+                    help="with --frame or --split-spread: only ink within N pixels of the nearest edge is looked at, 0 to 65535 "
+                         "(default 128; 0: the whole page)")
+    ap.add_argument("--frame-sides", default=None, metavar="LTRB",
+                    help="with --frame or --split-spread: the edges whose ink is removed, letters out of LTRB (default all four)")
+    ap.add_argument("--frame-min-area", type=int, default=None, metavar="N",
+                    help="with --frame or --split-spread: ink at an edge of fewer than N pixels is kept (default 0: none is)")
+    ap.add_argument("--frame-pad", type=int, default=None, metavar="N",
+                    help="with --frame or --split-spread: the margin kept around the content, 0 to 65535 pixels (default 16)")
+    ap.add_argument("--crop", default=None, metavar="X0,Y0,X1,Y1",
+                    help="read only that rectangle of the file (half open; it may reach beyond the file, where it is white), cut out "
+                         "on the GPU before anything else looks at the page.  Boxes are reported in the frame of the file as given "
+                         "(DESIGN.md 7.12)")
+    ap.add_argument("--split-spread", action="store_true",
+                    help="read the two pages of a book spread one after the other, the left page's text first: as --frame, and the "
+                         "content is cut at the gutter, the widest column-run without ink near its middle (a page without one is "
+                         "read whole)")
     ap.add_argument("-o", "--output")
     ap.add_argument("--debug", action="store_true")
     ap.add_argument("--text-map", action="store_true", help="write text-map.png (detect_text_pixels)")
@@ -174,6 +198,25 @@ def main(argv=None):
             ap.error("--morph: OP[:RX[xRY]] with OP one of %s, e.g. close, close:2, thicken:1x0; not %r" % (", ".join(MORPH_OPS), args.morph))
         rx = 1 if m.group(2) is None else int(m.group(2))
         morph_kw = {"op": m.group(1), "rx": rx, "ry": rx if m.group(3) is None else int(m.group(3))}
+    frame_kw = {}
+    if (args.frame_depth is not None or args.frame_sides is not None or args.frame_min_area is not None or args.frame_pad is not None) \
+            and not (args.frame or args.split_spread):
+        ap.error("--frame-depth, --frame-sides, --frame-min-area and --frame-pad are only valid with --frame or --split-spread")
+    if args.frame_sides is not None:
+        if not args.frame_sides or any(c not in "LTRB" for c in args.frame_sides.upper()):
+            ap.error("--frame-sides: letters out of LTRB, not %r" % args.frame_sides)
+        frame_kw["sides"] = args.frame_sides
+    for name, key in (("frame_depth", "depth"), ("frame_min_area", "min_area"), ("frame_pad", "pad")):
+        if getattr(args, name) is not None:
+            frame_kw[key] = getattr(args, name)
+    crop_rect = None
+    if args.crop is not None:
+        try:
+            crop_rect = tuple(int(v) for v in args.crop.split(","))
+        except ValueError:
+            crop_rect = ()
+        if len(crop_rect) != 4 or not all(abs(v) < 2 ** 31 for v in crop_rect):
+            ap.error("--crop takes four integers X0,Y0,X1,Y1")
     if args.perspective_fill is not None and args.perspective is None:
         ap.error("--perspective-fill is only valid with --perspective")
     if args.perspective is not None and args.perspective != "auto":
@@ -217,6 +260,13 @@ def main(argv=None):
         img = load_image(args.image)
         shape_hw = img.shape[:2]
         inp = engine.prepare_input(ImageSource.from_tensor(img, DimOrder.Hwc))
+    if crop_rect is not None:   # from here on the zone is the page; results are mapped back last
+        try:
+            inp = engine.crop(inp, crop_rect, 0.5)   # white around a zone that reaches beyond the file
+        except OcrsError as e:
+            if e.status != 1:   # OCRS_ERR_INVALID_ARGUMENT: a side outside 1 .. 65535
+                raise
+            ap.error("--crop: %s" % e)
     outline, quad_m = None, None
     if args.perspective is not None:   # from here on the straightened sheet is the page; results are mapped back last
         corners = None if args.perspective == "auto" else np.array(args.perspective, np.float32).reshape(4, 2)
@@ -232,7 +282,6 @@ def main(argv=None):
         outline = {"found": flat is not inp, "corners": (corners if found is None else found.corners).tolist()}
         if flat is not inp:
             inp, quad_m = flat, m
-    turn_hw = inp.shape[-2:]   # the frame the turn's results come back to
     norm_info = None
     if args.normalize:   # from here on the normalised page is the page; coordinates do not move
         inp, norm_info = engine.normalize(inp, tile=64 if args.normalize_tile is None else args.normalize_tile,
@@ -255,124 +304,170 @@ def main(argv=None):
             print("Binarize: %d of %d counted pixels are ink, written as %g (kept: %s); paper written as %g"
                   % (binarize_info["ink"], binarize_info["counted"], binarize_info["ink_fill"],
                      "yes" if args.binarize_keep_ink else "no", binarize_info["paper_fill"]))
-    speckle_info = None
-    if args.despeckle:   # from here on the page without its specks is the page; coordinates do not move
-        try:
-            inp, speckle_info = engine.despeckle(inp, max_area=4 if args.speck_max_area is None else args.speck_max_area,
-                                                 max_hole=0 if args.speck_fill_holes is None else args.speck_fill_holes,
-                                                 keep_near=0 if args.speck_keep_near is None else args.speck_keep_near, info=True)
-        except OcrsError as e:
-            if e.status != 1:   # OCRS_ERR_INVALID_ARGUMENT: a parameter out of range
-                raise
-            ap.error("--despeckle: %s" % e)
-        if args.debug:
-            print("Despeckle: %d specks (%d pixels) overwritten with %g (paper bin %d of %d pixels counted), %d kept near larger ink "
-                  "(%d pixels), %d holes (%d pixels) filled with %g (ink bin %d); %d pixels of ink"
-                  % (speckle_info["specks"], speckle_info["speck_pixels"], speckle_info["paper_fill"], speckle_info["paper_bin"],
-                     speckle_info["counted"], speckle_info["kept"], speckle_info["kept_pixels"], speckle_info["holes"],
-                     speckle_info["hole_pixels"], speckle_info["ink_fill"], speckle_info["ink_bin"], speckle_info["ink"]))
-    turns = None
-    if args.orientation is not None:   # from here on the turned page is the page; results are mapped back before output
-        if args.orientation == "auto":
-            found = engine.detect_orientation(inp)
-            turns = found.quarter_turns
+    def read_part(inp):
+        """One page from despeckling to recognition, its results back in the frame `inp` has here."""
+        turn_hw = inp.shape[-2:]   # the frame the turn's results come back to
+        speckle_info = None
+        if args.despeckle:   # from here on the page without its specks is the page; coordinates do not move (DESIGN.md 7.9)
+            try:
+                inp, speckle_info = engine.despeckle(inp, max_area=4 if args.speck_max_area is None else args.speck_max_area,
+                                                     max_hole=0 if args.speck_fill_holes is None else args.speck_fill_holes,
+                                                     keep_near=0 if args.speck_keep_near is None else args.speck_keep_near, info=True)
+            except OcrsError as e:
+                if e.status != 1:   # OCRS_ERR_INVALID_ARGUMENT: a parameter out of range
+                    raise
+                ap.error("--despeckle: %s" % e)
             if args.debug:
-                print("Orientation: vote %s (horizontal : vertical), scores %s over %s chars -> %d degrees"
-                      % (found.vote.tolist(), found.scores.tolist(), found.n_chars.tolist(), 90 * turns))
-        else:
-            turns = int(args.orientation) // 90
-        inp = engine.rotate(inp, turns)
-    skew, skew_map = None, None
-    if args.deskew is not None:   # from here on the upright page is the page; results are mapped back before output
-        skew = args.deskew
-        if skew == "auto":
-            found = engine.estimate_skew(inp)
-            skew = found.angle
+                print("Despeckle: %d specks (%d pixels) overwritten with %g (paper bin %d of %d pixels counted), %d kept near larger ink "
+                      "(%d pixels), %d holes (%d pixels) filled with %g (ink bin %d); %d pixels of ink"
+                      % (speckle_info["specks"], speckle_info["speck_pixels"], speckle_info["paper_fill"], speckle_info["paper_bin"],
+                         speckle_info["counted"], speckle_info["kept"], speckle_info["kept_pixels"], speckle_info["holes"],
+                         speckle_info["hole_pixels"], speckle_info["ink_fill"], speckle_info["ink_bin"], speckle_info["ink"]))
+        turns = None
+        if args.orientation is not None:   # from here on the turned page is the page; results are mapped back before output
+            if args.orientation == "auto":
+                found = engine.detect_orientation(inp)
+                turns = found.quarter_turns
+                if args.debug:
+                    print("Orientation: vote %s (horizontal : vertical), scores %s over %s chars -> %d degrees"
+                          % (found.vote.tolist(), found.scores.tolist(), found.n_chars.tolist(), 90 * turns))
+            else:
+                turns = int(args.orientation) // 90
+            inp = engine.rotate(inp, turns)
+        skew, skew_map = None, None
+        if args.deskew is not None:   # from here on the upright page is the page; results are mapped back before output
+            skew = args.deskew
+            if skew == "auto":
+                found = engine.estimate_skew(inp)
+                skew = found.angle
+                if args.debug:
+                    print("Skew: %.1f degrees (scores: best coarse %d, runner-up %d, at the angle %d; taken at %dx%d)"
+                          % (skew, found.scores[0], found.scores[1], found.scores[2], found.work_hw[1], found.work_hw[0]))
+            upright, m, _ = engine.deskew(inp, skew, fill=0.5 if args.deskew_fill is None else args.deskew_fill)
+            if upright is inp:
+                skew = 0.0
+            else:
+                inp, skew_map = upright, m
+        rules_info = None
+        if args.remove_rules:   # from here on the page without its rules is the page; coordinates do not move (DESIGN.md 7.8)
+            try:
+                inp, rules_info = engine.remove_rules(inp, min_length=96 if args.rules_min_length is None else args.rules_min_length,
+                                                      max_thickness=8 if args.rules_max_thickness is None else args.rules_max_thickness,
+                                                      margin=1 if args.rules_margin is None else args.rules_margin, info=True)
+            except OcrsError as e:
+                if e.status != 1:   # OCRS_ERR_INVALID_ARGUMENT: a parameter out of range
+                    raise
+                ap.error("--remove-rules: %s" % e)
             if args.debug:
-                print("Skew: %.1f degrees (scores: best coarse %d, runner-up %d, at the angle %d; taken at %dx%d)"
-                      % (skew, found.scores[0], found.scores[1], found.scores[2], found.work_hw[1], found.work_hw[0]))
-        upright, m, _ = engine.deskew(inp, skew, fill=0.5 if args.deskew_fill is None else args.deskew_fill)
-        if upright is inp:
-            skew = 0.0
+                print("Rules: %d pixels overwritten with %g (paper bin %d of %d pixels counted): %d of horizontal rules, %d of vertical "
+                      "rules, %d kept where a stroke crosses; %d pixels of ink"
+                      % (rules_info["overwritten"], rules_info["fill"], rules_info["paper_bin"], rules_info["counted"],
+                         rules_info["h_removed"], rules_info["v_removed"], rules_info["kept"], rules_info["ink"]))
+        morph_info = None
+        if morph_kw is not None:   # from here on the page with its strokes repaired is the page; coordinates do not move (DESIGN.md 7.11)
+            try:
+                inp, morph_info = engine.morph(inp, info=True, **morph_kw)
+            except OcrsError as e:
+                if e.status != 1:   # OCRS_ERR_INVALID_ARGUMENT: a parameter out of range
+                    raise
+                ap.error("--morph: %s" % e)
+            morph_info = dict(morph_info, **morph_kw)
+            if args.debug:
+                print("Morph: %s over %d x %d: %d of %d counted pixels changed; %d pixels of ink before, %d after"
+                      % (morph_kw["op"], 2 * morph_kw["rx"] + 1, 2 * morph_kw["ry"] + 1, morph_info["changed"], morph_info["counted"],
+                         morph_info["ink_before"], morph_info["ink_after"]))
+        tiled = False if args.tiled is None else True if args.tiled < 0 else args.tiled
+        work_hw = None   # the size the detector sees the (turned) page at: DESIGN.md 7.3
+        if args.work_scale is not None or args.work_max_side is not None:
+            from . import work_size
+            work_hw = work_size(inp.shape[-2:], scale=args.work_scale, max_side=args.work_max_side)
+            if args.debug:
+                print("Working resolution: %dx%d for a page of %dx%d" % (work_hw[1], work_hw[0], inp.shape[-1], inp.shape[-2]))
+        if args.text_map or args.text_mask:   # with a working resolution: the map of the work page, at its size
+            tm = engine.detect_text_pixels(inp if work_hw is None else engine.resize(inp, work_hw), tiled=tiled)
+            if args.text_map:
+                write_image("text-map.png", tm)
+            if args.text_mask:
+                write_image("text-mask.png", (tm > np.float32(engine.detection_threshold())).astype(np.float32))
+        word_boxes = None
+        if args.detection_confidence or args.min_word_score is not None:
+            words, wscore, wpixels = engine.detect_words(inp, scores=True, tiled=tiled, work_size=work_hw)
+            if args.min_word_score is not None:
+                keep = wscore >= np.float32(args.min_word_score)
+                words, wscore, wpixels = words[keep], wscore[keep], wpixels[keep]
+            lines, index = engine.find_text_lines(inp, words, index=True)
+            if args.detection_confidence:
+                word_boxes = [[(words[k], wscore[k], wpixels[k]) for k in idx] for idx in index]
         else:
-            inp, skew_map = upright, m
-    rules_info = None
-    if args.remove_rules:   # from here on the page without its rules is the page; coordinates do not move
+            words = engine.detect_words(inp, tiled=tiled, work_size=work_hw)
+            lines = engine.find_text_lines(inp, words)
+        if args.text_line_images:  # main.rs:66-86
+            os.makedirs("lines", exist_ok=True)
+            for i, line in enumerate(lines):
+                write_image("lines/line-%d.png" % i, engine.prepare_recognition_input(inp, line, rectify=args.rectify) + np.float32(0.5))
+        texts = engine.recognize_text(inp, lines, scores=args.confidence, rectify=args.rectify)
+        if skew_map is not None:
+            from . import unwarp_lines, unwarp_rects
+            texts = unwarp_lines(texts, skew_map)
+            if word_boxes is not None:
+                word_boxes = [[(unwarp_rects([r], skew_map)[0], s, n) for r, s, n in boxes] for boxes in word_boxes]
+        if turns is not None:
+            from . import unrotate_lines, unrotate_rects
+            texts = unrotate_lines(texts, tuple(turn_hw), turns)
+            if word_boxes is not None:
+                word_boxes = [[(unrotate_rects([r], tuple(turn_hw), turns)[0], s, n) for r, s, n in boxes] for boxes in word_boxes]
+        return {"texts": texts, "word_boxes": word_boxes, "words": words, "lines": lines, "turns": turns, "skew": skew,
+                "despeckle": speckle_info, "rules": rules_info, "morph": morph_info}
+
+    # the pages to read and where each lies on the page as it is here: the content box, the two pages of a spread, or the page
+    parts, frame_info = [(inp, None)], None
+    if args.frame or args.split_spread:   # from here on what surrounds the text is gone (DESIGN.md 7.12)
         try:
-            inp, rules_info = engine.remove_rules(inp, min_length=96 if args.rules_min_length is None else args.rules_min_length,
-                                                  max_thickness=8 if args.rules_max_thickness is None else args.rules_max_thickness,
-                                                  margin=1 if args.rules_margin is None else args.rules_margin, info=True)
-        except OcrsError as e:
-            if e.status != 1:   # OCRS_ERR_INVALID_ARGUMENT: a parameter out of range
+            if args.split_spread:
+                parts, frame_info = engine.split_spread(inp, info=True, **frame_kw)
+            else:
+                page, origin, frame_info = engine.frame(inp, info=True, **frame_kw)
+                parts = [(page, origin)]
+        except (OcrsError, ValueError) as e:
+            if isinstance(e, OcrsError) and e.status != 1:   # OCRS_ERR_INVALID_ARGUMENT: a parameter out of range
                 raise
-            ap.error("--remove-rules: %s" % e)
+            ap.error("--frame: %s" % e)
+        choice = frame_info.pop("choice")
+        frame_info["boxes"] = [[o[0], o[1], o[0] + p.shape[-1], o[1] + p.shape[-2]] for p, o in parts]
         if args.debug:
-            print("Rules: %d pixels overwritten with %g (paper bin %d of %d pixels counted): %d of horizontal rules, %d of vertical "
-                  "rules, %d kept where a stroke crosses; %d pixels of ink"
-                  % (rules_info["overwritten"], rules_info["fill"], rules_info["paper_bin"], rules_info["counted"],
-                     rules_info["h_removed"], rules_info["v_removed"], rules_info["kept"], rules_info["ink"]))
-    morph_info = None
-    if morph_kw is not None:   # from here on the page with its strokes repaired is the page; coordinates do not move
-        try:
-            inp, morph_info = engine.morph(inp, info=True, **morph_kw)
-        except OcrsError as e:
-            if e.status != 1:   # OCRS_ERR_INVALID_ARGUMENT: a parameter out of range
-                raise
-            ap.error("--morph: %s" % e)
-        morph_info = dict(morph_info, **morph_kw)
-        if args.debug:
-            print("Morph: %s over %d x %d: %d of %d counted pixels changed; %d pixels of ink before, %d after"
-                  % (morph_kw["op"], 2 * morph_kw["rx"] + 1, 2 * morph_kw["ry"] + 1, morph_info["changed"], morph_info["counted"],
-                     morph_info["ink_before"], morph_info["ink_after"]))
-    tiled = False if args.tiled is None else True if args.tiled < 0 else args.tiled
-    work_hw = None   # the size the detector sees the (turned) page at: DESIGN.md 7.3
-    if args.work_scale is not None or args.work_max_side is not None:
-        from . import work_size
-        work_hw = work_size(inp.shape[-2:], scale=args.work_scale, max_side=args.work_max_side)
-        if args.debug:
-            print("Working resolution: %dx%d for a page of %dx%d" % (work_hw[1], work_hw[0], inp.shape[-1], inp.shape[-2]))
-    if args.text_map or args.text_mask:   # with a working resolution: the map of the work page, at its size
-        tm = engine.detect_text_pixels(inp if work_hw is None else engine.resize(inp, work_hw), tiled=tiled)
-        if args.text_map:
-            write_image("text-map.png", tm)
-        if args.text_mask:
-            write_image("text-mask.png", (tm > np.float32(engine.detection_threshold())).astype(np.float32))
-    word_boxes = None
-    if args.detection_confidence or args.min_word_score is not None:
-        words, wscore, wpixels = engine.detect_words(inp, scores=True, tiled=tiled, work_size=work_hw)
-        if args.min_word_score is not None:
-            keep = wscore >= np.float32(args.min_word_score)
-            words, wscore, wpixels = words[keep], wscore[keep], wpixels[keep]
-        lines, index = engine.find_text_lines(inp, words, index=True)
-        if args.detection_confidence:
-            word_boxes = [[(words[k], wscore[k], wpixels[k]) for k in idx] for idx in index]
-    else:
-        words = engine.detect_words(inp, tiled=tiled, work_size=work_hw)
-        lines = engine.find_text_lines(inp, words)
-    if args.text_line_images:  # main.rs:66-86
-        os.makedirs("lines", exist_ok=True)
-        for i, line in enumerate(lines):
-            write_image("lines/line-%d.png" % i, engine.prepare_recognition_input(inp, line, rectify=args.rectify) + np.float32(0.5))
-    texts = engine.recognize_text(inp, lines, scores=args.confidence, rectify=args.rectify)
-    if skew_map is not None:
-        from . import unwarp_lines, unwarp_rects
-        texts = unwarp_lines(texts, skew_map)
-        if word_boxes is not None:
-            word_boxes = [[(unwarp_rects([r], skew_map)[0], s, n) for r, s, n in boxes] for boxes in word_boxes]
-    if turns is not None:
-        from . import unrotate_lines, unrotate_rects
-        texts = unrotate_lines(texts, tuple(turn_hw), turns)
-        if word_boxes is not None:
-            word_boxes = [[(unrotate_rects([r], tuple(turn_hw), turns)[0], s, n) for r, s, n in boxes] for boxes in word_boxes]
+            print("Frame: %d components (%d pixels) touching the frame overwritten with %g (paper bin %d of %d pixels counted), %d kept "
+                  "(%d pixels); %d of %d pixels of ink in the ring; content %s, gutter at %d -> %s"
+                  % (frame_info["removed"], frame_info["removed_pixels"], frame_info["paper_fill"], frame_info["paper_bin"],
+                     frame_info["counted"], frame_info["kept"], frame_info["kept_pixels"], frame_info["ring_ink"], frame_info["ink"],
+                     "found" if choice["found"] else "not found", choice["gutter_x"], frame_info["boxes"]))
+    texts, word_boxes, words, lines = [], None, [], []
+    for n_part, (part, origin) in enumerate(parts):   # the left page first
+        got = read_part(part)
+        if origin is not None:
+            from . import uncrop_lines, uncrop_rects
+            got["texts"] = uncrop_lines(got["texts"], origin)
+            if got["word_boxes"] is not None:
+                got["word_boxes"] = [[(uncrop_rects([r], origin)[0], s, n) for r, s, n in boxes] for boxes in got["word_boxes"]]
+        texts += got["texts"]
+        if got["word_boxes"] is not None:
+            word_boxes = (word_boxes or []) + got["word_boxes"]
+        words, lines = list(words) + list(got["words"]), list(lines) + list(got["lines"])
+        if n_part == 0:   # what the later steps report is what they found on the first page
+            turns, skew, speckle_info, rules_info, morph_info = got["turns"], got["skew"], got["despeckle"], got["rules"], got["morph"]
     if quad_m is not None:
         from . import unproject_lines, unproject_rects
         texts = unproject_lines(texts, quad_m)
         if word_boxes is not None:
             word_boxes = [[(unproject_rects([r], quad_m)[0], s, n) for r, s, n in boxes] for boxes in word_boxes]
+    if crop_rect is not None:
+        from . import uncrop_lines, uncrop_rects
+        texts = uncrop_lines(texts, crop_rect[:2])
+        if word_boxes is not None:
+            word_boxes = [[(uncrop_rects([r], crop_rect[:2])[0], s, n) for r, s, n in boxes] for boxes in word_boxes]
     if args.json:
         content = output.format_json_output(args.image, tuple(shape_hw), texts, confidence=args.confidence, word_boxes=word_boxes,
                                             orientation=None if turns is None else 90 * turns, normalize=norm_info, skew=skew, outline=outline,
-                                            rules=rules_info, despeckle=speckle_info, binarize=binarize_info, morph=morph_info)
+                                            rules=rules_info, despeckle=speckle_info, binarize=binarize_info, morph=morph_info, frame=frame_info)
     else:
         content = output.format_text_output(texts)
     if args.output:

@@ -586,6 +586,53 @@ int64_t morph_row_blocks(int h, int w);           // blocks a page takes in a ho
 // which the vertical pass sizes its LDS.
 void morph_pages(const MorphDesc* d_descs, int n_pages, const int row_blocks[2], const int col_blocks[2], int max_ry, hipStream_t s);
 
+// ---- kernels_frame.hip ------------------------------------
+struct FrameInfo {       // what a page's frame cleanup found: the layout of ocrs_frame_info
+    int32_t paper_bin;   // the bin the fill was taken from; -1: the fill was given
+    float paper_fill;    // what the removed ink was overwritten with
+    uint64_t ink;        // pixels under the threshold
+    uint64_t counted;    // pixels that are neither ink nor NaN
+    uint64_t ring_ink;   // |R|: ink inside the ring
+    uint64_t removed, removed_pixels;   // touching components of area >= min_area, and their pixels
+    uint64_t kept, kept_pixels;         // touching components of area < min_area, and their pixels
+};
+constexpr int FRAME_COUNTS = 32;   // 64-bit words of a block's record: [wave][8]
+struct FrameDesc {       // one page whose frame is cleaned: dst [h, w] from src [h, w]
+    const float* src;
+    float* dst;          // never overlaps src
+    unsigned long long* rmask;   // the row-major bit mask of R = ink in the ring: h * ww words (64 pixels a word, bits past the edge zero)
+    int32_t* labels;     // [h * w] the union-find forest over the pixels of R (the other entries are never written or read)
+    uint32_t* area;      // [h * w] at a root: the pixels of its component
+    uint8_t* seed_flag;  // [h * w] at a root: 1 when a pixel of its component lies on an enabled side
+    unsigned long long* hist;    // [256] paper pixels (neither ink nor NaN); zero when the first launch starts
+    unsigned long long* counts;  // [hw * ww, FRAME_COUNTS] what each block counted
+    FrameInfo* info;
+    uint8_t* mask_out;   // [h, w] the mask of include/ocrs_amd.h, or null
+    int32_t h, w;        // each 1 .. 65535, h * w < 2^31
+    int32_t ww, hw;      // ceil(w / 64), ceil(h / 64)
+    int32_t block0;      // the page's first block (one per 64 x 64 tile): the sum of hw * ww over the pages before it
+    int32_t depth, sides, min_area;
+    float threshold;
+    float paper;         // NaN: measured
+    int32_t vec;         // w % 4 == 0 and the buffers 16-byte aligned, so 16-byte accesses are safe
+};
+int64_t frame_tiles(int h, int w);   // blocks a page of this size takes (host)
+// Pages of any mix of sizes and parameters, six launches on `s`; total_blocks = the sum of frame_tiles() over the pages.
+void clean_frame_pages(const FrameDesc* d_descs, int n_pages, int total_blocks, hipStream_t s);
+// cols[w] and rows[h] (either may be null; zero when the launch starts) += the pixels of src [h, w] under `threshold`; one launch
+void ink_profiles(const float* src, int h, int w, float threshold, uint32_t* cols, uint32_t* rows, hipStream_t s);
+struct CropDesc {        // one rectangle cut out of a page: dst [oh, ow] = src [y0 .. y0 + oh, x0 .. x0 + ow), `fill` outside src
+    const uint32_t* src;
+    uint32_t* dst;
+    int32_t h, w;        // of src
+    int32_t oh, ow;      // each 1 .. 65535
+    int32_t x0, y0;      // any int32
+    uint32_t fill;       // the 32-bit word of a pixel outside src
+    int32_t block0;      // the page's first block (one per 64 x 64 tile of dst)
+    int32_t vec;         // ow % 4 == 0 and dst 16-byte aligned: 16-byte stores
+};
+void crop_pages(const CropDesc* d_descs, int n_pages, int total_blocks, hipStream_t s);
+
 // kernels_peaks.hip
 void measure_peaks(double* mfma_tflops, double* copy_gbps);
 
