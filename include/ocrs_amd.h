@@ -957,6 +957,61 @@ OCRS_API ocrs_status ocrs_engine_morph_pages(const ocrs_engine* e, const ocrs_pa
                                              ocrs_morph_info* out_infos);
 
 /* ------------------------------------------------------------------------
+ * Grain removal (no reference counterpart, opt-in).  Sensor noise of a photo taken in poor light, salt and
+ * pepper on a grey page, a halftone screen under the text: despeckling sees them only after a threshold has turned them
+ * into components and cannot touch salt inside strokes, stroke repair removes one polarity by growing the other, and
+ * binarisation turns grain into specks.  These calls make a new resident page of the same size by a rank filter over a
+ * rectangle around every pixel: a median, any percentile, or either applied to outliers only, so that hairlines and small
+ * print survive.  It belongs in front of the threshold.  A result pixel is always the 32-bit word of some pixel of the
+ * source, never a recomputed number; a NaN pixel keeps its own word (payload included); coordinates do not move, so nothing
+ * needs mapping back.  The source page is untouched; release both with ocrs_page_free in any order.  What a trained
+ * detector or recogniser gains is uncalibrated.
+ *
+ * The definition (tests/rank_ref.py restates it and the library equals it bit for bit; nothing is computed, so the result
+ * does not depend on schedule or batch):
+ *   order      stroke repair's: words w are ordered through the key k(w) = ~w if the sign bit is set, else w | 0x80000000;
+ *              -0.0 and +0.0 are two values.  NaN of any payload is not counted: it enters no window.
+ *   window     of pixel (y, x): [y - ry, y + ry] x [x - rx, x + rx] clipped to the page; at most 15 x 15.  A counted pixel
+ *              is in its own window, so the number n of counted pixels in it is at least 1.
+ *   rank       at(p) = (p (n - 1) + 50) / 100 in integers; s[0 .. n - 1] the window's counted keys in ascending order.  The
+ *              filter's value is the word of s[at(percent)]: percent 0 the least key (stroke repair's thicken), 100 the
+ *              greatest (thin), 50 the median, of an even n the upper one.
+ *   sparing    tail = 0: every counted pixel takes the filter's value.  tail >= 1: with lt the number of window keys under
+ *              the pixel's own key and le the number under or equal, the pixel keeps its word iff lt <= at(100 - tail) and
+ *              le - 1 >= at(tail): its own ranks meet the central part of its window, it is no outlier.  percent 50 with
+ *              tail 50 is percent 50 with tail 0; a tail so small that at(tail) = 0 spares every pixel.
+ *
+ * ocrs_rank_params_default: rx 1, ry 1, percent 50, tail 20.
+ * ocrs_rank_params_check (host only): OCRS_ERR_INVALID_ARGUMENT for an rx or ry outside 0 .. 7 or both 0, a percent outside
+ * 0 .. 100, a tail outside 0 .. 50; the engine calls refuse the same, and a page with a side over 65535 or with more than
+ * 2^31 - 1 pixels.
+ * ocrs_engine_rank_pages serves n pages of any sizes, each with its own params[i] (radii, percents and tails mix freely), in
+ * at most three launches for the whole batch on one stream; out_pages[n] receives the pages, out_infos[n] (may be NULL) the counts,
+ * out_masks[n] (may be NULL) per page a host uint8 [h][w], to be released with ocrs_buffer_free: bit 0 ink after (counted
+ * and under 0.0f), bit 1 the word changed.  A failed call writes no output pointer and leaves nothing allocated.
+ * ocrs_engine_rank_page: params == NULL means the default. */
+typedef struct ocrs_rank_params {
+    int32_t rx;            /* 0 .. 7: the window is (2 ry + 1) rows of (2 rx + 1) pixels */
+    int32_t ry;            /* 0 .. 7; not both 0 */
+    int32_t percent;       /* 0 .. 100: the rank taken, 50 the median */
+    int32_t tail;          /* 0 .. 50: a pixel whose ranks lie inside [tail, 100 - tail] percent keeps its word; 0: none does */
+} ocrs_rank_params;
+typedef struct ocrs_rank_info {
+    uint64_t counted;      /* pixels that are not NaN */
+    uint64_t changed;      /* counted pixels whose word changed */
+    uint64_t ink_before;   /* counted pixels under 0.0f on the source */
+    uint64_t ink_after;    /* counted pixels under 0.0f on the result */
+    uint64_t spared;       /* counted pixels that kept their word by the sparing rule */
+} ocrs_rank_info;
+OCRS_API ocrs_status ocrs_rank_params_default(ocrs_rank_params* out);
+OCRS_API ocrs_status ocrs_rank_params_check(const ocrs_rank_params* params);
+OCRS_API ocrs_status ocrs_engine_rank_page(const ocrs_engine* e, const ocrs_page* page, const ocrs_rank_params* params,
+                                           ocrs_page** out_page, uint8_t** out_mask, ocrs_rank_info* out_info);
+OCRS_API ocrs_status ocrs_engine_rank_pages(const ocrs_engine* e, const ocrs_page* const* pages, size_t n,
+                                            const ocrs_rank_params* params, ocrs_page** out_pages, uint8_t** out_masks,
+                                            ocrs_rank_info* out_infos);
+
+/* ------------------------------------------------------------------------
  * Page framing (no reference counterpart, opt-in).  What surrounds the text: the black bars of photocopies
  * and flatbed scans, the dark wedge a skewed sheet leaves, the slice of the neighbouring page and the gutter shadow of a
  * book scan, the two pages of a spread.  The detector turns such bars into word boxes and the line finder joins the two

@@ -16,7 +16,7 @@ from ._lib import OcrsError, check, lib
 
 __all__ = ["OcrEngine", "OcrEngineParams", "ImageSource", "ImageSourceError", "DimOrder", "DecodeMethod", "Model",
            "OcrInput", "TextLine", "TextWord", "TextChar", "OcrsError", "DEFAULT_ALPHABET", "EngineGroup", "line_frame",
-           "Orientation", "orientation_vote", "unrotate_rects", "unrotate_lines", "work_size", "rescale_rects", "normalize_params", "rules_params", "speckle_params", "binarize_params", "morph_params",
+           "Orientation", "orientation_vote", "unrotate_rects", "unrotate_lines", "work_size", "rescale_rects", "normalize_params", "rules_params", "speckle_params", "binarize_params", "morph_params", "rank_params",
            "frame_params", "frame_choose", "uncrop_rects", "uncrop_boxes", "uncrop_lines"]
 
 # lib.rs:34 (with the EUR sign the comment at lib.rs:33 asks for)
@@ -591,6 +591,30 @@ def _morph_struct(op=None, rx=None, ry=None):
             p.ry = int(rx)
     if ry is not None:
         p.ry = int(ry)
+    return p
+
+
+def rank_params(rx=None, ry=None, percent=None, tail=None):
+    """ocrs_rank_params as a dict: ocrs_rank_params_default (rx 1, ry 1, percent 50, tail 20) with the
+    given fields replaced (ry=None with an rx given means ry = rx), checked by ocrs_rank_params_check (host only)."""
+    p = _rank_struct(rx, ry, percent, tail)
+    check(lib().ocrs_rank_params_check(C.byref(p)))
+    return {"rx": int(p.rx), "ry": int(p.ry), "percent": int(p.percent), "tail": int(p.tail)}
+
+
+def _rank_struct(rx=None, ry=None, percent=None, tail=None):
+    p = _lib.RankParams()
+    check(lib().ocrs_rank_params_default(C.byref(p)))
+    if rx is not None:
+        p.rx = int(rx)   # out of range is the library's to refuse
+        if ry is None:
+            p.ry = int(rx)
+    if ry is not None:
+        p.ry = int(ry)
+    if percent is not None:
+        p.percent = int(percent)
+    if tail is not None:
+        p.tail = int(tail)
     return p
 
 
@@ -1202,6 +1226,27 @@ class OcrEngine:
         return self._page_op_batch("morph", lib().ocrs_engine_morph_pages, _lib.MorphParams, _morph_struct, _lib.MorphInfo,
                                            inputs, params, mask, info)
 
+    # ---- grain removal
+    def rank(self, inp, rx=1, ry=None, percent=50, tail=20, mask=False, info=False):
+        """ocrs_engine_rank_page: the page with its grain removed by a rank filter over the window of 2 ry + 1 rows of
+        2 rx + 1 pixels around every pixel, clipped to the page, as a new resident page of the same size (ry=None: ry = rx;
+        0 .. 7, not both 0).  percent: the rank taken among the n counted pixels of the window, (percent (n - 1) + 50) // 100
+        from the darkest: 50 the median, 0 the darkest (morph's "thicken"), 100 the lightest ("thin").  tail: 0 filters
+        every pixel; 1 .. 50 filters outliers only: a pixel whose own ranks in its window meet [tail, 100 - tail] percent
+        keeps its bits, which is what keeps hairlines and small print.  Every result pixel has the bits of some source
+        pixel; NaN pixels are not counted and keep their bits.  It belongs before binarize.  mask=True: also the uint8
+        [H, W] mask (bit 0 ink after, bit 1 changed); info=True: also {"counted", "changed", "ink_before", "ink_after",
+        "spared"}.  -> page, or (page[, mask][, info])."""
+        out = self.rank_batch([inp], [{"rx": rx, "ry": ry, "percent": percent, "tail": tail}], mask=mask, info=info)
+        return tuple(o[0] for o in out) if mask or info else out[0]
+
+    def rank_batch(self, inputs, params=None, mask=False, info=False):
+        """ocrs_engine_rank_pages: pages of any sizes, each with its own parameters (a dict of rank's keywords, or None
+        for the default; one for all, or one per page; radii, percents and tails mix freely), at most three launches for the
+        whole batch on one stream.  -> pages, or (pages[, masks][, infos])."""
+        return self._page_op_batch("rank", lib().ocrs_engine_rank_pages, _lib.RankParams, _rank_struct, _lib.RankInfo,
+                                           inputs, params, mask, info)
+
     # ---- page framing (DESIGN.md §7.12)
     def clean_frame(self, inp, depth=128, sides=15, min_area=0, threshold=0.0, paper=None, mask=False, info=False):
         """ocrs_engine_clean_frame_page: the page with the ink that is connected to its frame (scanner bars, the wedge of a
@@ -1704,7 +1749,7 @@ class OcrEngine:
 
     # ---- lib.rs:290-300
     def get_text(self, inp, rectify=False, orientation=None, work_size=None, normalize=None, deskew=None, deskew_fill=0.5,
-                 perspective=None, perspective_fill=0.5, rules=None, despeckle=None, binarize=None, morph=None, frame=None):
+                 perspective=None, perspective_fill=0.5, rules=None, despeckle=None, binarize=None, morph=None, frame=None, rank=None):
         """rectify=True: the same sequence (detect_words, find_text_lines, recognize_text) with rectified crops.
         orientation: None reads the page as given; an int turns it by that many quarter turns counter-clockwise first
         (rotate); "auto" by what detect_orientation finds.
@@ -1737,12 +1782,17 @@ class OcrEngine:
         needs dark ink on light paper, and bars survive a binarisation) and before despeckling, the turn, deskew and rule
         removal, so that detect_orientation and estimate_skew no longer see the bars.  The crop moves coordinates; get_text
         returns text alone, so nothing is mapped back.
+        rank: None reads the page as given; True or a dict of rank()'s keywords reads the page with its grain removed
+        (DESIGN.md §7.13).  Applied after perspective and normalisation and before binarisation, which would turn grain into
+        specks: everything downstream sees the cleaned page.  Coordinates do not move.
         get_text returns text alone; callers that want boxes run the steps
         themselves and bring them back last with unproject_rects / unproject_lines."""
         if perspective is not None:
             inp = self.straighten(inp, None if isinstance(perspective, str) and perspective == "auto" else perspective, fill=perspective_fill)[0]
         if normalize is not None and normalize is not False:
             inp = self.normalize(inp, **({} if normalize is True else dict(normalize)))
+        if rank is not None and rank is not False:
+            inp = self.rank(inp, **({} if rank is True else dict(rank)))
         if binarize is not None and binarize is not False:
             inp = self.binarize(inp, **({} if binarize is True else dict(binarize)))
         if frame is not None and frame is not False:

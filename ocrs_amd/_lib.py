@@ -94,6 +94,7 @@ DECLARED_SYMBOLS = [
     "ocrs_speckle_params_default", "ocrs_speckle_params_check", "ocrs_engine_despeckle_page", "ocrs_engine_despeckle_pages",
     "ocrs_binarize_params_default", "ocrs_binarize_params_check", "ocrs_engine_binarize_page", "ocrs_engine_binarize_pages",
     "ocrs_morph_params_default", "ocrs_morph_params_check", "ocrs_engine_morph_page", "ocrs_engine_morph_pages",
+    "ocrs_rank_params_default", "ocrs_rank_params_check", "ocrs_engine_rank_page", "ocrs_engine_rank_pages",
     "ocrs_frame_params_default", "ocrs_frame_params_check", "ocrs_engine_clean_frame_page", "ocrs_engine_clean_frame_pages",
     "ocrs_engine_ink_profiles", "ocrs_frame_choice_params_default", "ocrs_frame_choice_params_check", "ocrs_frame_choose",
     "ocrs_engine_crop_page", "ocrs_engine_crop_pages", "ocrs_uncrop_rects", "ocrs_uncrop_chars",
@@ -163,6 +164,17 @@ class MorphParams(C.Structure):   # include/ocrs_amd.h ocrs_morph_params
 
 class MorphInfo(C.Structure):   # include/ocrs_amd.h ocrs_morph_info
     _fields_ = [("counted", C.c_uint64), ("changed", C.c_uint64), ("ink_before", C.c_uint64), ("ink_after", C.c_uint64)]
+
+    def as_dict(self):
+        return {name: int(getattr(self, name)) for name, _ in self._fields_}
+
+
+class RankParams(C.Structure):   # include/ocrs_amd.h ocrs_rank_params
+    _fields_ = [("rx", C.c_int32), ("ry", C.c_int32), ("percent", C.c_int32), ("tail", C.c_int32)]
+
+
+class RankInfo(C.Structure):   # include/ocrs_amd.h ocrs_rank_info
+    _fields_ = [("counted", C.c_uint64), ("changed", C.c_uint64), ("ink_before", C.c_uint64), ("ink_after", C.c_uint64), ("spared", C.c_uint64)]
 
     def as_dict(self):
         return {name: int(getattr(self, name)) for name, _ in self._fields_}

@@ -140,6 +140,14 @@ def main(argv=None):
                          "thicken grows the ink, thin shrinks it; e.g. --morph close, --morph thicken:1x0 (applied last, after "
                          "--despeckle and --remove-rules; the JSON gains \"morph\"; no reference counterpart; what a detector gains "
                          "is uncalibrated: DESIGN.md 7.11)")
+    ap.add_argument("--rank", nargs="?", const="", default=None, metavar="R[xRY]][:PERCENT[:TAIL]",
+                    help="take grain (sensor noise, salt and pepper, a halftone screen) out of the page on the GPU before reading "
+                         "it, by a rank filter over a window that reaches R pixels to the left and right and RY up and down (0 to "
+                         "7, not both 0; default 1; RY defaults to R).  PERCENT: the rank taken, 0 to 100 (default 50, the median); "
+                         "TAIL: 0 filters every pixel, 1 to 50 only the pixels whose rank in their window lies in the outer TAIL "
+                         "percent (default 20: hairlines and small print are kept); e.g. --rank, --rank 2, --rank 1x0:50:0 (after "
+                         "--normalize, before --binarize; the JSON gains \"rank\"; no reference counterpart; what a detector "
+                         "gains is uncalibrated: DESIGN.md 7.13)")
     ap.add_argument("--frame", action="store_true",
                     help="take what surrounds the text out of the page on the GPU before reading it: ink that is connected to the "
                          "page's edges (scanner bars, the wedge of a skewed sheet, a slice of the neighbouring page) is overwritten "
@@ -198,6 +206,15 @@ def main(argv=None):
             ap.error("--morph: OP[:RX[xRY]] with OP one of %s, e.g. close, close:2, thicken:1x0; not %r" % (", ".join(MORPH_OPS), args.morph))
         rx = 1 if m.group(2) is None else int(m.group(2))
         morph_kw = {"op": m.group(1), "rx": rx, "ry": rx if m.group(3) is None else int(m.group(3))}
+    rank_kw = None
+    if args.rank is not None:
+        import re
+        m = re.fullmatch(r"(?:(\d+)(?:x(\d+))?)?(?::(\d+)(?::(\d+))?)?", args.rank)
+        if not m:
+            ap.error("--rank: [R[xRY]][:PERCENT[:TAIL]], e.g. 1, 2x1, 1:50, 1x0:50:0; not %r" % args.rank)
+        rx = 1 if m.group(1) is None else int(m.group(1))
+        rank_kw = {"rx": rx, "ry": rx if m.group(2) is None else int(m.group(2)), "percent": 50 if m.group(3) is None else int(m.group(3)),
+                   "tail": 20 if m.group(4) is None else int(m.group(4))}
     frame_kw = {}
     if (args.frame_depth is not None or args.frame_sides is not None or args.frame_min_area is not None or args.frame_pad is not None) \
             and not (args.frame or args.split_spread):
@@ -290,6 +307,19 @@ def main(argv=None):
             print("Normalize: %s page (vote %d), white bin %d, levels %d .. %d, %d pixels counted"
                   % ("dark" if norm_info["dark"] else "light", norm_info["vote"], norm_info["white"], norm_info["lo"], norm_info["hi"],
                      norm_info["counted"]))
+    rank_info = None
+    if rank_kw is not None:   # from here on the page without its grain is the page; coordinates do not move
+        try:
+            inp, rank_info = engine.rank(inp, info=True, **rank_kw)
+        except OcrsError as e:
+            if e.status != 1:   # OCRS_ERR_INVALID_ARGUMENT: a parameter out of range
+                raise
+            ap.error("--rank: %s" % e)
+        rank_info = dict(rank_info, **rank_kw)
+        if args.debug:
+            print("Rank: percent %d over %d x %d, tail %d: %d of %d counted pixels changed, %d spared; %d pixels of ink before, %d after"
+                  % (rank_kw["percent"], 2 * rank_kw["rx"] + 1, 2 * rank_kw["ry"] + 1, rank_kw["tail"], rank_info["changed"],
+                     rank_info["counted"], rank_info["spared"], rank_info["ink_before"], rank_info["ink_after"]))
     binarize_info = None
     if args.binarize:   # from here on the page cut into ink and paper is the page; coordinates do not move
         try:
@@ -467,7 +497,8 @@ def main(argv=None):
     if args.json:
         content = output.format_json_output(args.image, tuple(shape_hw), texts, confidence=args.confidence, word_boxes=word_boxes,
                                             orientation=None if turns is None else 90 * turns, normalize=norm_info, skew=skew, outline=outline,
-                                            rules=rules_info, despeckle=speckle_info, binarize=binarize_info, morph=morph_info, frame=frame_info)
+                                            rules=rules_info, despeckle=speckle_info, binarize=binarize_info, morph=morph_info, frame=frame_info,
+                                            rank=rank_info)
     else:
         content = output.format_text_output(texts)
     if args.output:

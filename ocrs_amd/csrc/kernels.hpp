@@ -586,6 +586,40 @@ int64_t morph_row_blocks(int h, int w);           // blocks a page takes in a ho
 // which the vertical pass sizes its LDS.
 void morph_pages(const MorphDesc* d_descs, int n_pages, const int row_blocks[2], const int col_blocks[2], int max_ry, hipStream_t s);
 
+// ---- kernels_rank.hip -------------------------------------
+struct RankInfo {        // what a page's grain removal counted: the layout of ocrs_rank_info
+    uint64_t counted;    // pixels that are not NaN
+    uint64_t changed;    // counted pixels whose 32-bit word changed
+    uint64_t ink_before; // counted pixels under 0.0f on the source
+    uint64_t ink_after;  // counted pixels under 0.0f on the result
+    uint64_t spared;     // counted pixels that kept their word by the sparing rule
+};
+constexpr int RANK_COUNTS = 5;        // 64-bit words of a block's record: the five counts of RankInfo
+constexpr int RANK_MAX_RADIUS = 7;
+constexpr int RANK_TILE_W = 64;       // columns of a block's tile: a lane per column
+constexpr int RANK_TILE_H = 16;       // rows of a block's tile: four waves, four rows each
+struct RankDesc {        // one page that is filtered: dst [h, w] from src [h, w]
+    const float* src;
+    float* dst;          // never overlaps src
+    unsigned long long* counts;  // [tiles_y * tiles_x, RANK_COUNTS] what each block counted
+    RankInfo* info;
+    uint8_t* mask_out;   // [h, w] the mask of include/ocrs_amd.h, or null
+    int32_t h, w;        // each 1 .. 65535, h * w < 2^31
+    int32_t block0;      // the sum of tiles_y * tiles_x over the pages before it: where the page's records lie in the batch's
+    int32_t reg_block0;  // the page's first block in the launch of the register classes: pages of class 2 take no blocks there
+    int32_t lds_block0;  // ... in the launch of class 2: pages of the register classes take no blocks there
+    int32_t tiles_x, tiles_y;   // ceil(w / RANK_TILE_W), ceil(h / RANK_TILE_H)
+    int32_t rx, ry;      // 0 .. 7, not both 0
+    int32_t percent;     // 0 .. 100
+    int32_t tail;        // 0 .. 50; 0: no pixel is spared
+    int32_t cls;         // rank_class(rx, ry): how the kernel holds the window
+};
+int64_t rank_blocks(int h, int w);   // blocks a page of this size takes (host)
+int rank_class(int rx, int ry);      // 0: a 3 x 3 window in registers, 1: 5 x 5 in registers, 2: walked in LDS (host)
+// Pages of any mix of sizes and parameters, at most three launches on `s`; reg_blocks and lds_blocks are the sums of
+// rank_blocks() over the pages of classes 0 and 1, and of class 2.
+void rank_pages(const RankDesc* d_descs, int n_pages, int reg_blocks, int lds_blocks, hipStream_t s);
+
 // ---- kernels_frame.hip ------------------------------------
 struct FrameInfo {       // what a page's frame cleanup found: the layout of ocrs_frame_info
     int32_t paper_bin;   // the bin the fill was taken from; -1: the fill was given

@@ -15,7 +15,7 @@ def rounded_vertex_coords(rect6):
     return [[_rround(x), _rround(y)] for x, y in rotated_rect_corners(rect6)]
 
 
-def ocr_json(input_path, input_hw, text_lines, confidence=False, word_boxes=None, orientation=None, normalize=None, skew=None, outline=None, rules=None, despeckle=None, binarize=None, morph=None, frame=None):
+def ocr_json(input_path, input_hw, text_lines, confidence=False, word_boxes=None, orientation=None, normalize=None, skew=None, outline=None, rules=None, despeckle=None, binarize=None, morph=None, frame=None, rank=None):
     """output.rs:34-76.  text_lines: list of TextLine | None.  confidence (no reference counterpart): every line and word
     object also gets "confidence" (TextLine / TextWord.confidence; the lines must come from a scored recognize_text).
     word_boxes (no reference counterpart; indexed like text_lines): per line the detector's word boxes in reading order as
@@ -40,7 +40,10 @@ def ocr_json(input_path, input_hw, text_lines, confidence=False, word_boxes=None
     asked for; the top level then gets "morph": {"changed", "counted", "ink_after", "ink_before", "op", "rx", "ry"}.
     frame (no reference counterpart): what OcrEngine.clean_frame(info=True) found on the page, with "boxes": the rectangles
     [x0, y0, x1, y1] that were read, in reading order (one, or the two pages of a spread); the top level then gets "frame":
-    {"boxes", "counted", "ink", "kept", "kept_pixels", "paper_bin", "paper_fill", "removed", "removed_pixels", "ring_ink"}."""
+    {"boxes", "counted", "ink", "kept", "kept_pixels", "paper_bin", "paper_fill", "removed", "removed_pixels", "ring_ink"}.
+    rank (no reference counterpart): what OcrEngine.rank(info=True) counted on the page, with the radii, the percent and the
+    tail it was asked for; the top level then gets "rank": {"changed", "counted", "ink_after", "ink_before", "percent", "rx",
+    "ry", "spared", "tail"}."""
     line_items = []
     for li, line in enumerate(text_lines):
         if line is None:
@@ -78,14 +81,16 @@ def ocr_json(input_path, input_hw, text_lines, confidence=False, word_boxes=None
     if frame is not None:
         doc["frame"] = {k: (float if k.endswith("_fill") else int)(v) for k, v in frame.items() if k != "boxes"}
         doc["frame"]["boxes"] = [[int(v) for v in b] for b in frame["boxes"]]
+    if rank is not None:
+        doc["rank"] = {k: int(v) for k, v in rank.items()}
     return doc
 
 
-def format_json_output(input_path, input_hw, text_lines, confidence=False, word_boxes=None, orientation=None, normalize=None, skew=None, outline=None, rules=None, despeckle=None, binarize=None, morph=None, frame=None):
+def format_json_output(input_path, input_hw, text_lines, confidence=False, word_boxes=None, orientation=None, normalize=None, skew=None, outline=None, rules=None, despeckle=None, binarize=None, morph=None, frame=None, rank=None):
     """output.rs:98-101 (serde_json::to_string_pretty).  serde_json without `preserve_order` keeps `json!` maps in a
     BTreeMap, so the reference emits every object's keys in alphabetical order (ocrs-cli/test-data/
     format-json-expected.json: image_height, image_width, paragraphs, url / text, vertices, words): sort_keys."""
-    return json.dumps(ocr_json(input_path, input_hw, text_lines, confidence, word_boxes, orientation, normalize, skew, outline, rules, despeckle, binarize, morph, frame), indent=2, ensure_ascii=False,
+    return json.dumps(ocr_json(input_path, input_hw, text_lines, confidence, word_boxes, orientation, normalize, skew, outline, rules, despeckle, binarize, morph, frame, rank), indent=2, ensure_ascii=False,
                       sort_keys=True)
 
 
