@@ -1119,6 +1119,83 @@ OCRS_API ocrs_status ocrs_engine_crop_page(const ocrs_engine* e, const ocrs_page
 OCRS_API ocrs_status ocrs_engine_crop_pages(const ocrs_engine* e, const ocrs_page* const* pages, size_t n, const ocrs_crop_rect* rects,
                                             const float* fill, ocrs_page** out_pages);
 
+/* ------------------------------------------------------------------------
+ * Page measurement (no reference counterpart, opt-in).  Every parameter of the page operations above is in
+ * pixels, and a good value depends on how large the text of this scan is.  This measures it on the device, without a
+ * detector: the page's stroke width from run-length histograms and its text height from the bounding boxes of its connected
+ * components, so that the working resolution ("Working resolution" above) can follow from the page instead of being set
+ * blind.  No page is made and no pixel is written.  The page is dark ink on light paper (ocrs_engine_normalize_page makes it
+ * so).  What a trained detector gains from the derived scale is uncalibrated.
+ *
+ * 1. ocrs_engine_measure_pages fills out_infos[n] for n pages of any sizes, each with its own params[i], in five launches
+ * for the whole batch on one stream.  The definition (tests/measure_ref.py restates it and the library equals it in every
+ * field and bin; integer and set arithmetic, so the record does not depend on schedule or batch):
+ *   ink        v < threshold, an ordinary float compare: NaN is not ink, v == threshold is not, -inf is.
+ *   components the 8-connected components of ink; the page edge is a wall.  counted: those of area >= min_area.
+ *   run_h, run_v  the maximal horizontal / vertical runs of ink by their length L, at index min(L, 255); the page edge ends a
+ *              run; index 0 stays 0.
+ *   comp_h, comp_w  the counted components by the height / width of their bounding box, at index min(side, 255).
+ *   area_by_h  the summed areas of the counted components, by the index of comp_h.
+ * ocrs_measure_params_default: threshold 0, min_area 4.  ocrs_measure_params_check (host only): OCRS_ERR_INVALID_ARGUMENT for
+ * a threshold that is not finite or a min_area outside 0 .. 65535; the engine calls refuse the same, and a page with a side
+ * over 65535 or with more than 2^31 - 1 pixels.  The workspace is 20 bytes and one bit per pixel; a batch of more than 2^31
+ * tiles of 64 x 64, or whose workspace exceeds the device's memory, fails with OCRS_ERR_CAPACITY before anything is launched.
+ * n == 0 succeeds and launches nothing.  A call that fails writes no output.  ocrs_engine_measure_page: params == NULL means
+ * the default.
+ *
+ * 2. ocrs_measure_choose (host only) makes a scale out of one record:
+ *   stroke     with r[L] = run_h[L] + run_v[L], the L in 1 .. 254 that maximises L * r[L], the pixels that lie in runs of that
+ *              length; the smallest L on a tie; 0 when no run is shorter than 255.
+ *   text_height  min_height_strokes is taken in 1/256: q = floor(min_height_strokes * 256 + 0.5).  A height H in 1 .. 254
+ *              qualifies when 256 H >= q * stroke (integers).  support = the counted components of a qualifying height.
+ *              text_height = the lower median of the qualifying heights by ink: the smallest qualifying H at which the
+ *              cumulative area_by_h reaches half of its sum over the qualifying heights, rounded up; 0 with no support.
+ *              Bin 255 (a picture, a rule) never qualifies; dots, commas and dashes hold next to no ink.
+ *   blank      support == 0.
+ * ocrs_measure_choice_params_default: min_height_strokes 0.5; _check: INVALID_ARGUMENT unless it is finite and 0 .. 255.
+ * ocrs_measure_choose refuses the same; params == NULL means the default.
+ *
+ * 3. ocrs_work_scale_for_text (host only): *scale = target_height / text_height clamped to [min_scale, max_scale], in double;
+ * 1.0 for text_height <= 0 (a blank page keeps its size).  INVALID_ARGUMENT unless target_height is finite and positive and
+ * 0 < min_scale <= max_scale, both finite.  Its result feeds ocrs_work_size.  OCRS_WORK_TEXT_HEIGHT_DEFAULT is the text
+ * height tests/measure_ref.py finds on the benchmark's synthetic pages, the size the synthetic detector
+ * was made for; for real models it is uncalibrated. */
+#define OCRS_MEASURE_BINS 256
+#define OCRS_WORK_TEXT_HEIGHT_DEFAULT 14
+typedef struct ocrs_measure_params {
+    float threshold;       /* finite; ink is v < threshold */
+    int32_t min_area;      /* 0 .. 65535: a component of fewer pixels is a speck and is not counted */
+} ocrs_measure_params;
+typedef struct ocrs_measure_info {
+    uint64_t ink;          /* pixels under the threshold */
+    uint32_t components;   /* 8-connected components of ink */
+    uint32_t counted;      /* those of area >= min_area */
+    uint32_t run_h[OCRS_MEASURE_BINS];      /* horizontal runs by min(length, 255) */
+    uint32_t run_v[OCRS_MEASURE_BINS];      /* vertical runs by min(length, 255) */
+    uint32_t comp_h[OCRS_MEASURE_BINS];     /* counted components by min(box height, 255) */
+    uint32_t comp_w[OCRS_MEASURE_BINS];     /* counted components by min(box width, 255) */
+    uint64_t area_by_h[OCRS_MEASURE_BINS];  /* their summed areas by min(box height, 255) */
+} ocrs_measure_info;
+typedef struct ocrs_measure_choice_params {
+    double min_height_strokes;  /* 0 .. 255, taken in 1/256 */
+} ocrs_measure_choice_params;
+typedef struct ocrs_text_scale {
+    int32_t stroke;        /* pixels; 0: no run shorter than 255 */
+    int32_t text_height;   /* pixels; 0: blank */
+    uint32_t support;      /* the components that entered the median */
+    int32_t blank;         /* 1: support == 0 */
+} ocrs_text_scale;
+OCRS_API ocrs_status ocrs_measure_params_default(ocrs_measure_params* out);
+OCRS_API ocrs_status ocrs_measure_params_check(const ocrs_measure_params* params);
+OCRS_API ocrs_status ocrs_engine_measure_page(const ocrs_engine* e, const ocrs_page* page, const ocrs_measure_params* params,
+                                              ocrs_measure_info* out_info);
+OCRS_API ocrs_status ocrs_engine_measure_pages(const ocrs_engine* e, const ocrs_page* const* pages, size_t n,
+                                               const ocrs_measure_params* params, ocrs_measure_info* out_infos);
+OCRS_API ocrs_status ocrs_measure_choice_params_default(ocrs_measure_choice_params* out);
+OCRS_API ocrs_status ocrs_measure_choice_params_check(const ocrs_measure_choice_params* params);
+OCRS_API ocrs_status ocrs_measure_choose(const ocrs_measure_info* info, const ocrs_measure_choice_params* params, ocrs_text_scale* out);
+OCRS_API ocrs_status ocrs_work_scale_for_text(int text_height, double target_height, double min_scale, double max_scale, double* scale);
+
 /* OcrEngine::detection_threshold (lib.rs:282-287). */
 OCRS_API float ocrs_engine_detection_threshold(const ocrs_engine* e);
 

@@ -6,6 +6,7 @@ Python mirror (ctypes) of the reference's public surface (ocrs/src/lib.rs:29-31,
 `trait Model` seam (ocrs/src/model.rs:6-17).  All compute happens in
 libocrs_amd.so (HIP, gfx950); this module only marshals arrays.
 """
+import collections
 import ctypes as C
 import math
 
@@ -17,7 +18,8 @@ from ._lib import OcrsError, check, lib
 __all__ = ["OcrEngine", "OcrEngineParams", "ImageSource", "ImageSourceError", "DimOrder", "DecodeMethod", "Model",
            "OcrInput", "TextLine", "TextWord", "TextChar", "OcrsError", "DEFAULT_ALPHABET", "EngineGroup", "line_frame",
            "Orientation", "orientation_vote", "unrotate_rects", "unrotate_lines", "work_size", "rescale_rects", "normalize_params", "rules_params", "speckle_params", "binarize_params", "morph_params", "rank_params",
-           "frame_params", "frame_choose", "uncrop_rects", "uncrop_boxes", "uncrop_lines"]
+           "frame_params", "frame_choose", "uncrop_rects", "uncrop_boxes", "uncrop_lines",
+           "measure_params", "measure_choose", "work_scale_for_text", "TextScale", "WORK_TEXT_HEIGHT_DEFAULT"]
 
 # lib.rs:34 (with the EUR sign the comment at lib.rs:33 asks for)
 DEFAULT_ALPHABET = " 0123456789!\"#$%&'()*+,-./:;<=>?@[\\]^_`{|}~€ABCDEFGHIJKLMNOPQRSTUVWXYZabcdefghijklmnopqrstuvwxyz"
@@ -684,6 +686,54 @@ def frame_choose(page_hw, col_ink, row_ink, min_count=None, pad=None, gutter_min
     return out.as_dict()
 
 
+def measure_params(threshold=None, min_area=None):
+    """ocrs_measure_params as a dict: ocrs_measure_params_default (threshold 0, min_area 4) with the given
+    fields replaced, checked by ocrs_measure_params_check (host only)."""
+    p = _measure_struct(threshold, min_area)
+    check(lib().ocrs_measure_params_check(C.byref(p)))
+    return {"threshold": float(p.threshold), "min_area": int(p.min_area)}
+
+
+def _measure_struct(threshold=None, min_area=None):
+    p = _lib.MeasureParams()
+    check(lib().ocrs_measure_params_default(C.byref(p)))
+    if threshold is not None:
+        p.threshold = float(threshold)
+    if min_area is not None:
+        p.min_area = int(max(-1, min(int(min_area), 1 << 30)))   # out of range is the library's to refuse
+    return p
+
+
+TextScale = collections.namedtuple("TextScale", ("stroke", "text_height", "support", "blank"))
+TextScale.__doc__ = """ocrs_text_scale (DESIGN.md §7.14): stroke and text_height in pixels (0: none found), support (the
+components that entered the median) and blank (bool: support == 0)."""
+WORK_TEXT_HEIGHT_DEFAULT = _lib.WORK_TEXT_HEIGHT_DEFAULT   # include/ocrs_amd.h OCRS_WORK_TEXT_HEIGHT_DEFAULT
+WORK_TEXT_SCALE_RANGE = (0.125, 4.0)   # what detect_words(work_text_height=...) keeps the derived scale within
+
+
+def measure_choose(info, min_height_strokes=None):
+    """ocrs_measure_choose (host only): the scale of a page from its measurement (OcrEngine.measure's dict)
+    -> TextScale.  min_height_strokes: None is the default, 0.5."""
+    p = _lib.MeasureChoiceParams()
+    check(lib().ocrs_measure_choice_params_default(C.byref(p)))
+    if min_height_strokes is not None:
+        p.min_height_strokes = float(min_height_strokes)
+    rec = _lib.MeasureInfo.from_dict(info)
+    out = _lib.TextScaleC()
+    check(lib().ocrs_measure_choose(C.byref(rec), C.byref(p), C.byref(out)))
+    return TextScale(int(out.stroke), int(out.text_height), int(out.support), bool(out.blank))
+
+
+def work_scale_for_text(text_height, target_height=None, min_scale=WORK_TEXT_SCALE_RANGE[0], max_scale=WORK_TEXT_SCALE_RANGE[1]):
+    """ocrs_work_scale_for_text (host only): the scale that brings text of text_height pixels to target_height (None:
+    WORK_TEXT_HEIGHT_DEFAULT), kept within [min_scale, max_scale]; 1.0 for a blank page (text_height 0).  Feeds work_size."""
+    out = C.c_double(0.0)
+    target = WORK_TEXT_HEIGHT_DEFAULT if target_height is None else target_height
+    check(lib().ocrs_work_scale_for_text(C.c_int(int(text_height)), C.c_double(float(target)), C.c_double(float(min_scale)),
+                                         C.c_double(float(max_scale)), C.byref(out)))
+    return out.value
+
+
 def uncrop_rects(rects, origin):
     """ocrs_uncrop_rects (host only): word rects found on a page cut out at origin = (x0, y0) -> the same rects in the frame
     of the page it was cut from, float32 [n, 6] (a copy)."""
@@ -1098,17 +1148,23 @@ class OcrEngine:
         return o
 
     # ---- the page operations with parameters per page
-    def _page_op_batch(self, name, entry, params_cls, struct_of, info_cls, inputs, params, mask, info):
-        """<name>_batch: `entry` on the pages of `inputs`, page i with the params struct struct_of(**params[i]) (a dict of
-        keywords, or None for the default; `params` is one for all, or one per page).  mask: None for an entry point that
-        takes no masks.  -> pages, or (pages[, masks][, infos])."""
+    @staticmethod
+    def _page_op_args(name, params_cls, struct_of, inputs, params):
+        """The pages of `inputs` and their parameter structs, as arrays: page i with struct_of(**params[i]) (a dict of
+        keywords, or None for the default; `params` is one for all, or one per page)."""
         n = len(inputs)
         if params is None or isinstance(params, dict):
             params = [params] * n
         if len(params) != n:
             raise ValueError("%s_batch: one parameter set per page" % name)
-        pages = _page_array(inputs)
-        ps = (params_cls * n)(*[struct_of(**(p or {})) for p in params])
+        return _page_array(inputs), (params_cls * n)(*[struct_of(**(p or {})) for p in params])
+
+    def _page_op_batch(self, name, entry, params_cls, struct_of, info_cls, inputs, params, mask, info):
+        """<name>_batch: `entry` on the pages of `inputs`, page i with the params struct struct_of(**params[i]) (a dict of
+        keywords, or None for the default; `params` is one for all, or one per page).  mask: None for an entry point that
+        takes no masks.  -> pages, or (pages[, masks][, infos])."""
+        n = len(inputs)
+        pages, ps = self._page_op_args(name, params_cls, struct_of, inputs, params)
         out = (C.c_void_p * n)()
         masks = (C.POINTER(C.c_uint8) * n)()
         infos = (info_cls * n)()
@@ -1279,6 +1335,33 @@ class OcrEngine:
                                              c.ctypes.data_as(C.POINTER(C.c_uint32)) if cols else None,
                                              r.ctypes.data_as(C.POINTER(C.c_uint32)) if rows else None))
         return c, r
+
+    # ---- page measurement
+    def measure(self, inp, threshold=0.0, min_area=4):
+        """ocrs_engine_measure_page: the page's run-length and component histograms -> {"ink", "components", "counted"
+        (ints), "run_h", "run_v", "comp_h", "comp_w" (uint32 [256]), "area_by_h" (uint64 [256])}: exact integers, equal to
+        tests/measure_ref.py in every bin.  Ink is v < threshold; a component of fewer than min_area pixels (0 .. 65535) is
+        not counted.  The page is not changed and none is made."""
+        return self.measure_batch([inp], [{"threshold": threshold, "min_area": min_area}])[0]
+
+    def measure_batch(self, inputs, params=None):
+        """ocrs_engine_measure_pages: pages of any sizes, each with its own parameters (a dict of measure's keywords, or
+        None for the default; one for all, or one per page), all passes for the whole batch on one stream -> infos."""
+        n = len(inputs)
+        pages, ps = self._page_op_args("measure", _lib.MeasureParams, _measure_struct, inputs, params)
+        infos = (_lib.MeasureInfo * n)()
+        check(lib().ocrs_engine_measure_pages(self._h, pages, C.c_size_t(n), ps, infos))
+        return [infos[i].as_dict() for i in range(n)]
+
+    def text_scale(self, inp, min_height_strokes=None, **kw):
+        """measure (keywords threshold, min_area) followed by measure_choose -> TextScale."""
+        return measure_choose(self.measure(inp, **kw), min_height_strokes)
+
+    def _work_size_for_text(self, inp, target_height=True, **kw):
+        """The work size at which the page's text is target_height pixels tall (True: WORK_TEXT_HEIGHT_DEFAULT): text_scale
+        (its keywords in kw), work_scale_for_text within [1/8, 4], work_size.  A blank page keeps its size."""
+        target = None if target_height is True else target_height
+        return work_size(inp.shape[-2:], scale=work_scale_for_text(self.text_scale(inp, **kw).text_height, target))
 
     def crop(self, inp, rect, fill=0.5):
         """ocrs_engine_crop_page: rect = (x0, y0, x1, y1), half open, cut out of the page as a new resident page of (y1 - y0)
@@ -1468,14 +1551,21 @@ class OcrEngine:
         return _new_inputs(out, n)
 
     # ---- lib.rs:193-199
-    def detect_words(self, inp, scores=False, tiled=False, work_size=None, work_filter="auto"):
+    def detect_words(self, inp, scores=False, tiled=False, work_size=None, work_filter="auto", work_text_height=None):
         """scores=True: through ocrs_engine_detect_words_scored -> (words, score float32 [n], pixels uint32 [n]): per word
         the mean text probability of its component's pixels and their number.
         tiled=True | <overlap>: through ocrs_engine_detect_words_tiled: the page is cut into model-sized tiles at its own
         resolution instead of being resized to the model input (about one detector run per tile).
         work_size=(h, w): through ocrs_engine_detect_words_at: the detector sees the page resampled to that size (filter
         work_filter, as resize) and the words come back in the page's own frame; scores and pixels are those of the work
-        page.  work_size() makes one from a scale or a longest side."""
+        page.  work_size() makes one from a scale or a longest side.
+        work_text_height=N | True: the work size is the one at which the page's measured text is N pixels tall (True:
+        WORK_TEXT_HEIGHT_DEFAULT), within a scale of 1/8 .. 4 (text_scale, work_scale_for_text, work_size); then as work_size.  Not
+        together with work_size.  None launches nothing more than before."""
+        if work_text_height is not None and work_text_height is not False:
+            if work_size is not None:
+                raise ValueError("detect_words: work_size or work_text_height, not both")
+            work_size = self._work_size_for_text(inp, work_text_height)
         if work_size is not None:
             out = self.detect_words_batch([inp], scores, tiled, [work_size], work_filter)
             return tuple(o[0] for o in out) if scores else out[0]
@@ -1749,7 +1839,8 @@ class OcrEngine:
 
     # ---- lib.rs:290-300
     def get_text(self, inp, rectify=False, orientation=None, work_size=None, normalize=None, deskew=None, deskew_fill=0.5,
-                 perspective=None, perspective_fill=0.5, rules=None, despeckle=None, binarize=None, morph=None, frame=None, rank=None):
+                 perspective=None, perspective_fill=0.5, rules=None, despeckle=None, binarize=None, morph=None, frame=None, rank=None,
+                 work_text_height=None):
         """rectify=True: the same sequence (detect_words, find_text_lines, recognize_text) with rectified crops.
         orientation: None reads the page as given; an int turns it by that many quarter turns counter-clockwise first
         (rotate); "auto" by what detect_orientation finds.
@@ -1785,6 +1876,10 @@ class OcrEngine:
         rank: None reads the page as given; True or a dict of rank()'s keywords reads the page with its grain removed
         (DESIGN.md §7.13).  Applied after perspective and normalisation and before binarisation, which would turn grain into
         specks: everything downstream sees the cleaned page.  Coordinates do not move.
+        work_text_height: None reads the page as given; N or True detects the words at the size at which the measured text
+        is N pixels (True: WORK_TEXT_HEIGHT_DEFAULT) tall.  The page is measured as the detector will
+        see it, after every operation above; lines and text are read at full resolution, as with work_size.  Not together
+        with work_size.
         get_text returns text alone; callers that want boxes run the steps
         themselves and bring them back last with unproject_rects / unproject_lines."""
         if perspective is not None:
@@ -1808,8 +1903,12 @@ class OcrEngine:
             inp = self.remove_rules(inp, **({} if rules is True else dict(rules)))
         if morph is not None and morph is not False:
             inp = self.morph(inp, **({} if morph is True else dict(morph)))
-        if work_size is not None or rectify:
-            lines = self.find_text_lines(inp, self.detect_words(inp, work_size=work_size))
+        if work_text_height is False:
+            work_text_height = None
+        if work_size is not None and work_text_height is not None:
+            raise ValueError("get_text: work_size or work_text_height, not both")
+        if work_size is not None or work_text_height is not None or rectify:
+            lines = self.find_text_lines(inp, self.detect_words(inp, work_size=work_size, work_text_height=work_text_height))
             return "\n".join(str(t) for t in self.recognize_text(inp, lines, rectify=rectify) if t is not None)
         txt = C.c_char_p()
         check(lib().ocrs_engine_get_text(self._h, inp._h, C.byref(txt)))

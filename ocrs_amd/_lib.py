@@ -98,12 +98,16 @@ DECLARED_SYMBOLS = [
     "ocrs_frame_params_default", "ocrs_frame_params_check", "ocrs_engine_clean_frame_page", "ocrs_engine_clean_frame_pages",
     "ocrs_engine_ink_profiles", "ocrs_frame_choice_params_default", "ocrs_frame_choice_params_check", "ocrs_frame_choose",
     "ocrs_engine_crop_page", "ocrs_engine_crop_pages", "ocrs_uncrop_rects", "ocrs_uncrop_chars",
+    "ocrs_measure_params_default", "ocrs_measure_params_check", "ocrs_engine_measure_page", "ocrs_engine_measure_pages",
+    "ocrs_measure_choice_params_default", "ocrs_measure_choice_params_check", "ocrs_measure_choose", "ocrs_work_scale_for_text",
 ]
 
 ABI_VERSION = 6   # include/ocrs_amd.h OCRS_ABI_VERSION
 TILE_OVERLAP_DEFAULT = 100   # include/ocrs_amd.h OCRS_TILE_OVERLAP_DEFAULT
 RESAMPLE_FILTERS = {"auto": 0, "bilinear": 1, "area": 2}   # include/ocrs_amd.h ocrs_resample_filter
 POLARITIES = {"auto": 0, "keep": 1, "invert": 2}   # include/ocrs_amd.h ocrs_polarity
+MEASURE_BINS = 256   # include/ocrs_amd.h OCRS_MEASURE_BINS
+WORK_TEXT_HEIGHT_DEFAULT = 14   # include/ocrs_amd.h OCRS_WORK_TEXT_HEIGHT_DEFAULT
 
 
 class NormalizeParams(C.Structure):   # include/ocrs_amd.h ocrs_normalize_params
@@ -201,6 +205,46 @@ class FrameChoice(C.Structure):   # include/ocrs_amd.h ocrs_frame_choice
 
     def as_dict(self):
         return {name: int(getattr(self, name)) for name, _ in self._fields_}
+
+
+class MeasureParams(C.Structure):   # include/ocrs_amd.h ocrs_measure_params
+    _fields_ = [("threshold", C.c_float), ("min_area", C.c_int32)]
+
+
+class MeasureInfo(C.Structure):   # include/ocrs_amd.h ocrs_measure_info
+    _fields_ = [("ink", C.c_uint64), ("components", C.c_uint32), ("counted", C.c_uint32), ("run_h", C.c_uint32 * MEASURE_BINS),
+                ("run_v", C.c_uint32 * MEASURE_BINS), ("comp_h", C.c_uint32 * MEASURE_BINS), ("comp_w", C.c_uint32 * MEASURE_BINS),
+                ("area_by_h", C.c_uint64 * MEASURE_BINS)]
+
+    def as_dict(self):
+        import numpy as np
+        out = {}
+        for name, _ in self._fields_:   # exact integers: Python ints and uint32 / uint64 [256] arrays
+            v = getattr(self, name)
+            out[name] = int(v) if isinstance(v, int) else np.array(v[:], np.uint64 if name == "area_by_h" else np.uint32)
+        return out
+
+    @classmethod
+    def from_dict(cls, info):
+        import numpy as np
+        out = cls()
+        for name, _ in cls._fields_:
+            if name in ("ink", "components", "counted"):
+                setattr(out, name, int(info[name]))
+            else:
+                a = np.asarray(info[name])
+                if a.shape != (MEASURE_BINS,):
+                    raise ValueError("measure info: %s holds %d bins" % (name, MEASURE_BINS))
+                getattr(out, name)[:] = [int(v) for v in a.tolist()]
+        return out
+
+
+class MeasureChoiceParams(C.Structure):   # include/ocrs_amd.h ocrs_measure_choice_params
+    _fields_ = [("min_height_strokes", C.c_double)]
+
+
+class TextScaleC(C.Structure):   # include/ocrs_amd.h ocrs_text_scale
+    _fields_ = [("stroke", C.c_int32), ("text_height", C.c_int32), ("support", C.c_uint32), ("blank", C.c_int32)]
 
 
 class CropRect(C.Structure):   # include/ocrs_amd.h ocrs_crop_rect

@@ -17,6 +17,8 @@ import sys
 
 import numpy as np
 
+from . import _lib
+
 
 def load_image(path):
     """main.rs:312-323: image::open(..).into_rgb8() -> [H, W, 3] u8."""
@@ -31,6 +33,14 @@ def write_image(path, chw_or_hw):
     a = np.asarray(chw_or_hw, np.float32)
     a = a.reshape(a.shape[-2], a.shape[-1])
     Image.fromarray((np.clip(a, np.float32(0.0), np.float32(1.0)) * np.float32(255.0)).astype(np.uint8), "L").save(path)
+
+
+def positive_int(text):
+    """argparse type of --work-text-height N."""
+    n = int(text)
+    if n <= 0:
+        raise argparse.ArgumentTypeError("a positive number of pixels, not %r" % text)
+    return n
 
 
 def main(argv=None):
@@ -72,6 +82,16 @@ def main(argv=None):
     work.add_argument("--work-max-side", type=int, metavar="N",
                       help="as --work-scale with S = min(1, N / the page's longer side): the detector sees a page of at most N "
                            "pixels a side")
+    work.add_argument("--work-text-height", type=positive_int, nargs="?", const=True, default=None, metavar="N",
+                      help="as --work-scale with the S at which the page's text is N pixels tall (default %d), within 1/8 to 4: the "
+                           "text height is measured on the GPU from the page's connected components, without a detector, on the "
+                           "page as the detector will see it; N is a positive number of pixels (write --work-text-height=N, or put another "
+                           "option after the bare flag, so that the image path is not read as N); a blank page keeps its size; implies what --measure reports (no "
+                           "reference counterpart; for real models the default is uncalibrated: DESIGN.md 7.14)" % _lib.WORK_TEXT_HEIGHT_DEFAULT)
+    ap.add_argument("--measure", action="store_true",
+                    help="measure the page's stroke width and text height on the GPU (run-length histograms and the bounding boxes of "
+                         "connected components) and print them; with -j the JSON gains \"measure\" (no reference counterpart: "
+                         "DESIGN.md 7.14)")
     ap.add_argument("--normalize", action="store_true",
                     help="normalise the page on the GPU before reading it: the background is flattened (shadows, uneven light), "
                          "the levels are stretched (faint copies) and light text on a dark page is inverted; the JSON gains "
@@ -411,8 +431,21 @@ def main(argv=None):
         if args.work_scale is not None or args.work_max_side is not None:
             from . import work_size
             work_hw = work_size(inp.shape[-2:], scale=args.work_scale, max_side=args.work_max_side)
-            if args.debug:
-                print("Working resolution: %dx%d for a page of %dx%d" % (work_hw[1], work_hw[0], inp.shape[-1], inp.shape[-2]))
+        measure_info = None
+        if args.measure or args.work_text_height is not None:   # of the page as the detector will see it
+            from . import measure_choose, work_scale_for_text, work_size
+            record = engine.measure(inp)
+            scale = measure_choose(record)
+            measure_info = dict(scale._asdict(), ink=record["ink"], components=record["components"])
+            if args.work_text_height is not None:
+                work_hw = work_size(inp.shape[-2:], scale=work_scale_for_text(scale.text_height, None if args.work_text_height is True else args.work_text_height))
+            if args.debug or not args.json:
+                print("Measure: %s; %d pixels of ink in %d components"
+                      % ("a blank page: no text to measure" if scale.blank else
+                         "strokes of %d pixels, text %d pixels tall (over %d components)" % (scale.stroke, scale.text_height, scale.support),
+                         record["ink"], record["components"]))
+        if work_hw is not None and args.debug:
+            print("Working resolution: %dx%d for a page of %dx%d" % (work_hw[1], work_hw[0], inp.shape[-1], inp.shape[-2]))
         if args.text_map or args.text_mask:   # with a working resolution: the map of the work page, at its size
             tm = engine.detect_text_pixels(inp if work_hw is None else engine.resize(inp, work_hw), tiled=tiled)
             if args.text_map:
@@ -447,7 +480,7 @@ def main(argv=None):
             if word_boxes is not None:
                 word_boxes = [[(unrotate_rects([r], tuple(turn_hw), turns)[0], s, n) for r, s, n in boxes] for boxes in word_boxes]
         return {"texts": texts, "word_boxes": word_boxes, "words": words, "lines": lines, "turns": turns, "skew": skew,
-                "despeckle": speckle_info, "rules": rules_info, "morph": morph_info}
+                "despeckle": speckle_info, "rules": rules_info, "morph": morph_info, "measure": measure_info}
 
     # the pages to read and where each lies on the page as it is here: the content box, the two pages of a spread, or the page
     parts, frame_info = [(inp, None)], None
@@ -484,6 +517,7 @@ def main(argv=None):
         words, lines = list(words) + list(got["words"]), list(lines) + list(got["lines"])
         if n_part == 0:   # what the later steps report is what they found on the first page
             turns, skew, speckle_info, rules_info, morph_info = got["turns"], got["skew"], got["despeckle"], got["rules"], got["morph"]
+            measure_info = got["measure"]
     if quad_m is not None:
         from . import unproject_lines, unproject_rects
         texts = unproject_lines(texts, quad_m)
@@ -498,7 +532,7 @@ def main(argv=None):
         content = output.format_json_output(args.image, tuple(shape_hw), texts, confidence=args.confidence, word_boxes=word_boxes,
                                             orientation=None if turns is None else 90 * turns, normalize=norm_info, skew=skew, outline=outline,
                                             rules=rules_info, despeckle=speckle_info, binarize=binarize_info, morph=morph_info, frame=frame_info,
-                                            rank=rank_info)
+                                            rank=rank_info, measure=measure_info)
     else:
         content = output.format_text_output(texts)
     if args.output:

@@ -667,6 +667,37 @@ struct CropDesc {        // one rectangle cut out of a page: dst [oh, ow] = src 
 };
 void crop_pages(const CropDesc* d_descs, int n_pages, int total_blocks, hipStream_t s);
 
+// ---- kernels_measure.hip ----------------------------------
+constexpr int MEASURE_BINS = 256;        // a length, height or width L is counted at min(L, 255)
+constexpr int MEASURE_MAX_MIN_AREA = 65535;
+struct MeasureInfo {     // what a page's measurement counted: the layout of ocrs_measure_info
+    uint64_t ink;        // pixels under the threshold
+    uint32_t components; // 8-connected components of ink
+    uint32_t counted;    // those of area >= min_area
+    uint32_t run_h[MEASURE_BINS], run_v[MEASURE_BINS];     // maximal horizontal / vertical runs of ink by length
+    uint32_t comp_h[MEASURE_BINS], comp_w[MEASURE_BINS];   // counted components by the height / width of their box
+    uint64_t area_by_h[MEASURE_BINS];                      // their summed areas, by the height
+};
+struct MeasureDesc {     // one page that is measured; nothing is made of it
+    const float* src;    // [h, w]
+    unsigned long long* mask;    // the row-major ink bit mask of h * ww words (64 pixels a word, bits past the edge zero)
+    int32_t* labels;     // [h * w] the union-find forest over page-local pixel indices; written and read on ink alone
+    uint32_t* area;      // [h * w] at a root: the pixels of its component.  This and the three box words are written at
+    uint32_t* x0;        // [h * w] the heads of the in-word runs of ink alone: a root is one of them.  The least x,
+    uint32_t* x1;        // [h * w] the largest x
+    uint32_t* y1;        // [h * w] and the largest y of its component; the least y is that of the root itself
+    MeasureInfo* info;   // zero when the first launch starts; every launch adds to it
+    int32_t h, w;        // each 1 .. 65535, h * w < 2^31
+    int32_t ww;          // ceil(w / 64)
+    int32_t block0;      // first block of this page: the sum of measure_tiles() of the pages before it
+    int32_t min_area;    // 0 .. 65535
+    float threshold;
+};
+int64_t measure_tiles(int h, int w);        // blocks a page of this size takes (host)
+size_t measure_mask_words(int h, int w);    // 64-bit words of MeasureDesc::mask (host)
+// Pages of any mix of sizes and parameters, five launches on `s`; total_blocks = the sum of measure_tiles() over the pages.
+void measure_pages(const MeasureDesc* d_descs, int n_pages, int total_blocks, hipStream_t s);
+
 // kernels_peaks.hip
 void measure_peaks(double* mfma_tflops, double* copy_gbps);
 
