@@ -1196,6 +1196,74 @@ OCRS_API ocrs_status ocrs_measure_choice_params_check(const ocrs_measure_choice_
 OCRS_API ocrs_status ocrs_measure_choose(const ocrs_measure_info* info, const ocrs_measure_choice_params* params, ocrs_text_scale* out);
 OCRS_API ocrs_status ocrs_work_scale_for_text(int text_height, double target_height, double min_scale, double max_scale, double* scale);
 
+/* ------------------------------------------------------------------------
+ * Reverse-video repair (no reference counterpart, opt-in).  Every page operation above takes one polarity
+ * for the whole page, but a table's header row in white on a dark band, the buttons, banners and sidebars of a screenshot, a
+ * dark code pane beside a light document, a pull-quote or the reversed title block of a form are light text on a solid dark
+ * panel.  There the panel is "ink" and its text "paper": a whole-page inversion only swaps which half of the page is lost.
+ * These calls make a new resident page of the same size on which the solid dark panels that enclose light marks, and what
+ * they enclose, are inverted: pages are centred on 0, so the sign bit of those pixels is flipped.  Every result pixel is the
+ * source's 32-bit word or that word XOR 0x80000000 (NaN payloads, -0.0 and denormals included); coordinates do not move,
+ * so nothing needs mapping back.  The source page is untouched; release both with ocrs_page_free in any order.  Call it
+ * before ocrs_engine_clean_frame_page, which would remove a sidebar that touches the edge as a bar.  What a trained
+ * detector or recogniser gains is uncalibrated.
+ *
+ * The definition (tests/reverse_ref.py restates it and the library equals it bit for bit; integer and set arithmetic on
+ * sets taken from the input page, nothing iterated but the labelling, so the result does not depend on schedule or batch):
+ *   ink        v < threshold, an ordinary float compare: NaN is not ink, v == threshold is not.  Its 8-connected components
+ *              have an area A and a bounding box of bh x bw; the page edge is a wall.
+ *   candidates a component with bh >= min_height, bw >= min_width and 256 A >= q bh bw in 64-bit integers, q = floor(256
+ *              min_fill + 0.5) in float.  M = the candidates' pixels.  A table grid or a page frame fails the fill test, a
+ *              letter the size test.
+ *   holes      everything outside M (paper, NaN, the ink of non-candidates) is 4-connected.  A component that holds a pixel
+ *              of the page's first or last row or column is open; every other is a hole of area a.  Its encloser is the
+ *              candidate that owns the pixel west of the hole's raster-first pixel (least row, then least column).  A hole
+ *              counts when max_hole == 0 or a <= max_hole: a large light card inside a panel stays as it is.
+ *   panels     a candidate that is the encloser of at least min_holes counting holes.  The default of 3 keeps a bold
+ *              headline O, B or 8 out; with 0 every candidate is a panel and solid bars turn white.
+ *   output     the sign bit flipped on every pixel of a panel and of a counting hole whose encloser is a panel; the page's
+ *              own word elsewhere.
+ * Not covered: a panel whose light text touches the panel's edge (open, not a hole), light text on dark with no solid
+ * panel around it, nested panels beyond what the definition gives.
+ *
+ * ocrs_reverse_params_default: threshold 0, min_height 32, min_width 64, min_fill 0.4, min_holes 3, max_hole 0.  All five
+ * are UNCALIBRATED: no real scans stand behind them.
+ * ocrs_reverse_params_check (host only): OCRS_ERR_INVALID_ARGUMENT for a threshold that is not finite, a min_height or
+ * min_width outside 1 .. 65535, a min_fill outside [0, 1] or NaN, a negative min_holes or max_hole; the engine calls refuse
+ * the same, and a page with a side over 65535 or with more than 2^31 - 1 pixels; OCRS_ERR_CAPACITY for a batch of more than
+ * 2^31 tiles of 64 x 64 or whose workspace (20 bytes a pixel) exceeds the device's memory, before anything is allocated.
+ * ocrs_engine_unreverse_pages serves n pages of any sizes, each with its own params[i], in nine launches for the whole batch
+ * on one stream; out_pages[n] receives the pages, out_infos[n] (may be NULL) what was found, out_masks[n] (may be NULL) per
+ * page a host uint8 [h][w], to be released with ocrs_buffer_free: bit 0 inverted, bit 1 in M, bit 2 in a panel, bit 3 in a
+ * hole (counting or not, whatever its encloser).
+ * ocrs_engine_unreverse_page: params == NULL means the default. */
+typedef struct ocrs_reverse_params {
+    float threshold;       /* finite; ink is v < threshold */
+    int32_t min_height;    /* 1 .. 65535: the least height of a candidate's box (default 32, uncalibrated) */
+    int32_t min_width;     /* 1 .. 65535: the least width of a candidate's box (default 64, uncalibrated) */
+    float min_fill;        /* [0, 1]: the least share of its box a candidate fills, taken in 1/256 (default 0.4, uncalibrated) */
+    int32_t min_holes;     /* >= 0: the counting holes that make a candidate a panel (default 3, uncalibrated) */
+    int32_t max_hole;      /* >= 0 pixels: the largest hole that counts and is inverted; 0: no limit (default 0, uncalibrated) */
+} ocrs_reverse_params;
+typedef struct ocrs_reverse_info {
+    uint64_t ink;            /* pixels under the threshold */
+    uint64_t components;     /* 8-connected components of ink */
+    uint64_t candidates;     /* those large and solid enough */
+    uint64_t panels;         /* candidates with at least min_holes counting holes */
+    uint64_t panel_pixels;   /* their pixels */
+    uint64_t holes;          /* counting holes of panels */
+    uint64_t hole_pixels;    /* their pixels */
+    uint64_t skipped_holes;  /* holes of panels over max_hole: not inverted */
+    uint64_t inverted;       /* panel_pixels + hole_pixels */
+} ocrs_reverse_info;
+OCRS_API ocrs_status ocrs_reverse_params_default(ocrs_reverse_params* out);
+OCRS_API ocrs_status ocrs_reverse_params_check(const ocrs_reverse_params* params);
+OCRS_API ocrs_status ocrs_engine_unreverse_page(const ocrs_engine* e, const ocrs_page* page, const ocrs_reverse_params* params,
+                                                ocrs_page** out_page, uint8_t** out_mask, ocrs_reverse_info* out_info);
+OCRS_API ocrs_status ocrs_engine_unreverse_pages(const ocrs_engine* e, const ocrs_page* const* pages, size_t n,
+                                                 const ocrs_reverse_params* params, ocrs_page** out_pages, uint8_t** out_masks,
+                                                 ocrs_reverse_info* out_infos);
+
 /* OcrEngine::detection_threshold (lib.rs:282-287). */
 OCRS_API float ocrs_engine_detection_threshold(const ocrs_engine* e);
 

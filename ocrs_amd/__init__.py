@@ -17,7 +17,7 @@ from ._lib import OcrsError, check, lib
 
 __all__ = ["OcrEngine", "OcrEngineParams", "ImageSource", "ImageSourceError", "DimOrder", "DecodeMethod", "Model",
            "OcrInput", "TextLine", "TextWord", "TextChar", "OcrsError", "DEFAULT_ALPHABET", "EngineGroup", "line_frame",
-           "Orientation", "orientation_vote", "unrotate_rects", "unrotate_lines", "work_size", "rescale_rects", "normalize_params", "rules_params", "speckle_params", "binarize_params", "morph_params", "rank_params",
+           "Orientation", "orientation_vote", "unrotate_rects", "unrotate_lines", "work_size", "rescale_rects", "normalize_params", "rules_params", "speckle_params", "reverse_params", "binarize_params", "morph_params", "rank_params",
            "frame_params", "frame_choose", "uncrop_rects", "uncrop_boxes", "uncrop_lines",
            "measure_params", "measure_choose", "work_scale_for_text", "TextScale", "WORK_TEXT_HEIGHT_DEFAULT"]
 
@@ -704,6 +704,35 @@ def _measure_struct(threshold=None, min_area=None):
     return p
 
 
+def reverse_params(min_height=None, min_width=None, min_fill=None, min_holes=None, max_hole=None, threshold=None):
+    """ocrs_reverse_params as a dict: ocrs_reverse_params_default (min_height 32, min_width 64, min_fill
+    0.4, min_holes 3, max_hole 0 = no limit, threshold 0; the five are uncalibrated) with the given fields replaced, checked
+    by ocrs_reverse_params_check (host only)."""
+    p = _reverse_struct(min_height, min_width, min_fill, min_holes, max_hole, threshold)
+    check(lib().ocrs_reverse_params_check(C.byref(p)))
+    return {"min_height": int(p.min_height), "min_width": int(p.min_width), "min_fill": float(p.min_fill), "min_holes": int(p.min_holes),
+            "max_hole": int(p.max_hole), "threshold": float(p.threshold)}
+
+
+def _reverse_struct(min_height=None, min_width=None, min_fill=None, min_holes=None, max_hole=None, threshold=None):
+    p = _lib.ReverseParams()
+    check(lib().ocrs_reverse_params_default(C.byref(p)))
+    clip = lambda v: int(max(-1, min(int(v), (1 << 31) - 1)))   # out of range is the library's to refuse
+    if min_height is not None:
+        p.min_height = clip(min_height)
+    if min_width is not None:
+        p.min_width = clip(min_width)
+    if min_fill is not None:
+        p.min_fill = float(min_fill)
+    if min_holes is not None:
+        p.min_holes = clip(min_holes)
+    if max_hole is not None:
+        p.max_hole = clip(max_hole)
+    if threshold is not None:
+        p.threshold = float(threshold)
+    return p
+
+
 TextScale = collections.namedtuple("TextScale", ("stroke", "text_height", "support", "blank"))
 TextScale.__doc__ = """ocrs_text_scale (DESIGN.md §7.14): stroke and text_height in pixels (0: none found), support (the
 components that entered the median) and blank (bool: support == 0)."""
@@ -1353,6 +1382,28 @@ class OcrEngine:
         check(lib().ocrs_engine_measure_pages(self._h, pages, C.c_size_t(n), ps, infos))
         return [infos[i].as_dict() for i in range(n)]
 
+    # ---- reverse-video repair
+    def unreverse(self, inp, min_height=32, min_width=64, min_fill=0.4, min_holes=3, max_hole=0, threshold=0.0, mask=False, info=False):
+        """ocrs_engine_unreverse_page: the page with its solid dark panels that enclose light marks (a table's header band, a
+        screenshot's buttons and sidebars, a dark code pane), and what they enclose, inverted by flipping the sign bit, as a
+        new resident page of the same size; every other pixel keeps its bits.  A candidate: an 8-connected component of ink
+        (< threshold) whose box is at least min_height x min_width and which fills at least min_fill of it.  A hole: a
+        4-connected component of everything outside the candidates that does not touch the page's edge; it counts when
+        max_hole is 0 or it has at most max_hole pixels.  A candidate that encloses at least min_holes counting holes is a
+        panel.  The five defaults are uncalibrated.  mask=True: also the uint8 [H, W] mask (bit 0 inverted, 1 candidate, 2
+        panel, 3 hole); info=True: also {"ink", "components", "candidates", "panels", "panel_pixels", "holes", "hole_pixels",
+        "skipped_holes", "inverted"}.  -> page, or (page[, mask][, info])."""
+        out = self.unreverse_batch([inp], [{"min_height": min_height, "min_width": min_width, "min_fill": min_fill, "min_holes": min_holes,
+                                            "max_hole": max_hole, "threshold": threshold}], mask=mask, info=info)
+        return tuple(o[0] for o in out) if mask or info else out[0]
+
+    def unreverse_batch(self, inputs, params=None, mask=False, info=False):
+        """ocrs_engine_unreverse_pages: pages of any sizes, each with its own parameters (a dict of unreverse's keywords, or
+        None for the default; one for all, or one per page), all passes for the whole batch on one stream.  -> pages, or
+        (pages[, masks][, infos])."""
+        return self._page_op_batch("unreverse", lib().ocrs_engine_unreverse_pages, _lib.ReverseParams, _reverse_struct, _lib.ReverseInfo,
+                                           inputs, params, mask, info)
+
     def text_scale(self, inp, min_height_strokes=None, **kw):
         """measure (keywords threshold, min_area) followed by measure_choose -> TextScale."""
         return measure_choose(self.measure(inp, **kw), min_height_strokes)
@@ -1840,7 +1891,7 @@ class OcrEngine:
     # ---- lib.rs:290-300
     def get_text(self, inp, rectify=False, orientation=None, work_size=None, normalize=None, deskew=None, deskew_fill=0.5,
                  perspective=None, perspective_fill=0.5, rules=None, despeckle=None, binarize=None, morph=None, frame=None, rank=None,
-                 work_text_height=None):
+                 work_text_height=None, unreverse=None):
         """rectify=True: the same sequence (detect_words, find_text_lines, recognize_text) with rectified crops.
         orientation: None reads the page as given; an int turns it by that many quarter turns counter-clockwise first
         (rotate); "auto" by what detect_orientation finds.
@@ -1880,6 +1931,10 @@ class OcrEngine:
         is N pixels (True: WORK_TEXT_HEIGHT_DEFAULT) tall.  The page is measured as the detector will
         see it, after every operation above; lines and text are read at full resolution, as with work_size.  Not together
         with work_size.
+        unreverse: None reads the page as given; True or a dict of unreverse()'s keywords reads the page with its
+        reverse-video panels inverted.  Applied after perspective, normalisation, grain removal and
+        binarisation and before frame, which would remove a sidebar that touches the edge as a bar; despeckling and
+        everything later then see one polarity.  Coordinates do not move.
         get_text returns text alone; callers that want boxes run the steps
         themselves and bring them back last with unproject_rects / unproject_lines."""
         if perspective is not None:
@@ -1890,6 +1945,8 @@ class OcrEngine:
             inp = self.rank(inp, **({} if rank is True else dict(rank)))
         if binarize is not None and binarize is not False:
             inp = self.binarize(inp, **({} if binarize is True else dict(binarize)))
+        if unreverse is not None and unreverse is not False:
+            inp = self.unreverse(inp, **({} if unreverse is True else dict(unreverse)))
         if frame is not None and frame is not False:
             inp = self.frame(inp, **({} if frame is True else dict(frame)))[0]
         if despeckle is not None and despeckle is not False:

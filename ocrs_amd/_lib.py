@@ -100,6 +100,7 @@ DECLARED_SYMBOLS = [
     "ocrs_engine_crop_page", "ocrs_engine_crop_pages", "ocrs_uncrop_rects", "ocrs_uncrop_chars",
     "ocrs_measure_params_default", "ocrs_measure_params_check", "ocrs_engine_measure_page", "ocrs_engine_measure_pages",
     "ocrs_measure_choice_params_default", "ocrs_measure_choice_params_check", "ocrs_measure_choose", "ocrs_work_scale_for_text",
+    "ocrs_reverse_params_default", "ocrs_reverse_params_check", "ocrs_engine_unreverse_page", "ocrs_engine_unreverse_pages",
 ]
 
 ABI_VERSION = 6   # include/ocrs_amd.h OCRS_ABI_VERSION
@@ -245,6 +246,19 @@ class MeasureChoiceParams(C.Structure):   # include/ocrs_amd.h ocrs_measure_choi
 
 class TextScaleC(C.Structure):   # include/ocrs_amd.h ocrs_text_scale
     _fields_ = [("stroke", C.c_int32), ("text_height", C.c_int32), ("support", C.c_uint32), ("blank", C.c_int32)]
+
+
+class ReverseParams(C.Structure):   # include/ocrs_amd.h ocrs_reverse_params
+    _fields_ = [("threshold", C.c_float), ("min_height", C.c_int32), ("min_width", C.c_int32), ("min_fill", C.c_float), ("min_holes", C.c_int32),
+                ("max_hole", C.c_int32)]
+
+
+class ReverseInfo(C.Structure):   # include/ocrs_amd.h ocrs_reverse_info
+    _fields_ = [("ink", C.c_uint64), ("components", C.c_uint64), ("candidates", C.c_uint64), ("panels", C.c_uint64), ("panel_pixels", C.c_uint64),
+                ("holes", C.c_uint64), ("hole_pixels", C.c_uint64), ("skipped_holes", C.c_uint64), ("inverted", C.c_uint64)]
+
+    def as_dict(self):
+        return {name: int(getattr(self, name)) for name, _ in self._fields_}
 
 
 class CropRect(C.Structure):   # include/ocrs_amd.h ocrs_crop_rect

@@ -16,8 +16,8 @@ CSRC = os.path.join(HERE, "csrc")
 OBJ = os.path.join(HERE, "_build")
 LIB = os.path.join(HERE, "libocrs_amd.so")
 
-SOURCES = ["common.cpp", "layout.cpp", "model_load.cpp", "model.cpp", "model_packed.cpp", "engine.cpp", "ctc_beam.cpp", "text_items.cpp", "abi.cpp", "abi_util.cpp", "orient.cpp", "resample.cpp", "normalize.cpp", "rules.cpp", "speckle.cpp", "binarize.cpp", "morph.cpp", "rank.cpp", "frame.cpp", "measure.cpp", "deskew.cpp", "perspective.cpp", "group.cpp", "jpeg_host.cpp", "kernels_jpeg.hip", "kernels_image.hip", "kernels_ccl.hip", "kernels_score.hip", "kernels_tile.hip",
-           "kernels_nn.hip", "kernels_det.hip", "kernels_det_stream.hip", "kernels_det_rows.hip", "kernels_gru.hip", "kernels_gru_split.hip", "kernels_lines.hip", "kernels_rectify.hip", "kernels_rotate.hip", "kernels_resample.hip", "kernels_normalize.hip", "kernels_rules.hip", "kernels_speckle.hip", "kernels_binarize.hip", "kernels_morph.hip", "kernels_rank.hip", "kernels_frame.hip", "kernels_measure.hip", "kernels_deskew.hip", "kernels_perspective.hip", "kernels_beam.hip", "kernels_rec.hip", "kernels_peaks.hip"]
+SOURCES = ["common.cpp", "layout.cpp", "model_load.cpp", "model.cpp", "model_packed.cpp", "engine.cpp", "ctc_beam.cpp", "text_items.cpp", "abi.cpp", "abi_util.cpp", "orient.cpp", "resample.cpp", "normalize.cpp", "rules.cpp", "speckle.cpp", "binarize.cpp", "morph.cpp", "rank.cpp", "frame.cpp", "measure.cpp", "reverse.cpp", "deskew.cpp", "perspective.cpp", "group.cpp", "jpeg_host.cpp", "kernels_jpeg.hip", "kernels_image.hip", "kernels_ccl.hip", "kernels_score.hip", "kernels_tile.hip",
+           "kernels_nn.hip", "kernels_det.hip", "kernels_det_stream.hip", "kernels_det_rows.hip", "kernels_gru.hip", "kernels_gru_split.hip", "kernels_lines.hip", "kernels_rectify.hip", "kernels_rotate.hip", "kernels_resample.hip", "kernels_normalize.hip", "kernels_rules.hip", "kernels_speckle.hip", "kernels_binarize.hip", "kernels_morph.hip", "kernels_rank.hip", "kernels_frame.hip", "kernels_measure.hip", "kernels_reverse.hip", "kernels_deskew.hip", "kernels_perspective.hip", "kernels_beam.hip", "kernels_rec.hip", "kernels_peaks.hip"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-fno-fast-math",
          "-fvisibility=hidden", "-Wall", "-Wno-unused-function", "-Wno-pass-failed"]
 

@@ -142,6 +142,25 @@ def main(argv=None):
     ap.add_argument("--speck-keep-near", type=int, default=None, metavar="N",
                     help="with --despeckle: keep a speck that lies within N pixels of larger ink, 0 to 16 (default 0: keep none); for "
                          "i-dots and full stops when --speck-max-area is large")
+    ap.add_argument("--unreverse", action="store_true",
+                    help="turn reverse-video regions to dark on light on the GPU before reading the page: solid dark panels that "
+                         "enclose light marks (a table's header band, the buttons and sidebars of a screenshot, a dark code pane) are "
+                         "inverted with what they enclose (after --normalize and --binarize, before --frame, which would remove a "
+                         "sidebar at the edge, and --despeckle); the JSON gains \"unreverse\" (no reference counterpart; the defaults "
+                         "and what a detector gains are uncalibrated: DESIGN.md 7.15)")
+    ap.add_argument("--unreverse-min-height", type=int, default=None, metavar="N",
+                    help="with --unreverse: the least height of a panel's box, 1 to 65535 pixels (default 32, uncalibrated)")
+    ap.add_argument("--unreverse-min-width", type=int, default=None, metavar="N",
+                    help="with --unreverse: the least width of a panel's box, 1 to 65535 pixels (default 64, uncalibrated)")
+    ap.add_argument("--unreverse-min-fill", type=float, default=None, metavar="X",
+                    help="with --unreverse: the least share of its box a panel's ink fills, 0 to 1 (default 0.4, uncalibrated); a table "
+                         "grid or a page frame fills less")
+    ap.add_argument("--unreverse-min-holes", type=int, default=None, metavar="N",
+                    help="with --unreverse: the enclosed light marks that make a dark region a panel (default 3, uncalibrated; it keeps "
+                         "a bold O, B or 8 out; 0 inverts solid bars too)")
+    ap.add_argument("--unreverse-max-hole", type=int, default=None, metavar="N",
+                    help="with --unreverse: an enclosed light region of more than N pixels (a light card with dark text of its own) is "
+                         "left as it is (default 0: no limit, uncalibrated)")
     ap.add_argument("--binarize", action="store_true",
                     help="cut the page into ink and paper on the GPU before reading it, by Sauvola's local threshold over a "
                          "window around every pixel instead of one cut for the page (after --normalize, before --despeckle, "
@@ -216,6 +235,11 @@ def main(argv=None):
         ap.error("--speck-max-area, --speck-fill-holes and --speck-keep-near are only valid with --despeckle")
     if (args.binarize_radius is not None or args.binarize_k is not None or args.binarize_keep_ink) and not args.binarize:
         ap.error("--binarize-radius, --binarize-k and --binarize-keep-ink are only valid with --binarize")
+    unreverse_kw = {key: getattr(args, "unreverse_" + key) for key in ("min_height", "min_width", "min_fill", "min_holes", "max_hole")
+                    if getattr(args, "unreverse_" + key) is not None}
+    if unreverse_kw and not args.unreverse:
+        ap.error("--unreverse-min-height, --unreverse-min-width, --unreverse-min-fill, --unreverse-min-holes and --unreverse-max-hole are "
+                 "only valid with --unreverse")
     morph_kw = None
     if args.morph is not None:
         import re
@@ -354,6 +378,20 @@ def main(argv=None):
             print("Binarize: %d of %d counted pixels are ink, written as %g (kept: %s); paper written as %g"
                   % (binarize_info["ink"], binarize_info["counted"], binarize_info["ink_fill"],
                      "yes" if args.binarize_keep_ink else "no", binarize_info["paper_fill"]))
+    unreverse_info = None
+    if args.unreverse:   # from here on the page of one polarity is the page; coordinates do not move
+        try:
+            inp, unreverse_info = engine.unreverse(inp, info=True, **unreverse_kw)
+        except OcrsError as e:
+            if e.status != 1:   # OCRS_ERR_INVALID_ARGUMENT: a parameter out of range
+                raise
+            ap.error("--unreverse: %s" % e)
+        if args.debug:
+            print("Unreverse: %d panels (%d pixels) of %d candidates among %d components of ink inverted with %d holes (%d pixels), "
+                  "%d holes over the limit left alone; %d pixels inverted, %d pixels of ink"
+                  % (unreverse_info["panels"], unreverse_info["panel_pixels"], unreverse_info["candidates"], unreverse_info["components"],
+                     unreverse_info["holes"], unreverse_info["hole_pixels"], unreverse_info["skipped_holes"], unreverse_info["inverted"],
+                     unreverse_info["ink"]))
     def read_part(inp):
         """One page from despeckling to recognition, its results back in the frame `inp` has here."""
         turn_hw = inp.shape[-2:]   # the frame the turn's results come back to
@@ -532,7 +570,7 @@ def main(argv=None):
         content = output.format_json_output(args.image, tuple(shape_hw), texts, confidence=args.confidence, word_boxes=word_boxes,
                                             orientation=None if turns is None else 90 * turns, normalize=norm_info, skew=skew, outline=outline,
                                             rules=rules_info, despeckle=speckle_info, binarize=binarize_info, morph=morph_info, frame=frame_info,
-                                            rank=rank_info, measure=measure_info)
+                                            rank=rank_info, measure=measure_info, unreverse=unreverse_info)
     else:
         content = output.format_text_output(texts)
     if args.output:

@@ -698,6 +698,50 @@ size_t measure_mask_words(int h, int w);    // 64-bit words of MeasureDesc::mask
 // Pages of any mix of sizes and parameters, five launches on `s`; total_blocks = the sum of measure_tiles() over the pages.
 void measure_pages(const MeasureDesc* d_descs, int n_pages, int total_blocks, hipStream_t s);
 
+// ---- kernels_reverse.hip ----------------------------------
+struct ReverseInfo {     // what a page's reverse-video repair found: the layout of ocrs_reverse_info
+    uint64_t ink;            // pixels under the threshold
+    uint64_t components;     // 8-connected components of ink
+    uint64_t candidates;     // those large and solid enough to be a panel
+    uint64_t panels;         // candidates that enclose at least min_holes counting holes
+    uint64_t panel_pixels;   // their pixels
+    uint64_t holes;          // counting holes of panels
+    uint64_t hole_pixels;    // their pixels
+    uint64_t skipped_holes;  // holes of panels larger than max_hole: left as they are
+    uint64_t inverted;       // panel_pixels + hole_pixels
+};
+constexpr int REVERSE_COUNTS = 32;   // 64-bit words of a block's record: [wave][8]
+constexpr int REVERSE_MAX_SIDE = 65535;
+constexpr int REVERSE_WORKSPACE_PER_PIXEL = 20;   // bytes: labels, area and three box words; and two bits of masks
+struct ReverseDesc {     // one page that is repaired: dst [h, w] from src [h, w]
+    const float* src;
+    float* dst;          // never overlaps src
+    unsigned long long* masks;   // 2 row-major bit masks of h * ww words (64 pixels a word, bits past the edge zero): ink, M
+    int32_t* labels;     // [h * w] two union-find forests over page-local pixel indices that never unite: the ink's (8-connected;
+                         // from pass 4 on kept on M alone) and, from pass 4 on, that of everything outside M (4-connected)
+    uint32_t* area;      // [h * w] at a root: the pixels of its component (ink until pass 4, outside M from pass 5 on)
+    uint32_t* x0;        // [h * w] at an ink root: the least x of its component; from pass 5 on, at a root outside M: 1 when
+                         // its component touches the page's edge
+    uint32_t* x1;        // [h * w] at an ink root: the largest x; from pass 5 on, at a root of M: its counting holes
+    uint32_t* y1;        // [h * w] at an ink root: the largest y; the least y is that of the root itself
+    unsigned long long* counts;  // [hw * ww, REVERSE_COUNTS] what each block counted
+    ReverseInfo* info;
+    uint8_t* mask_out;   // [h, w] the mask of include/ocrs_amd.h, or null
+    int32_t h, w;        // each 1 .. 65535, h * w < 2^31
+    int32_t ww, hw;      // ceil(w / 64), ceil(h / 64)
+    int32_t block0;      // first block of this page: the sum of hw * ww of the pages before it
+    int32_t min_height, min_width;   // 1 .. 65535
+    int32_t fill_q8;     // floor(256 min_fill + 0.5): 0 .. 256
+    int32_t min_holes, max_hole;     // >= 0; max_hole 0: no limit
+    float threshold;
+    int32_t vec;         // w % 4 == 0 and the buffers 16-byte aligned, so 16-byte accesses are safe
+};
+int64_t reverse_tiles(int h, int w);        // blocks a page of this size takes (host)
+size_t reverse_mask_words(int h, int w);    // 64-bit words of ReverseDesc::masks (host)
+int reverse_fill_q8(float min_fill);        // (host)
+// Pages of any mix of sizes and parameters, nine launches on `s`; total_blocks = the sum of reverse_tiles() over the pages.
+void unreverse_pages(const ReverseDesc* d_descs, int n_pages, int total_blocks, hipStream_t s);
+
 // kernels_peaks.hip
 void measure_peaks(double* mfma_tflops, double* copy_gbps);
 

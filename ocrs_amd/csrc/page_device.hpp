@@ -1,5 +1,5 @@
 // What the kernels of the page operations share on the device: kernels_normalize.hip, kernels_rules.hip,
-// kernels_speckle.hip, kernels_binarize.hip, kernels_morph.hip, kernels_frame.hip, kernels_rank.hip, kernels_measure.hip.  The grey-level bins are part of the bit-exact contract
+// kernels_speckle.hip, kernels_binarize.hip, kernels_morph.hip, kernels_frame.hip, kernels_rank.hip, kernels_measure.hip, kernels_reverse.hip.  The grey-level bins are part of the bit-exact contract
 // with tests/*_ref.py: they are defined here and nowhere else.
 #pragma once
 #include <hip/hip_runtime.h>

@@ -1,7 +1,8 @@
 // Page operations: what the calls that make new resident pages out of resident pages share: quarter
 // turns (orient.cpp), resampling (resample.cpp), normalisation (normalize.cpp), the deskew warp (deskew.cpp), rule removal
 // (rules.cpp), despeckling (speckle.cpp), adaptive binarisation (binarize.cpp), stroke repair
-// (morph.cpp), page framing (frame.cpp), grain removal (rank.cpp).  Not part of the public header.
+// (morph.cpp), page framing (frame.cpp), grain removal (rank.cpp), reverse-video repair (reverse.cpp).  Not part of the
+// public header.
 #pragma once
 #include <cstdlib>
 #include <limits>
@@ -50,7 +51,7 @@ inline bool vec16_ok(int w, const void* src, const void* dst) { return w % 4 == 
 // One launch for a batch of pages: a descriptor per page, whose block0 is the sum of the blocks of the pages before it;
 // a block finds its page with find_desc (find_desc.hpp).  The batch owns the pages it makes until release_into.
 //
-// A masked operation (rules.cpp, speckle.cpp, binarize.cpp, morph.cpp, frame.cpp's cleanup, rank.cpp) makes a page of its input's size and, per page, an
+// A masked operation (rules.cpp, speckle.cpp, binarize.cpp, morph.cpp, frame.cpp's cleanup, rank.cpp, reverse.cpp) makes a page of its input's size and, per page, an
 // info record and, if asked for, a byte mask; its descriptor has src, dst, h, w, counts, info and mask_out.  It calls
 // add_like for every page, then carve_outputs, fills in what is its own, and run_outputs.
 template <class Desc>

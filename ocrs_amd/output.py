@@ -15,7 +15,7 @@ def rounded_vertex_coords(rect6):
     return [[_rround(x), _rround(y)] for x, y in rotated_rect_corners(rect6)]
 
 
-def ocr_json(input_path, input_hw, text_lines, confidence=False, word_boxes=None, orientation=None, normalize=None, skew=None, outline=None, rules=None, despeckle=None, binarize=None, morph=None, frame=None, rank=None, measure=None):
+def ocr_json(input_path, input_hw, text_lines, confidence=False, word_boxes=None, orientation=None, normalize=None, skew=None, outline=None, rules=None, despeckle=None, binarize=None, morph=None, frame=None, rank=None, measure=None, unreverse=None):
     """output.rs:34-76.  text_lines: list of TextLine | None.  confidence (no reference counterpart): every line and word
     object also gets "confidence" (TextLine / TextWord.confidence; the lines must come from a scored recognize_text).
     word_boxes (no reference counterpart; indexed like text_lines): per line the detector's word boxes in reading order as
@@ -46,7 +46,10 @@ def ocr_json(input_path, input_hw, text_lines, confidence=False, word_boxes=None
     "ry", "spared", "tail"}.
     measure (no reference counterpart): the scale measure_choose made of OcrEngine.measure's record of the page the detector
     saw, with the record's ink and components; the top level then gets "measure": {"blank", "components", "ink", "stroke",
-    "support", "text_height"}; blank (a bool) says that no text was found to measure."""
+    "support", "text_height"}; blank (a bool) says that no text was found to measure.
+    unreverse (no reference counterpart): what OcrEngine.unreverse(info=True) found on the page; the top level then gets
+    "unreverse": {"candidates", "components", "hole_pixels", "holes", "ink", "inverted", "panel_pixels", "panels",
+    "skipped_holes"}."""
     line_items = []
     for li, line in enumerate(text_lines):
         if line is None:
@@ -89,14 +92,16 @@ def ocr_json(input_path, input_hw, text_lines, confidence=False, word_boxes=None
     if measure is not None:
         doc["measure"] = {k: int(measure[k]) for k in ("components", "ink", "stroke", "support", "text_height")}
         doc["measure"]["blank"] = bool(measure["blank"])
+    if unreverse is not None:
+        doc["unreverse"] = {k: int(v) for k, v in unreverse.items()}
     return doc
 
 
-def format_json_output(input_path, input_hw, text_lines, confidence=False, word_boxes=None, orientation=None, normalize=None, skew=None, outline=None, rules=None, despeckle=None, binarize=None, morph=None, frame=None, rank=None, measure=None):
+def format_json_output(input_path, input_hw, text_lines, confidence=False, word_boxes=None, orientation=None, normalize=None, skew=None, outline=None, rules=None, despeckle=None, binarize=None, morph=None, frame=None, rank=None, measure=None, unreverse=None):
     """output.rs:98-101 (serde_json::to_string_pretty).  serde_json without `preserve_order` keeps `json!` maps in a
     BTreeMap, so the reference emits every object's keys in alphabetical order (ocrs-cli/test-data/
     format-json-expected.json: image_height, image_width, paragraphs, url / text, vertices, words): sort_keys."""
-    return json.dumps(ocr_json(input_path, input_hw, text_lines, confidence, word_boxes, orientation, normalize, skew, outline, rules, despeckle, binarize, morph, frame, rank, measure), indent=2, ensure_ascii=False,
+    return json.dumps(ocr_json(input_path, input_hw, text_lines, confidence, word_boxes, orientation, normalize, skew, outline, rules, despeckle, binarize, morph, frame, rank, measure, unreverse), indent=2, ensure_ascii=False,
                       sort_keys=True)
 
 
